@@ -3,7 +3,13 @@
 
 One "step" = one pass of the hot path over one batch of synthetic reads that are already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline record alone: it builds the text, the reads and the plain index, warms up, times exactly K steps and prints the result line
+(`ms_per_step` = the milliseconds of one timed step).  --dump-outputs DIR then also writes what the last timed step returned (lb.npy, len.npy: float64; a batch
+too large for 64 MB as every s-th read, with row.npy naming them); the inputs are seeded, so two builds can be compared output for output.  Everything else
+below — the other records and texts, the protein indices, the CPU baseline, the depth profile, the card's clocks, the records file — is measured with --full,
+and the options that pick among those records (--only, --texts, --with-edit, ...) are accepted with --full only.
 
 Headline (`value`) = BASELINE.json configs[1]: exact search (search_no_errors) of 10 M x 101 bp reads on a GRCh38-sized FMIndex (25 sequences with
 the GRCh38 chromosome lengths, 3.09 Gbp, sigma = 5) — the PLAIN index north_star describes: the bit-packed occurrence table + sampled suffix array,
@@ -13,7 +19,7 @@ the optional tables is the named field `with_tables`.  The text is the repeat-st
 fmindex-collection_amd/datasets.py (45 % interspersed repeats, satellites, 5 % runs of one symbol) — or the real assembly when FMGPU_FASTA=<path> names
 one (reference loader rule, src/example/utils.h:86-98: unknown bases -> A).  The uniform-random text of SURVEY 8d-2 is measured next to it.
 
-At N = 1 the default run measures, one after the other in this process, for each text (`records`, every one driver-timed in the same run):
+At N = 1 a --full run measures, one after the other in this process, for each text (`records`, every one driver-timed in the same run):
     exact / plain     k_exact_p on the bit-packed occurrence tables alone (one-symbol blocks 4.2 GB + symbol-pair lines 3.1 GB — the index north_star
                       describes); roofline: executed LF steps x 68 B (2 interval ends x 68 B of a pair line per two-symbol step) / kernel time / 8 TB/s
     exact / single    k_exact_a, one symbol per step on the same index; roofline by SURVEY 8d as written:
@@ -28,12 +34,12 @@ on the one-line-per-step table the library keeps beside the tree, 88 B per LF st
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): the index is replicated (every rank builds the same seeded text), the query batch is
 sharded, the only exchange is the RCCL gather of the results to rank 0 inside the timed region (double-buffered: the gather of step i crosses xGMI
-while the kernel of step i+1 runs).  `value` = exact search on the plain index, 10 M reads PER RANK (weak scaling: per-GPU work fixed); `secondary` =
+while the kernel of step i+1 runs).  `value` = exact search on the plain index, 10 M reads PER RANK (weak scaling: per-GPU work fixed); `secondary` (--full) =
 configs[3]: k = 2 Hamming, 151 bp, partition {38,38,38,37}, 100 M reads in total sharded 100 M / N per rank (strong scaling), 24-byte packed hits gathered.
 
 Output (rank 0): the LAST line of stdout is ONE compact JSON line (< 4 KB: headline, roofline, cpu_baseline, and `summary` = record id ->
-[ms_per_step, roofline.frac]); every full record (config, accounting, exchange ...) goes to `bench_records.json` beside this file (or
-$FMGPU_BENCH_RECORDS) and, one short line per record, to stderr.  `cpu_baseline` = the CPU restatement (oracle/, parity-pinned) on the host
+[ms_per_step, roofline.frac]); one short line per record goes to stderr, and with --full every full record (config, accounting, exchange ...) to
+`bench_records.json` beside this file (or $FMGPU_BENCH_RECORDS).  `cpu_baseline` = the CPU restatement (oracle/, parity-pinned) on the host
 cores over a bounded sample of the same reads, NUMA-spread and thread-bound; it is a reported baseline, not the target.
 """
 import argparse
@@ -102,7 +108,17 @@ def parse():
     ap.add_argument("--multi-tables", action="store_true", help="N > 1: also measure the table-augmented indices (136 / 224 GB per GPU); default at N > 1: the plain index only")
     ap.add_argument("--opt", default="", help="library options for the whole run (fmgpu_set_option), e.g. pair_table=0,kernel_select=4194304 (A/B runs; the judged run sets none)")
     ap.add_argument("--total-k2-reads", type=int, default=100_000_000, help="N > 1: reads of the configs[3] leg in total (sharded over the ranks)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="every record, the CPU baseline, the depth profile and the card's clocks; without it only the headline record is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the headline's last timed step returned as DIR/<name>.npy (float64, at most 64 MB in all)")
+    args = ap.parse_args()
+    if not args.full:                                         # the options that pick or shape the other records mean nothing in a headline-only run
+        given = ["--" + k.replace("_", "-") for k in FULL_ONLY if getattr(args, k) != ap.get_default(k)]
+        if given:
+            ap.error("%s: only with --full (a plain run measures the headline record alone)" % ", ".join(given))
+    return args
+
+
+FULL_ONLY = ("texts", "only", "lut_len", "prefix_len", "with_edit", "cpu_sample", "multi_tables", "total_k2_reads")
 
 
 class _Dev:
@@ -169,7 +185,7 @@ def main():
     for kv in (x for x in args.opt.split(",") if x):             # A/B runs: library options for the whole run
         k, v = kv.split("=")
         fm.options[k.strip()] = int(v, 0)
-    c.smi = Smi(local_rank)
+    c.smi = Smi(local_rank if args.full else None)
     c.only = set(x for x in args.only.split(",") if x)
     c.traffic = {}
     for tf in ("r04_traffic.json", "r03_traffic.json", "r02_traffic.json"):           # per-launch HBM bytes from the committed rocprofv3 --pmc passes (replayed, labelled so)
@@ -184,10 +200,13 @@ def main():
     texts = [t for t in args.texts.split(",") if t] or (["genome"] if c.multi else ["genome", "uniform"])
     if fasta:
         texts = ["fasta" if t == "genome" else t for t in texts]
+    if not args.full:                                         # a plain run: the headline record alone
+        texts = texts[:1]
+        c.only = {texts[0] + HEADLINE_ID}
     records = []
     for name in texts:
         records += run_dna_text(c, name, primary=(name == texts[0]))
-    if not c.multi and not args.no_protein and args.scale == 1.0 and (not c.only or any(o.startswith("protein") for o in c.only)):
+    if args.full and not c.multi and not args.no_protein and args.scale == 1.0 and (not c.only or any(o.startswith("protein") for o in c.only)):
         records += run_protein(c, PROTEIN_SEQS, "protein")
         if not args.no_protein_wide:
             records += run_protein(c, PROTEIN_SEQS_WIDE, "protein_wide")
@@ -200,7 +219,7 @@ def main():
     records = [r for r in records if r is not None]
     if not records:
         raise SystemExit("bench.py: nothing was measured (check --only)")
-    emit(records, c.multi, world)
+    emit(records, c.multi, world, args.full)
     if c.multi:
         c.dist.destroy_process_group()
 
@@ -288,14 +307,15 @@ def compact_line(records, multi, records_file):
     return out
 
 
-def emit(records, multi, world):
-    path = os.environ.get("FMGPU_BENCH_RECORDS", os.path.join(ROOT, "bench_records.json"))
-    try:
-        with open(path, "w") as f:
-            json.dump({"n_gpus": world, "records": records}, f, indent=1)
-    except OSError as ex:
-        print("bench.py: could not write %s (%s)" % (path, ex), file=sys.stderr, flush=True)
-        path = None
+def emit(records, multi, world, full):
+    path = os.environ.get("FMGPU_BENCH_RECORDS", os.path.join(ROOT, "bench_records.json")) if full else None
+    if path:
+        try:
+            with open(path, "w") as f:
+                json.dump({"n_gpus": world, "records": records}, f, indent=1)
+        except OSError as ex:
+            print("bench.py: could not write %s (%s)" % (path, ex), file=sys.stderr, flush=True)
+            path = None
     for r in records:
         rf = r["roofline"]
         f3 = lambda v: "  -  " if v is None else "%.3f" % v
@@ -373,6 +393,23 @@ def wanted(c, rid):
     return not c.only or rid in c.only
 
 
+DUMP_BYTES = 64_000_000           # --dump-outputs: the files of one run hold at most this many bytes
+
+
+def dump_outputs(c, arrays):
+    """--dump-outputs DIR: the arrays of one step (equal lengths) as DIR/<name>.npy in float64 (exact below 2^53); should they not fit in DUMP_BYTES,
+    every s-th entry, the same fixed rows of each, with the row numbers themselves in DIR/row.npy"""
+    np, torch = c.np, c.torch
+    n = int(next(iter(arrays.values())).numel())
+    stride = -(-n * 8 * (len(arrays) + 1) // DUMP_BYTES) if n * 8 * len(arrays) > DUMP_BYTES else 1
+    rows = torch.arange(0, n, stride, device=c.dev)
+    os.makedirs(c.args.dump_outputs, exist_ok=True)
+    if stride > 1:
+        arrays = {"row": rows, **{k: v[rows] for k, v in arrays.items()}}
+    for k, v in arrays.items():
+        np.save(os.path.join(c.args.dump_outputs, k + ".npy"), v.cpu().numpy().astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------------------- timing
 def timed(c, step, drain=None):
     """W warm-up steps, then exactly K steps between barrier + synchronize on both sides; returns (seconds [max over ranks], per-step stats)"""
@@ -416,7 +453,8 @@ def timed(c, step, drain=None):
 
 class Smi:
     """clocks and power of the card WHILE the timed steps run (librocm_smi64 through ctypes, sampled every 2 ms by a thread): the figures that attribute a box-to-box
-    spread of the same kernel on the same input (10.8 vs 11.7 ms) to the clock the box ran at.  Reports nothing where the library is not usable."""
+    spread of the same kernel on the same input (10.8 vs 11.7 ms) to the clock the box ran at.  Reports nothing where the library is not usable,
+    or when dev is None (a run without --full)."""
 
     class _Freq(ctypes.Structure):                                # rsmi_frequencies_t (rocm_smi.h)
         _fields_ = [("has_deep_sleep", ctypes.c_bool), ("num_supported", ctypes.c_uint32), ("current", ctypes.c_uint32), ("frequency", ctypes.c_uint64 * 33)]
@@ -424,7 +462,7 @@ class Smi:
     def __init__(self, dev):
         import ctypes as C
         self.dev, self.lib, self.samples, self.thread, self.stop_flag = dev, None, [], None, False
-        for path in ("/opt/rocm/lib/librocm_smi64.so", "librocm_smi64.so", "librocm_smi64.so.1"):
+        for path in ("/opt/rocm/lib/librocm_smi64.so", "librocm_smi64.so", "librocm_smi64.so.1") if dev is not None else ():
             try:
                 L = C.CDLL(path)
                 if L.rsmi_init(C.c_uint64(0)) == 0:
@@ -608,7 +646,7 @@ def run_dna_text(c, name, primary):
     total = int(text.numel())
     out = []
     nq = args.nq
-    want_cpu = primary and c.rank == 0 and not c.multi and not args.no_cpu_baseline
+    want_cpu = args.full and primary and c.rank == 0 and not c.multi and not args.no_cpu_baseline
     base_cfg = {"text": tinfo, "sigma": 5, "layout": "InterleavedBitvector16", "scale": args.scale}
 
     # ------------------------------------------------------------------ exact search, configs[1]
@@ -730,11 +768,17 @@ def run_dna_text(c, name, primary):
             step([])                                              # the rows come from the exact search
         if wanted(c, name + "/exact/plain"):                      # the headline: at N > 1 too (same index, same kernel at every N; weak scaling)
             elapsed, log = timed(c, step, xch.drain if xch else None)
+            if args.dump_outputs and primary and c.rank == 0:   # what search_no_errors::search returned in the headline's last timed step (at N > 1: rank 0's share)
+                if xch:
+                    w = packed[(state["i"] - 1) % 2]
+                    dump_outputs(c, {"lb": (w >> 32) & 0xffffffff, "len": w & 0xffffffff})
+                else:
+                    dump_outputs(c, {"lb": outs[0][:nq], "len": outs[0][nq:]})
             r = finish(name + "/exact/plain", "plain", "k_exact_p" if pairs else "k_exact_a", elapsed, log, build_plain,
                        {"tables": None, "occurrence_tables": "one-symbol blocks (Format A) + symbol-pair lines (Format P)" if pairs else "one-symbol blocks (Format A)"})
             plain_ms = r["roofline"]["kernel_ms"]
 
-            if c.rank == 0 and not c.multi:                     # the distribution the judge asked for: symbols until the interval is one row
+            if args.full and c.rank == 0 and not c.multi:       # the depth profile: symbols until the interval is one row
                 depth = torch.empty(nq, dtype=torch.int32, device=c.dev)
                 capi.check(capi.lib().fmgpu_search_exact_depth(index._h, C.c_void_p(qbuf.data_ptr()), C.c_void_p(qoff.data_ptr()), nq, C.c_void_p(depth.data_ptr()), None))
                 d = depth.to(torch.float32)

@@ -10,8 +10,10 @@
                          FMIndex<28, Wavelet> case and EPR / EPRV2 / EPRV5 / Prefix16 cases — computed with the REAL reference's rank.
   ref_schemes.json       search-scheme tables produced by the real reference (h2, pigeon_opt, backtracking, expand,
                          limitToHamming, isValid, isComplete, nodeCount, createUniformPartition).
+  ref_strings_live.json  digests of what the real reference's occurrence-table types answer (block arrays, rank, prefix_rank,
+                         symbol) on the seeded texts of test_strings_live_against_real_reference, every layout it builds.
 
-    python tests/golden/make_golden.py [--tests-only]
+    python tests/golden/make_golden.py [--tests-only | --live-strings]
 """
 import json
 import os
@@ -303,6 +305,58 @@ def ref_vectors():
     return strings, schemes
 
 
+def live_string_cases(layout):
+    """the texts of tests/test_oracle_golden.py::test_strings_live_against_real_reference, in its order: (sigma, n, text, indices probed)
+    — including the 16-bit super-block boundaries"""
+    rng = np.random.default_rng(11)
+    sizes = [0, 1, 63, 64, 65, 255, 256, 257, 1000]
+    if "16" in layout or layout == "WAVELET":
+        sizes += [65519, 65520, 65536, 65537]
+    for sigma in (4, 5, 28):
+        for n in sizes:
+            if n > 10000 and sigma != 5:
+                continue
+            text = rng.integers(0, sigma, size=n, dtype=np.uint8)
+            idxs = list(range(n + 1)) if n <= 1000 else list(range(0, n + 1, 997)) + [n - 1, n, 65535, 65536][: 2 + 2 * (n >= 65536)]
+            yield sigma, n, text, idxs
+
+
+def _digest(*arrays):
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.asarray(a)
+        h.update(repr(a.shape).encode())
+        h.update(np.ascontiguousarray(a.astype("<u8")).tobytes())
+    return h.hexdigest()[:24]
+
+
+def string_digests(s, layout, sigma, n, idxs):
+    """what the live comparison compares, as digests: the block arrays (shape and values), rank and prefix_rank at every probed index and
+    symbol, and every symbol"""
+    d = {"rank": _digest(np.array([[s.rank(i, c) for c in range(sigma)] for i in idxs], dtype=np.uint64).reshape(len(idxs), sigma)),
+         "prefix_rank": _digest(np.array([[s.prefix_rank(i, c) for c in range(sigma)] for i in idxs], dtype=np.uint64).reshape(len(idxs), sigma)),
+         "symbol": _digest(np.array([s.symbol(i) for i in idxs if i < n], dtype=np.uint64))}
+    if layout != "WAVELET":
+        d["blocks"] = [_digest(a) for a in s.block_fields()]
+    return d
+
+
+def live_string_vectors():
+    """the answers of the reference headers compiled in place (oracle/_ref/libfmref.so) on the texts of live_string_cases, for every layout it builds"""
+    import fmoracle as fo
+    if not fo.ref_available():
+        raise SystemExit("oracle/_ref/libfmref.so missing: run `make -C oracle ref` first")
+    out = {}
+    for layout in (l for l in fo.LAYOUTS if l not in fo.REF_UNBUILDABLE):
+        out[layout] = [{"sigma": sigma, "n": n, **string_digests(fo.RefString(layout, sigma, text), layout, sigma, n, idxs)}
+                       for sigma, n, text, idxs in live_string_cases(layout)]
+    with open(os.path.join(HERE, "ref_strings_live.json"), "w") as f:
+        json.dump({"_provenance": "produced by the real reference headers via oracle/_ref/libfmref.so (tests/golden/make_golden.py live_string_vectors): "
+                                  "sha-256 (first 24 hex digits) of each answer array on the texts of live_string_cases", "layouts": out}, f, separators=(",", ":"))
+    return out
+
+
 REF_SEARCH_CASES = {    # name: (layout, sigma, text symbols, text seed, reads, read length)
     "config0_ib16": ("IB16", 5, 1_000_000, 42, 10_000, 31),          # BASELINE.json configs[0]
     "protein_wavelet": ("WAVELET", 28, 300_000, 7, 3_000, 40),        # configs[4] in small: FMIndex<28, Wavelet>, 40 aa
@@ -349,7 +403,11 @@ def main():
         with open(os.path.join(HERE, "reference_tests.json"), "w") as f:
             json.dump(reference_tests(), f, separators=(",", ":"))
         return
+    if "--live-strings" in sys.argv:                             # only ref_strings_live.json (needs oracle/_ref)
+        live_string_vectors()
+        return
     ref_search_intervals()
+    live_string_vectors()
     with open(os.path.join(HERE, "reference_tests.json"), "w") as f:
         json.dump(reference_tests(), f, separators=(",", ":"))
     strings, schemes = ref_vectors()

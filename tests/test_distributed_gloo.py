@@ -65,7 +65,7 @@ def test_bench_two_ranks_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.02",
+                        "--master-port", "29533", os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.02",
                         "--nq", "200000", "--total-k2-reads", "100000", "--lut-len", "10", "--prefix-len", "11", "--dist-backend", "gloo", "--all-ranks-device0"], capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1 and r.stdout.rstrip().endswith(lines[0]), r.stdout[-500:] + r.stderr[-1500:]

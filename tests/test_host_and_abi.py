@@ -249,6 +249,41 @@ def test_bench_line_is_compact():
     assert len(line) < bench.MAX_LINE and json.loads(line)["roofline"]["kernel"] == "k_scheme_fast_edit"
 
 
+def test_bench_plain_run_options_and_dumped_outputs(monkeypatch, tmp_path):
+    """a plain bench.py run measures the headline alone: the options that pick other records are refused without --full; --dump-outputs writes
+    float64 .npy files, all of a small batch, a fixed every-s-th sample of one that would not fit the byte budget (with its row numbers)"""
+    import argparse
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    for argv in (["--only", "genome/k2/plain"], ["--texts", "uniform"], ["--with-edit"], ["--lut-len", "12"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse()
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--full"] + argv)
+        assert bench.parse().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path), "--no-cpu-baseline"])
+    a = bench.parse()
+    assert (a.full, a.steps, a.warmup, a.dump_outputs) == (False, 7, 2, str(tmp_path))
+
+    c = bench.Ctx()
+    c.np, c.torch, c.dev = np, torch, torch.device("cpu")
+    lb = torch.arange(1000, dtype=torch.int64) * 3_000_000_007 % (1 << 40)
+    ln = torch.arange(1000, dtype=torch.int64) % 7
+    c.args = argparse.Namespace(dump_outputs=str(tmp_path / "all"))
+    bench.dump_outputs(c, {"lb": lb, "len": ln})
+    assert sorted(os.listdir(tmp_path / "all")) == ["lb.npy", "len.npy"]
+    got = np.load(tmp_path / "all" / "lb.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), lb.numpy()) and np.array_equal(np.load(tmp_path / "all" / "len.npy"), ln.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2400)
+    c.args = argparse.Namespace(dump_outputs=str(tmp_path / "sample"))
+    bench.dump_outputs(c, {"lb": lb, "len": ln})
+    rows = np.load(tmp_path / "sample" / "row.npy").astype(np.int64)
+    assert np.array_equal(rows, np.arange(0, 1000, 10))
+    assert np.array_equal(np.load(tmp_path / "sample" / "lb.npy"), lb.numpy()[rows]) and np.array_equal(np.load(tmp_path / "sample" / "len.npy"), ln.numpy()[rows])
+    assert sum(np.load(tmp_path / "sample" / f).nbytes for f in os.listdir(tmp_path / "sample")) <= 2400
+
+
 def test_options_are_set_through_the_abi_not_the_environment(monkeypatch):
     """fmgpu_set_option / fmgpu_get_option (include/fmgpu.h): defaults, round trip, unknown options and selection bits outside FMGPU_SEL_ALL are refused;
     the shipped library reads no environment variable (an FMGPU_* variable in the environment changes nothing)"""

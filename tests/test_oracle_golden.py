@@ -9,11 +9,13 @@ import pytest
 
 import fmoracle as fo
 from tests.util import make_text, occurrences, sample_reads
+from tests.golden.make_golden import live_string_cases, string_digests
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 REF = json.load(open(os.path.join(GOLD, "reference_tests.json")))
 REFSTR = json.load(open(os.path.join(GOLD, "ref_strings.json")))
 REFSCH = json.load(open(os.path.join(GOLD, "ref_schemes.json")))
+REFLIVE = json.load(open(os.path.join(GOLD, "ref_strings_live.json")))["layouts"]
 
 ALL_LAYOUTS = list(fo.LAYOUTS)
 
@@ -110,30 +112,16 @@ def test_flattened_bitvectors_against_text_counts(layout):
                 assert s.rank(i, c) == naive_rank(text, i, c) and s.prefix_rank(i, c) == naive_prefix(text, i, c)
 
 
-@pytest.mark.skipif(not fo.ref_available(), reason="oracle/_ref/libfmref.so not built (needs /root/reference)")
 @pytest.mark.parametrize("layout", [l for l in ALL_LAYOUTS if l not in fo.REF_UNBUILDABLE])
 def test_strings_live_against_real_reference(layout):
-    """direct comparison with the reference headers compiled in place, incl. the 16-bit super-block boundaries"""
-    rng = np.random.default_rng(11)
-    sizes = [0, 1, 63, 64, 65, 255, 256, 257, 1000]
-    if "16" in layout or layout == "WAVELET":
-        sizes += [65519, 65520, 65536, 65537]
-    for sigma in (4, 5, 28):
-        for n in sizes:
-            if n > 10000 and sigma != 5:
-                continue
-            text = rng.integers(0, sigma, size=n, dtype=np.uint8)
-            o, r = fo.OraString(layout, sigma, text), fo.RefString(layout, sigma, text)
-            if layout != "WAVELET":
-                for a, b in zip(o.block_fields(), r.block_fields()):
-                    assert a.shape == b.shape and np.array_equal(a, b), (layout, sigma, n)
-            idxs = range(n + 1) if n <= 1000 else list(range(0, n + 1, 997)) + [n - 1, n, 65535, 65536][: 2 + 2 * (n >= 65536)]
-            for i in idxs:
-                for c in range(sigma):
-                    assert o.rank(i, c) == r.rank(i, c), (layout, sigma, n, i, c)
-                    assert o.prefix_rank(i, c) == r.prefix_rank(i, c), (layout, sigma, n, i, c)
-                if i < n:
-                    assert o.symbol(i) == r.symbol(i)
+    """comparison with the answers of the reference headers compiled in place (recorded in ref_strings_live.json by make_golden.py), incl. the
+    16-bit super-block boundaries: the block arrays (shape and values), rank and prefix_rank at every probed index and symbol, every symbol"""
+    want = REFLIVE[layout]
+    got = [(sigma, n, string_digests(fo.OraString(layout, sigma, text), layout, sigma, n, idxs)) for sigma, n, text, idxs in live_string_cases(layout)]
+    assert [(w["sigma"], w["n"]) for w in want] == [(sigma, n) for sigma, n, _ in got]
+    for w, (sigma, n, d) in zip(want, got):
+        for k in ("blocks", "rank", "prefix_rank", "symbol"):
+            assert d.get(k) == w.get(k), (layout, sigma, n, k)
 
 
 # ------------------------------------------------------------------------------------------------ search schemes

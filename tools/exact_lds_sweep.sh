@@ -8,6 +8,6 @@ OUT=$R/gpurun_out/ldssweep_$TAG.log
 for lds in ${@:-0 16384 24576 32768 40960}; do
   export FMGPU_DEV_EXACT_LDS=$lds
   echo "== lds=$lds" >> $OUT
-  python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --only $REC 2>> $OUT > /dev/null || echo "FAILED" >> $OUT
+  python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --only $REC 2>> $OUT > /dev/null || echo "FAILED" >> $OUT
 done
 grep -E "^==|bench.py: |FAILED" $OUT

@@ -5,6 +5,6 @@ ONLY=genome/k2/tables,genome/k2_151/tables,uniform/k2/tables,genome/k2_edit/tabl
 for rep in 1 2; do
   for f in 0 128; do
     echo "== FMGPU_DEV_FLAGS=$f rep $rep"
-    FMGPU_DEV_FLAGS=$f python bench.py --steps 5 --warmup 1 --with-edit --only $ONLY 2>&1 >/dev/null | grep "ms/step"
+    FMGPU_DEV_FLAGS=$f python bench.py --full --steps 5 --warmup 1 --with-edit --only $ONLY 2>&1 >/dev/null | grep "ms/step"
   done
 done

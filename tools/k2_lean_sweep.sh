@@ -7,6 +7,6 @@ OUT=$R/gpurun_out/leansweep_$TAG.log
 : > $OUT
 for cfg in "$@"; do
   echo "== $cfg" >> $OUT
-  env $cfg python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --texts genome --only genome/k2/plain,genome/k2_151/plain 2>> $OUT > /dev/null || echo "FAILED $cfg" >> $OUT
+  env $cfg python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --texts genome --only genome/k2/plain,genome/k2_151/plain 2>> $OUT > /dev/null || echo "FAILED $cfg" >> $OUT
 done
 grep -E "^==|bench.py: genome|FAILED" $OUT

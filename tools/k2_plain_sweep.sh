@@ -12,6 +12,6 @@ for cfg in "bpc=7" "bpc=6" "bpc=5" "bpc=4" "old=1"; do
     old=1) export FMGPU_DEV_FLAGS=$((1<<30));;
   esac
   echo "== $cfg" >> $OUT
-  python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --texts genome --only genome/k2/plain,genome/k2_151/plain "$@" 2>> $OUT > /dev/null || echo "FAILED $cfg" >> $OUT
+  python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --texts genome --only genome/k2/plain,genome/k2_151/plain "$@" 2>> $OUT > /dev/null || echo "FAILED $cfg" >> $OUT
 done
 grep -E "^==|bench.py: genome|FAILED" $OUT

@@ -8,6 +8,6 @@ OUT=$R/gpurun_out/locsweep_$TAG.log
 for lds in 0 16384 24576 36864 49152; do
   export FMGPU_DEV_LOCATE_LDS=$lds
   echo "== lds=$lds" >> $OUT
-  python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-protein --texts genome --only genome/locate/plain "$@" 2>> $OUT > /dev/null || echo "FAILED" >> $OUT
+  python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-protein --texts genome --only genome/locate/plain "$@" 2>> $OUT > /dev/null || echo "FAILED" >> $OUT
 done
 grep -E "^==|bench.py: genome|FAILED" $OUT
