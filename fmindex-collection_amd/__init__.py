@@ -14,10 +14,10 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import FmgpuError, DeviceBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE
+from .capi import FmgpuError, DeviceBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE
 from . import search_scheme  # noqa: F401
 
-__all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "LocateLinear",
+__all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "LocateLinear", "search_locate",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options"]
 
 
@@ -76,6 +76,13 @@ def flatten(sequences):
 
 def _u64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.uint64))
+
+
+def _buffer(a):
+    """(void*, bytes) of a numpy array, a DeviceBuffer / (ptr, nbytes) device view or a torch tensor (its memory in place)"""
+    if hasattr(a, "data_ptr") and hasattr(a, "element_size"):
+        return C.c_void_p(a.data_ptr()), a.numel() * a.element_size()
+    return capi.ptr(a), a.nbytes
 
 
 class _StringArrays:
@@ -342,6 +349,34 @@ class FMIndex:
         capi.check(capi.lib().fmgpu_locate(self._h, capi.ptr(rows), rows.size, capi.ptr(seq), capi.ptr(pos), capi.ptr(steps),
                                            C.byref(st) if want_stats else None, None))
         return (seq, pos, steps, st) if want_stats else (seq, pos, steps)
+
+
+    def locate_hits(self, hits, capacity=None, want_stats=False, out=None, stream=None):
+        """every row of every hit record located in one call (fmgpu_locate_hits): the loop over LocateLinear{index, cursor} of fmc::Search for a
+        whole batch.  hits = HIT_DTYPE array, DeviceBuffer or torch tensor (in HBM: used in place).  Returns a POSITION_DTYPE array, one record per
+        row — hits in the given order, inside a hit rows lb .. lb + len - 1.  out = a device buffer / tensor to write the records into instead
+        (then the record count is returned); stream = a hipStream_t (int) or a torch stream."""
+        if isinstance(hits, np.ndarray):
+            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        hp, hbytes = _buffer(hits)
+        count = hbytes // HIT_DTYPE.itemsize
+        st, cnt = capi.Stats(), C.c_uint64()
+        sp = None if stream is None else C.c_void_p(stream if isinstance(stream, int) else getattr(stream, "cuda_stream", 0))
+        if out is not None:
+            op, obytes = _buffer(out)
+            capi.check(capi.lib().fmgpu_locate_hits(self._h, hp, count, op, obytes // POSITION_DTYPE.itemsize, C.byref(cnt),
+                                                    C.byref(st) if want_stats else None, sp))
+            return (cnt.value, st) if want_stats else cnt.value
+        cap = capacity if capacity is not None else max(1024, 4 * count)
+        for _ in range(2):                                            # once more with the size the call reported
+            res = np.zeros(max(cap, 1), dtype=POSITION_DTYPE)
+            rc = capi.lib().fmgpu_locate_hits(self._h, hp, count, capi.ptr(res), cap, C.byref(cnt), C.byref(st) if want_stats else None, sp)
+            if rc != capi.FMGPU_ERR_CAPACITY:
+                break
+            cap = int(cnt.value)
+        capi.check(rc)
+        res = res[: cnt.value]
+        return (res, st) if want_stats else res
 
 
 class BiFMIndex(FMIndex):
@@ -668,3 +703,77 @@ class LocateLinear:
     def __call__(self):
         seq, pos, steps = self.index.locate(self.rows)
         return self.owner, seq, pos, steps
+
+
+def _device_hits(index, qbuf, qoff, nq, scheme, n, edit):
+    """search_ng26 over one batch with the hit records left in HBM and put into callback order there: (DeviceBuffer, count)"""
+    pi, l, u = (_u64(x) for x in scheme)
+    sc = capi.Scheme()
+    sc.n_searches, sc.n_parts = pi.shape
+    sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
+    sc.partition, sc.edit = None, 1 if edit else 0
+    cap, cnt = max(1024, 4 * nq), C.c_uint64()
+    for _ in range(2):
+        buf = DeviceBuffer(cap * HIT_DTYPE.itemsize)
+        rc = capi.lib().fmgpu_search_scheme(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(sc), n, capi.ptr(buf), cap, C.byref(cnt), None, None)
+        if rc != capi.FMGPU_ERR_CAPACITY:
+            break
+        buf.free()
+        cap = int(cnt.value)
+    capi.check(rc)
+    capi.check(capi.lib().fmgpu_hits_sort(capi.ptr(buf), cnt.value, None))
+    return buf, int(cnt.value)
+
+
+def _device_positions(index, hits, count):
+    """fmgpu_locate_hits from hit records in HBM into HBM; one copy of the records to the host"""
+    if count == 0:
+        return np.zeros(0, dtype=POSITION_DTYPE)
+    cap, cnt = max(1024, 4 * count), C.c_uint64()
+    for _ in range(2):
+        out = DeviceBuffer(cap * POSITION_DTYPE.itemsize)
+        rc = capi.lib().fmgpu_locate_hits(index._h, capi.ptr(hits), count, capi.ptr(out), cap, C.byref(cnt), None, None)
+        if rc != capi.FMGPU_ERR_CAPACITY:
+            break
+        out.free()
+        cap = int(cnt.value)
+    capi.check(rc)
+    return out.to_array(POSITION_DTYPE, int(cnt.value))
+
+
+def search_locate(index, queries, errors, n=UINT64_MAX, edit=True, compat_auto_scheme=False):
+    """fmc::Search{index, queries, editDistance=edit, errors, maxResults=n}() (search/search.h:48-75): search, then every row of every reported
+    cursor located — what the reference reports as reportFunc(qidx, seqId, pos + offset, errors), in the same order and with the same duplicates.
+    The k > 0 pipeline keeps the hit records in HBM (search_ng26 -> fmgpu_hits_sort -> fmgpu_locate_hits); the only copy to the host is the
+    result: an array of (qidx, seq_id, pos, errors) records.  n = maxResults (UINT64_MAX = none: fmc::search, else fmc::search_n)."""
+    fields = ["qidx", "seq_id", "pos", "errors"]
+    if errors == 0 and n == UINT64_MAX:                       # search_no_errors: one cursor per query, its {lb, len} come back anyway
+        hits = search(index, queries, 0)
+        return index.locate_hits(hits)[fields]
+    qbuf, qoff, nq = _queries(queries)
+    if not isinstance(qoff, np.ndarray):                      # the length classes are split on the host, as in _auto_scheme_search
+        qoff = qoff.to_array(np.uint64, nq + 1) if isinstance(qoff, DeviceBuffer) else np.asarray(qoff)
+    if not isinstance(qbuf, np.ndarray):
+        qbuf = qbuf.to_array(np.uint8, int(qoff[-1]))
+    lens = np.diff(qoff.astype(np.int64))
+    parts = []
+    for short in (False, True):
+        sel = np.nonzero((lens == 2) == short)[0]
+        if sel.size == 0:
+            continue
+        sc = search_scheme.h2(errors + (1 if short else 2), 0, errors)
+        if compat_auto_scheme and not edit:
+            sc = search_scheme.limitToHamming(sc)
+        qb, qo = (qbuf, qoff) if sel.size == nq else flatten([qbuf[int(qoff[i]): int(qoff[i + 1])] for i in sel])
+        hits, count = _device_hits(index, qb, qo, sel.size, sc, n, edit)
+        pos = _device_positions(index, hits, count)
+        hits.free()
+        if sel.size != nq:
+            pos["qidx"] = sel.astype(np.uint64)[pos["qidx"].astype(np.int64)]
+        parts.append(pos)
+    if not parts:
+        return np.zeros(0, dtype=POSITION_DTYPE)[fields]
+    pos = parts[0] if len(parts) == 1 else np.concatenate(parts)
+    if len(parts) > 1:
+        pos = pos[np.argsort(pos["qidx"], kind="stable")]     # the two length classes hold different queries: ascending qidx, each query's rows in order
+    return pos[fields]

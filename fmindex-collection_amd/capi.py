@@ -73,6 +73,15 @@ HIT_DTYPE = np.dtype([("qidx", "<u8"), ("lb", "<u8"), ("lb_rev", "<u8"), ("len",
 assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 40
 
 
+class Position(C.Structure):
+    """fmgpu_position: one located row of a hit record (fmgpu_locate_hits)"""
+    _fields_ = [("qidx", C.c_uint64), ("seq_id", C.c_uint64), ("pos", C.c_uint64), ("errors", C.c_uint32), ("hit", C.c_uint32)]
+
+
+POSITION_DTYPE = np.dtype([("qidx", "<u8"), ("seq_id", "<u8"), ("pos", "<u8"), ("errors", "<u4"), ("hit", "<u4")])
+assert POSITION_DTYPE.itemsize == C.sizeof(Position) == 32
+
+
 class Scheme(C.Structure):
     _fields_ = [("n_searches", C.c_int32), ("n_parts", C.c_int32), ("pi", u64p), ("l", u64p), ("u", u64p),
                 ("partition", u64p), ("edit", C.c_int32), ("reserved", C.c_int32)]
@@ -91,7 +100,7 @@ class Stats(C.Structure):
 EXPORTS = [
     "fmgpu_abi_version", "fmgpu_last_error", "fmgpu_device_count", "fmgpu_set_device",
     "fmgpu_index_create", "fmgpu_index_destroy", "fmgpu_index_info", "fmgpu_string_query",
-    "fmgpu_search_exact", "fmgpu_search_exact_packed", "fmgpu_search_scheme", "fmgpu_search_ng21", "fmgpu_search_backtracking", "fmgpu_locate",
+    "fmgpu_search_exact", "fmgpu_search_exact_packed", "fmgpu_search_scheme", "fmgpu_search_ng21", "fmgpu_search_backtracking", "fmgpu_locate", "fmgpu_locate_hits",
     "fmgpu_malloc", "fmgpu_free", "fmgpu_memcpy_h2d", "fmgpu_memcpy_d2h", "fmgpu_synchronize",
     "fmgpu_build_index", "fmgpu_built_free", "fmgpu_built_get", "fmgpu_index_accelerate", "fmgpu_index_accelerate_search",
     "fmgpu_index_accelerate_exact", "fmgpu_index_accelerate_locate", "fmgpu_hits_sort", "fmgpu_hits_pack16",
@@ -172,6 +181,7 @@ def lib():
                                             C.c_void_p, C.c_uint64, u64p, C.POINTER(Stats), C.c_void_p]
     L.fmgpu_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(Stats), C.c_void_p]
+    L.fmgpu_locate_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.POINTER(Stats), C.c_void_p]
     if hasattr(L, "fmgpu_index_accelerate"):
         L.fmgpu_index_accelerate.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(L, "fmgpu_hits_pack16"):

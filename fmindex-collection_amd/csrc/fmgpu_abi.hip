@@ -278,6 +278,11 @@ int fmgpu_search_backtracking(fmgpu_index_t h, const uint8_t* qbuf, const uint64
 int fmgpu_locate(fmgpu_index_t h, const uint64_t* rows, uint64_t count, uint64_t* out_seq, uint64_t* out_pos, uint64_t* out_steps, fmgpu_stats* stats, void* stream) {
     ROUTE(h, fmgpu_locate(h, rows, count, out_seq, out_pos, out_steps, stats, stream));
 }
+int fmgpu_locate_hits(fmgpu_index_t h, const fmgpu_hit* hits, uint64_t count, fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                      fmgpu_stats* stats, void* stream) {
+    if (count && (!hits || !out || !out_count)) return fail(FMGPU_ERR_INVALID, "hits / out / out_count is null");
+    ROUTE(h, fmgpu_locate_hits(h, hits, count, out, capacity, out_count, stats, stream));
+}
 int fmgpu_cursor_extend(fmgpu_index_t h, int32_t direction, uint64_t count, const uint64_t* lb, const uint64_t* lb_rev, const uint64_t* len, const uint8_t* symb,
                         uint64_t* out_lb, uint64_t* out_lb_rev, uint64_t* out_len, void* stream) {
     ROUTE(h, fmgpu_cursor_extend(h, direction, count, lb, lb_rev, len, symb, out_lb, out_lb_rev, out_len, stream));

@@ -3,26 +3,79 @@
 //  k_locate_fused  fused presence bits, one row per lane
 //  k_locate        any layout (presence-bit probe + LF step), or the explicit LF table
 //  k_locate_tab    the per-row answer table (fmgpu_index_accelerate_locate)
+// Every kernel reads its rows from a row source: fmgpu_locate's array of rows with three answer arrays (RowArray), or fmgpu_locate_hits's hit records, whose
+// rows [lb, lb + len) are generated in the kernel from the exclusive scan of their lengths and answered with one fmgpu_position per row (HitRows).
 #include "fmgpu_search_shared.h"
 
+#include <hipcub/hipcub.hpp>
+
 namespace FMGPU_NS {
+
+// ------------------------------------------------------------------ row sources
+// last(): the last hit (HitRows); at(t, lo, hi, h): row t of the launch (h: what emit() needs to place its answer; lo / hi: the hits that row t can belong to, HitRows only);
+// emit(t, h, seq, pos, steps): the answer of row t (all ones: no answer).
+struct RowArray {
+    static constexpr bool kHits = false;
+    const uint64_t* rows;
+    uint64_t* out_seq; uint64_t* out_pos; uint64_t* out_steps;
+    __device__ __forceinline__ uint64_t last() const { return 0; }
+    __device__ __forceinline__ uint64_t at(uint64_t t, uint64_t, uint64_t, uint64_t&) const { return rows[t]; }
+    __device__ __forceinline__ void emit(uint64_t t, uint64_t, uint64_t seq, uint64_t pos, uint64_t st) const { out_seq[t] = seq; out_pos[t] = pos; out_steps[t] = st; }
+};
+// row t of the launch is row lb + (t - off[h]) of the hit h with off[h] <= t < off[h + 1] (off = exclusive scan of the hits' len; a hit of len 0 owns no row)
+struct HitRows {
+    static constexpr bool kHits = true;
+    const fmgpu_hit* hits;
+    const uint64_t* off;
+    uint64_t nhits;
+    fmgpu_position* out;
+    // the last hit h in [lo, hi] with off[h] <= t (given off[lo] <= t): never an empty hit, as its successor has the same offset
+    __device__ __forceinline__ uint64_t find(uint64_t lo, uint64_t hi, uint64_t t) const {
+        while (lo < hi) {
+            const uint64_t mid = hi - (hi - lo) / 2u;
+            if (off[mid] <= t) lo = mid; else hi = mid - 1u;
+        }
+        return lo;
+    }
+    // the same, found by the 64 lanes of a wave together (every lane gets the answer): a 64-ary search, one load per lane and round — 5 rounds of
+    // dependent loads over 10^7 hits where find() needs 24
+    __device__ __forceinline__ uint64_t find_wave(uint64_t lo, uint64_t hi, uint64_t t, uint32_t lane) const {
+        for (;;) {
+            const uint64_t step = hi - lo < 64u ? 1u : (hi - lo + 64u) / 64u;
+            const uint64_t p = lo + (uint64_t)lane * step;
+            const uint64_t below = __ballot(p <= hi && off[p] <= t);       // a prefix of the lanes (lane 0 probes lo: always set)
+            const uint64_t k = 63u - (uint64_t)__clzll(below);
+            if (step == 1u) return lo + k;
+            hi = min(hi, lo + (k + 1u) * step - 1u);                       // off[lo + (k + 1) * step] > t, or beyond hi
+            lo += k * step;
+        }
+    }
+    __device__ __forceinline__ uint64_t last() const { return nhits - 1u; }
+    __device__ __forceinline__ uint64_t at(uint64_t t, uint64_t lo, uint64_t hi, uint64_t& h) const { h = find(lo, hi, t); return hits[h].lb + (t - off[h]); }
+    __device__ __forceinline__ void emit(uint64_t t, uint64_t h, uint64_t seq, uint64_t pos, uint64_t st) const {
+        const fmgpu_hit& x = hits[h];
+        fmgpu_position p;
+        p.qidx = x.qidx; p.seq_id = seq; p.pos = pos + st; p.errors = x.errors & 0xffu; p.hit = (uint32_t)h;     // (pos + steps = locate.h:46-56's pos + offset)
+        out[t] = p;
+    }
+};
 
 // ------------------------------------------------------------------ locate
 #if !FMGPU_WIDE
 // with the per-row answer table (fmgpu_index_accelerate_locate): one 12-byte load per row
-__global__ __launch_bounds__(256) void k_locate_tab(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ rows, uint64_t count, idx_t n,
-                                                    uint64_t* __restrict__ out_seq, uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_steps,
-                                                    unsigned long long* __restrict__ steps_total) {
+template <class Src>
+__global__ __launch_bounds__(256) void k_locate_tab(const uint32_t* __restrict__ tab, Src src, uint64_t count, idx_t n, unsigned long long* __restrict__ steps_total) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t steps = 0;
     if (t < count) {
-        uint64_t r = rows[t], seq = ~0ull, pos = ~0ull, st = ~0ull;
+        uint64_t h = 0;
+        uint64_t r = src.at(t, 0, src.last(), h), seq = ~0ull, pos = ~0ull, st = ~0ull;
         if (r < n) {
             const uint32_t* p = tab + 3u * (size_t)r;
             const uint32_t a = p[0], b = p[1], c = p[2];
             if (c != 0xffffffffu) { seq = a; pos = b; st = c; steps = c; }
         }
-        out_seq[t] = seq; out_pos[t] = pos; out_steps[t] = st;
+        src.emit(t, h, seq, pos, st);
     }
     add_counters(steps_total, steps, 0u, 0u);
 }
@@ -33,14 +86,13 @@ constexpr uint32_t kLocateStepCap = 1u << 24;   // a valid index reaches a sampl
 // FMIndex::locate on a Format A table with fused presence bits (sigma <= 5; fmgpu_common.h): ONE 64-byte block per step answers "is this row
 // sampled", "which symbol precedes it" and "where does that lead" (fmindex/FMIndex.h:113-124 with suffixarray/SparseArray.h:63-70's presence test
 // read from the block); the Bitvector2L rank and the two DenseVector reads happen once, at the sampled row.
-template <int SIGMA>
-__global__ __launch_bounds__(256) void k_locate_fused(OccA<SIGMA> occ, ViewSA sa, const uint64_t* __restrict__ rows, uint64_t count, idx_t n,
-                                                      uint64_t* __restrict__ out_seq, uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_steps,
-                                                      unsigned long long* __restrict__ steps_total) {
+template <int SIGMA, class Src>
+__global__ __launch_bounds__(256) void k_locate_fused(OccA<SIGMA> occ, ViewSA sa, Src src, uint64_t count, idx_t n, unsigned long long* __restrict__ steps_total) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t steps = 0;
     if (t < count) {
-        uint64_t r64 = rows[t];
+        uint64_t h = 0;
+        uint64_t r64 = src.at(t, 0, src.last(), h);
         uint64_t seq = ~0ull, pos = ~0ull, st = ~0ull;
         if (r64 < n) {
             idx_t row = (idx_t)r64;
@@ -80,7 +132,7 @@ __global__ __launch_bounds__(256) void k_locate_fused(OccA<SIGMA> occ, ViewSA sa
                 st = steps;
             }
         }
-        out_seq[t] = seq; out_pos[t] = pos; out_steps[t] = st;
+        src.emit(t, h, seq, pos, st);
     }
     add_counters(steps_total, steps, 0u, 0u);
 }
@@ -98,12 +150,14 @@ constexpr uint32_t kLocRegion = 1024u + 16u;         // bytes per region of a ro
 constexpr uint32_t kLocSlotWords = kWide ? 4u : 2u;  // a row's LDS slot: the row, later {rank among the sampled rows (32-bit rows) or the sampled row itself, steps}
 constexpr uint32_t kLocWaveWords = 4u * (kLocRegion / 4u);
 constexpr uint32_t kLocBlockWords = 4u * kLocWaveWords + kLocRows * kLocSlotWords + 4u;
+// Rows generated from hit records (HitRows) add 4 words behind these: the first and the last hit of the workgroup's rows, found once by the first wave.  Every other
+// lane finds the hit of its row by a binary search between the two, again in the write-out phase; no hit number is kept beside a slot, so the LDS of a workgroup
+// grows by 16 bytes (33 040 -> 33 056 bytes with 32-bit rows, 49 424 -> 49 440 with 64-bit rows) and the resident workgroups per CU (160 KiB) stay 4 and 3.
+constexpr uint32_t kLocSegWords = 4u;
 constexpr uint32_t kLocNoSteps = 0xffffffffu;
-template <int SIGMA>
-__global__ __launch_bounds__(256) void k_locate_coop(OccA<SIGMA> occ, ViewSA sa, const uint64_t* __restrict__ rows, uint64_t count, idx_t n,
-                                                     uint64_t* __restrict__ out_seq, uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_steps,
-                                                     unsigned long long* __restrict__ steps_total) {
-    extern __shared__ uint32_t s_loc[];                             // 4 waves x 4 regions | kLocRows slots | the pool's hand-out counter
+template <int SIGMA, class Src>
+__global__ __launch_bounds__(256) void k_locate_coop(OccA<SIGMA> occ, ViewSA sa, Src src, uint64_t count, idx_t n, unsigned long long* __restrict__ steps_total) {
+    extern __shared__ uint32_t s_loc[];                             // 4 waves x 4 regions | kLocRows slots | the pool's hand-out counter | (HitRows) first, last hit
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     lds_word* const wave_lds = (lds_word*)(s_loc + wave * kLocWaveWords);
     uint32_t* const slots = s_loc + 4u * kLocWaveWords;
@@ -111,8 +165,22 @@ __global__ __launch_bounds__(256) void k_locate_coop(OccA<SIGMA> occ, ViewSA sa,
     const lds_word* const own = wave_lds + (lane & 3u) * (kLocRegion / 4u) + (lane >> 2) * 16u;
     const uint64_t base = (uint64_t)blockIdx.x * kLocRows;
     const uint32_t cnt = base < count ? (uint32_t)min((uint64_t)kLocRows, count - base) : 0u;
+    uint64_t seg_lo = 0, seg_hi = 0;                                // the hits that the workgroup's rows belong to (HitRows)
+    if constexpr (Src::kHits) {
+        uint64_t* const s_seg = (uint64_t*)(slots + kLocRows * kLocSlotWords + 4u);
+        if (wave == 0 && cnt) {                                      // (cnt is uniform: the whole wave searches)
+            const uint64_t first = src.find_wave(0, src.last(), base, lane);
+            const uint64_t final_hit = src.find_wave(first, src.last(), base + cnt - 1u, lane);
+            if (lane == 0) { s_seg[0] = first; s_seg[1] = final_hit; }
+        }
+        __syncthreads();
+        if (cnt) { seg_lo = s_seg[0]; seg_hi = s_seg[1]; }
+    }
+    uint64_t lo = seg_lo;                                           // a lane's rows ascend: so do their hits
     for (uint32_t t = threadIdx.x; t < cnt; t += 256u) {
-        const uint64_t r = rows[base + t];
+        uint64_t h = 0;
+        const uint64_t r = src.at(base + t, lo, seg_hi, h);
+        lo = h;
         if constexpr (kWide) { slots[4u * t] = (uint32_t)r; slots[4u * t + 1u] = (uint32_t)(r >> 32); slots[4u * t + 2u] = r < n ? 0u : kLocNoSteps; }
         else { slots[2u * t] = (uint32_t)r; slots[2u * t + 1u] = r < n ? 0u : kLocNoSteps; }
     }
@@ -182,7 +250,10 @@ __global__ __launch_bounds__(256) void k_locate_coop(OccA<SIGMA> occ, ViewSA sa,
         asm volatile("" ::: "memory");
     }
     __syncthreads();                                                // every wave has parked its rows
+    lo = seg_lo;
     for (uint32_t t = threadIdx.x; t < cnt; t += 256u) {            // the values of the sampled rows (suffixarray/SparseArray.h:63-70), all lanes at once
+        uint64_t h = 0;
+        if constexpr (Src::kHits) { h = src.find(lo, seg_hi, base + t); lo = h; }
         const uint32_t* e = slots + (size_t)t * kLocSlotWords;
         uint64_t seq = ~0ull, pos = ~0ull, st = ~0ull;
         const uint32_t ns = e[kLocSlotWords - (kWide ? 2u : 1u)];
@@ -193,19 +264,19 @@ __global__ __launch_bounds__(256) void k_locate_coop(OccA<SIGMA> occ, ViewSA sa,
             pos = dense_access(sa.f1, sa.bits1, sa.div1, k);
             st = ns;
         }
-        out_seq[base + t] = seq; out_pos[base + t] = pos; out_steps[base + t] = st;
+        src.emit(base + t, h, seq, pos, st);
     }
     add_counters(steps_total, total_steps, 0u, 0u);
 }
 
-template <class Occ>
-__global__ __launch_bounds__(256) void k_locate(Occ occ, const idx_t* __restrict__ lf_table, ViewSA sa, const uint64_t* __restrict__ rows, uint64_t count, idx_t n,
-                                                uint64_t* __restrict__ out_seq, uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_steps,
+template <class Occ, class Src>
+__global__ __launch_bounds__(256) void k_locate(Occ occ, const idx_t* __restrict__ lf_table, ViewSA sa, Src src, uint64_t count, idx_t n,
                                                 unsigned long long* __restrict__ steps_total) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t steps = 0;
     if (t < count) {
-        uint64_t r64 = rows[t];
+        uint64_t h = 0;
+        uint64_t r64 = src.at(t, 0, src.last(), h);
         uint64_t seq = ~0ull, pos = ~0ull, st = ~0ull;
         if (r64 < n) {
             idx_t row = (idx_t)r64;
@@ -221,9 +292,62 @@ __global__ __launch_bounds__(256) void k_locate(Occ occ, const idx_t* __restrict
                 st = steps;
             }
         }
-        out_seq[t] = seq; out_pos[t] = pos; out_steps[t] = st;
+        src.emit(t, h, seq, pos, st);
     }
     add_counters(steps_total, steps, 0u, 0u);
+}
+
+// the lengths pass of fmgpu_locate_hits: len[i] of every hit (len[count] = 0, so that the exclusive scan of count + 1 entries ends in the total), and a flag
+// for a hit whose rows leave the index
+__global__ __launch_bounds__(256) void k_hit_lengths(const fmgpu_hit* __restrict__ hits, uint64_t count, uint64_t n, uint64_t* __restrict__ len,
+                                                     unsigned long long* __restrict__ bad) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > count) return;
+    uint64_t l = 0;
+    if (t < count) {
+        const uint64_t lb = hits[t].lb;
+        l = hits[t].len;
+        if (l > n || lb > n - l) atomicOr(bad, 1ull);
+    }
+    len[t] = l;
+}
+
+// the locate kernel that serves an index, for `count` rows of a row source (the caller times the launch)
+template <class Src>
+static int launch_locate(Index* x, const Src& src, uint64_t count, unsigned long long* dsteps, hipStream_t stream, EventTimer& timer) {
+    // k_locate runs best with 4 resident blocks per CU (9 M rows of the 3.09 Gbp index: 8 / 5 / 4 / 3 blocks = 4.73 / 4.20 / 3.99 / 4.03 ms — its lanes
+    // leave after 0 .. 15 LF steps and more waves only queue up at the memory system): 36 KB of unused dynamic LDS set the residency
+    size_t locate_lds = (size_t)36 * 1024;
+    { const char* ev = dev_env("FMGPU_DEV_LOCATE_LDS"); if (ev) locate_lds = (size_t)atoi(ev); }
+    FM_GRID(grid, count);
+    const dim3 block(256);
+    const idx_t n = (idx_t)x->bwt.n;
+    int rc = 0;
+    timer.start();
+#if !FMGPU_WIDE
+    if (x->loc_tab)
+        k_locate_tab<<<grid, block, 0, stream>>>(x->loc_tab, src, count, n, dsteps);
+    else
+#endif
+    if (x->bwt.va.fused && x->bwt.search_family() == FAM_A) {      // one line per step: presence bit, symbol and LF from the row's block (also ahead of the explicit LF table: that is two lines per step)
+        const bool coop = (uint64_t)x->bwt.n < (1ull << 38) && !(kernel_flags() & (1 << 23));   // (bit 23: one row per lane, k_locate_fused)
+        const dim3 cgrid((unsigned)((count + kLocRows - 1u) / kLocRows));
+        const size_t coop_lds = (size_t)(kLocBlockWords + (Src::kHits ? kLocSegWords : 0u)) * 4 + (dev_env("FMGPU_DEV_LOCATE_LDS") ? locate_lds : 0);
+        if (coop && count / kLocRows < kMaxGridBlocks) {
+            if (x->bwt.sigma == 5) k_locate_coop<5><<<cgrid, block, coop_lds, stream>>>(OccA<5>{x->bwt.va}, x->vsa, src, count, n, dsteps);
+            else k_locate_coop<0><<<cgrid, block, coop_lds, stream>>>(OccA<0>{x->bwt.va}, x->vsa, src, count, n, dsteps);
+        } else
+        if (x->bwt.sigma == 5) k_locate_fused<5><<<grid, block, locate_lds, stream>>>(OccA<5>{x->bwt.va}, x->vsa, src, count, n, dsteps);
+        else k_locate_fused<0><<<grid, block, locate_lds, stream>>>(OccA<0>{x->bwt.va}, x->vsa, src, count, n, dsteps);
+    } else
+    rc = dispatch_occ(x->bwt, [&](auto occ, auto) {
+        k_locate<decltype(occ)><<<grid, block, locate_lds, stream>>>(occ, x->bwt.lf_table, x->vsa, src, count, n, dsteps);
+        return 0;
+    });
+    timer.stop();
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "k_locate launch");
+    return rc;
 }
 
 namespace api {
@@ -231,10 +355,6 @@ namespace api {
 
 int fmgpu_locate(fmgpu_index_t h, const uint64_t* rows, uint64_t count, uint64_t* out_seq, uint64_t* out_pos, uint64_t* out_steps,
                  fmgpu_stats* stats, void* stream_) {
-    // k_locate runs best with 4 resident blocks per CU (9 M rows of the 3.09 Gbp index: 8 / 5 / 4 / 3 blocks = 4.73 / 4.20 / 3.99 / 4.03 ms — its lanes
-    // leave after 0 .. 15 LF steps and more waves only queue up at the memory system): 36 KB of unused dynamic LDS set the residency
-    size_t locate_lds = (size_t)36 * 1024;
-    { const char* ev = dev_env("FMGPU_DEV_LOCATE_LDS"); if (ev) locate_lds = (size_t)atoi(ev); }
     Index* x = reinterpret_cast<Index*>(h);
     if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
     if (int drc = on_handle_device(x)) return drc;
@@ -252,34 +372,8 @@ int fmgpu_locate(fmgpu_index_t h, const uint64_t* rows, uint64_t count, uint64_t
     unsigned long long* dsteps = nullptr;
     if ((rc = step_counters(stats != nullptr, stream, &dsteps))) return rc;
     EventTimer timer(stream, stats != nullptr);
-    FM_GRID(grid, count);
-    const dim3 block(256);
-    const idx_t n = (idx_t)x->bwt.n;
-    timer.start();
-#if !FMGPU_WIDE
-    if (x->loc_tab)
-        k_locate_tab<<<grid, block, 0, stream>>>(x->loc_tab, (const uint64_t*)srows.dev, count, n, (uint64_t*)sseq.dev, (uint64_t*)spos.dev, (uint64_t*)sst.dev, dsteps);
-    else
-#endif
-    if (x->bwt.va.fused && x->bwt.search_family() == FAM_A) {      // one line per step: presence bit, symbol and LF from the row's block (also ahead of the explicit LF table: that is two lines per step)
-        const bool coop = (uint64_t)x->bwt.n < (1ull << 38) && !(kernel_flags() & (1 << 23));   // (bit 23: one row per lane, k_locate_fused)
-        const dim3 cgrid((unsigned)((count + kLocRows - 1u) / kLocRows));
-        const size_t coop_lds = (size_t)kLocBlockWords * 4 + (dev_env("FMGPU_DEV_LOCATE_LDS") ? locate_lds : 0);
-        if (coop && count / kLocRows < kMaxGridBlocks) {
-            if (x->bwt.sigma == 5) k_locate_coop<5><<<cgrid, block, coop_lds, stream>>>(OccA<5>{x->bwt.va}, x->vsa, (const uint64_t*)srows.dev, count, n, (uint64_t*)sseq.dev, (uint64_t*)spos.dev, (uint64_t*)sst.dev, dsteps);
-            else k_locate_coop<0><<<cgrid, block, coop_lds, stream>>>(OccA<0>{x->bwt.va}, x->vsa, (const uint64_t*)srows.dev, count, n, (uint64_t*)sseq.dev, (uint64_t*)spos.dev, (uint64_t*)sst.dev, dsteps);
-        } else
-        if (x->bwt.sigma == 5) k_locate_fused<5><<<grid, block, locate_lds, stream>>>(OccA<5>{x->bwt.va}, x->vsa, (const uint64_t*)srows.dev, count, n, (uint64_t*)sseq.dev, (uint64_t*)spos.dev, (uint64_t*)sst.dev, dsteps);
-        else k_locate_fused<0><<<grid, block, locate_lds, stream>>>(OccA<0>{x->bwt.va}, x->vsa, (const uint64_t*)srows.dev, count, n, (uint64_t*)sseq.dev, (uint64_t*)spos.dev, (uint64_t*)sst.dev, dsteps);
-    } else
-    rc = dispatch_occ(x->bwt, [&](auto occ, auto) {
-        k_locate<decltype(occ)><<<grid, block, locate_lds, stream>>>(occ, x->bwt.lf_table, x->vsa, (const uint64_t*)srows.dev, count, n, (uint64_t*)sseq.dev,
-                                                           (uint64_t*)spos.dev, (uint64_t*)sst.dev, dsteps);
-        return 0;
-    });
-    timer.stop();
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_locate launch");
+    const RowArray src{(const uint64_t*)srows.dev, (uint64_t*)sseq.dev, (uint64_t*)spos.dev, (uint64_t*)sst.dev};
+    if ((rc = launch_locate(x, src, count, dsteps, stream, timer))) return rc;
     if (stats) {
         unsigned long long hs[kCounterKinds] = {0, 0, 0, 0};
         if ((rc = read_step_counters(dsteps, stream, hs))) return rc;
@@ -288,6 +382,60 @@ int fmgpu_locate(fmgpu_index_t h, const uint64_t* rows, uint64_t count, uint64_t
     rc = sseq.finish(); if (!rc) rc = spos.finish(); if (!rc) rc = sst.finish();
     if (stats || sseq.owned || spos.owned || sst.owned) (void)hipStreamSynchronize(stream);
     return rc;
+}
+
+int fmgpu_locate_hits(fmgpu_index_t h, const fmgpu_hit* hits, uint64_t count, fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                      fmgpu_stats* stats, void* stream_) {
+    Index* x = reinterpret_cast<Index*>(h);
+    if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
+    if (int drc = on_handle_device(x)) return drc;
+    if (!x->has_sa) return fail(FMGPU_ERR_INVALID, "index was created without an annotated (sampled suffix) array");
+    if (stats) *stats = fmgpu_stats{};
+    if (out_count) *out_count = 0;
+    if (count == 0) return 0;
+    if (!hits || !out || !out_count) return fail(FMGPU_ERR_INVALID, "hits / out / out_count is null");
+    hipStream_t stream = (hipStream_t)stream_;
+    Staged sh;
+    int rc;
+    if ((rc = sh.in(hits, count * sizeof(fmgpu_hit), stream))) return rc;
+    const fmgpu_hit* dh = (const fmgpu_hit*)sh.dev;
+    // lengths pass: off = exclusive scan of len over count + 1 entries (off[count] = the total), off[count + 1] = the bad-hit flag; ONE read-back of both
+    DBuf len, off, tmp;
+    if ((rc = len.alloc((count + 1) * 8)) || (rc = off.alloc((count + 2) * 8))) return rc;
+    unsigned long long* dbad = (unsigned long long*)(off.as<uint64_t>() + count + 1);
+    FM_HIP(hipMemsetAsync(dbad, 0, 8, stream));
+    FM_GRID(lgrid, count + 1);
+    k_hit_lengths<<<lgrid, dim3(256), 0, stream>>>(dh, count, x->bwt.n, len.as<uint64_t>(), dbad);
+    FM_LAUNCHED("k_hit_lengths");
+    size_t tb = 0;
+    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, len.as<uint64_t>(), off.as<uint64_t>(), (size_t)(count + 1), stream));
+    if ((rc = tmp.alloc(tb))) return rc;
+    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, len.as<uint64_t>(), off.as<uint64_t>(), (size_t)(count + 1), stream));
+    CallScratch* sc = nullptr;
+    if ((rc = call_scratch(&sc))) return rc;
+    unsigned long long* hback = sc->pinned;
+    FM_HIP(hipMemcpyAsync(hback, off.as<uint64_t>() + count, 16, hipMemcpyDeviceToHost, stream));
+    FM_HIP(hipStreamSynchronize(stream));
+    const uint64_t total = hback[0];
+    *out_count = total;
+    if (hback[1]) return fail(FMGPU_ERR_INVALID, "a hit record's rows [lb, lb + len) reach beyond the index's rows");
+    if (total > capacity) return fail(FMGPU_ERR_CAPACITY, "position buffer too small: " + std::to_string(total) + " rows, capacity " + std::to_string(capacity));
+    if (total == 0) return 0;
+    Staged so;
+    if ((rc = so.out(out, total * sizeof(fmgpu_position), stream))) return rc;
+    unsigned long long* dsteps = nullptr;
+    if ((rc = step_counters(stats != nullptr, stream, &dsteps))) return rc;
+    EventTimer timer(stream, stats != nullptr);
+    const HitRows src{dh, off.as<uint64_t>(), count, (fmgpu_position*)so.dev};
+    if ((rc = launch_locate(x, src, total, dsteps, stream, timer))) return rc;
+    if (stats) {
+        unsigned long long hs[kCounterKinds] = {0, 0, 0, 0};
+        if ((rc = read_step_counters(dsteps, stream, hs))) return rc;
+        stats->lf_steps = hs[0]; stats->hits = total; stats->kernel_ms = timer.ms();
+    }
+    rc = so.finish();
+    if (stats || so.owned) (void)hipStreamSynchronize(stream);
+    return rc;                                                      // (the scratch is freed on return: hipFree waits for the device)
 }
 
 #if FMGPU_WIDE

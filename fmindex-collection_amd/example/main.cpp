@@ -269,17 +269,15 @@ struct Run {
     }
 
     std::vector<Placement> locate(std::vector<Hit> const& hits) const {
-        std::vector<uint64_t> rows;
-        for (auto const& h : hits) for (uint64_t r = 0; r < h.rows; ++r) rows.push_back(h.firstRow + r);
-        auto const where = index.locate(rows);
+        std::vector<fmgpu_hit> cursors(hits.size());
+        for (size_t i = 0; i < hits.size(); ++i) { cursors[i].qidx = hits[i].read; cursors[i].lb = hits[i].firstRow; cursors[i].len = hits[i].rows; }
+        auto const where = index.locateHits(cursors);                   // every row of every hit, in hit order: one call
         std::vector<Placement> placed;
-        placed.reserve(rows.size());
-        size_t at = 0;
-        for (auto const& h : hits)
-            for (uint64_t r = 0; r < h.rows; ++r, ++at) {
-                auto const& [sequence, sampled, walked] = where[at];
-                placed.push_back({h.read, sequence, sampled + walked, h.errors});
-            }
+        placed.reserve(where.size());
+        for (auto const& p : where) {
+            auto const& h = hits[p.hit];
+            placed.push_back({h.read, static_cast<uint32_t>(p.seq_id), p.pos, h.errors});
+        }
         return placed;
     }
 

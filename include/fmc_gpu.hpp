@@ -122,6 +122,17 @@ struct GpuIndexBase {
         for (size_t i = 0; i < rows.size(); ++i) out[i] = {static_cast<uint32_t>(seq[i]), static_cast<uint32_t>(pos[i]), static_cast<size_t>(steps[i])};
         return out;
     }
+    // every row of every hit record located in one call (fmgpu_locate_hits): one fmgpu_position per row, hits in the given order, inside a hit the rows
+    // lb .. lb + len - 1 — what a LocateLinear per cursor gives, with pos = sampled pos + offset
+    auto locateHits(std::vector<fmgpu_hit> const& hits) const -> std::vector<fmgpu_position> {
+        uint64_t total = 0;
+        for (auto const& h : hits) total += h.len;
+        std::vector<fmgpu_position> out(std::max<uint64_t>(total, 1));
+        uint64_t count = 0;
+        detail::check(fmgpu_locate_hits(handle, hits.data(), hits.size(), out.data(), total, &count, nullptr, nullptr));
+        out.resize(count);
+        return out;
+    }
 };
 
 template <size_t TSigma, template <size_t> class String = string::FlattenedBitvectors_512_64k>   // fmindex/FMIndex.h:14
@@ -696,7 +707,8 @@ struct LocateLinear {
 template <typename Index, typename Cursor> LocateLinear(Index const&, Cursor const&) -> LocateLinear<Index, Cursor>;
 
 // fmc::Search{index, queries, editDistance, errors, maxResults, reportFunc}() — search/search.h:48-75: searches, locates every row of every
-// reported cursor and calls reportFunc(qidx, seqId, pos + offset, errors)
+// reported cursor and calls reportFunc(qidx, seqId, pos + offset, errors).  The cursors of the batch are collected in callback order and located
+// by ONE fmgpu_locate_hits call; the reports come in the order of the reference's per-cursor LocateLinear loop.
 template <typename index_t, typename queries_t, typename delegate_t>
 struct Search {
     index_t const&        index;
@@ -706,8 +718,11 @@ struct Search {
     std::optional<size_t> maxResults{};
     delegate_t const&     reportFunc;
     void operator()() {
+        std::vector<fmgpu_hit> hits;
         auto report = [&](size_t qidx, auto const& cursor, size_t e) {
-            for (auto [sid, spos, offset] : LocateLinear{index, cursor}) reportFunc(qidx, sid, spos + offset, e);
+            fmgpu_hit h{};
+            h.qidx = qidx; h.lb = cursor.lb; h.len = cursor.len; h.errors = static_cast<uint32_t>(e);
+            hits.push_back(h);
         };
         if (maxResults) {
             if (editDistance) search_n<true>(index, queries, errors, *maxResults, report);
@@ -716,6 +731,8 @@ struct Search {
             if (editDistance) search<true>(index, queries, errors, report);
             else search<false>(index, queries, errors, report);
         }
+        for (auto const& p : index.locateHits(hits))     // (seqId as LocateLinear's entry holds it: 32 bits)
+            reportFunc(static_cast<size_t>(p.qidx), static_cast<uint32_t>(p.seq_id), static_cast<size_t>(p.pos), static_cast<size_t>(p.errors));
     }
 };
 template <typename I, typename Q, typename D> Search(I const&, Q const&, bool, size_t, std::optional<size_t>, D const&) -> Search<I, Q, D>;

@@ -339,6 +339,32 @@ int fmgpu_search_backtracking(fmgpu_index_t h, const uint8_t* qbuf, const uint64
 int fmgpu_locate(fmgpu_index_t h, const uint64_t* rows, uint64_t count,
                  uint64_t* out_seq, uint64_t* out_pos, uint64_t* out_steps, fmgpu_stats* stats, void* stream);
 
+/* One located row of a hit record: what fmc::Search reports for it (search/search.h:55-59). */
+typedef struct fmgpu_position {
+    uint64_t qidx;      /* the hit's qidx */
+    uint64_t seq_id;    /* seqId of the sampled entry reached */
+    uint64_t pos;       /* its pos + the LF steps walked = pos + offset (locate.h:46-56) */
+    uint32_t errors;    /* the hit's errors & 0xff */
+    uint32_t hit;       /* index of the hit record the row belongs to, low 32 bits */
+} fmgpu_position;       /* 32 bytes */
+
+/* Every row of every hit record located in one call: the loop `for (auto [seqId, pos, offset] : LocateLinear{index, cursor})` of fmc::Search
+ * (search/search.h:48-75, locate.h:14-57) over a whole batch of cursors.  The rows are generated inside the locate kernels from the hits' {lb, len};
+ * no array of rows is built.
+ *   - Output order: one record per row; hits in the order given, inside a hit the rows lb, lb + 1, ..., lb + len - 1 — the sequence of the
+ *     per-cursor loops.  After fmgpu_hits_sort the output is in fmc::Search's report order.  A hit with len == 0 produces nothing.  Positions are
+ *     not deduplicated (two cursors that reach one row both report it, as in the reference).
+ *   - Each record holds exactly what the locate of that row gives (seq_id = out_seq, pos = out_pos + out_steps), whichever locate kernel serves the index.
+ *   - *out_count = the sum of len over the hits, on success and on FMGPU_ERR_CAPACITY alike; if it exceeds `capacity`, the call returns
+ *     FMGPU_ERR_CAPACITY and writes nothing to `out`.
+ *   - FMGPU_ERR_INVALID: a hit with lb + len > n (checked on the device, in the pass that sums the lengths), an index without an annotated
+ *     array, or a null hits / out / out_count while count > 0.  count == 0 returns 0 with *out_count = 0 (out_count may then be NULL).
+ *   - hits and out may be host or device memory.  The call reads back the sum of the lengths once (the capacity check needs it) and returns
+ *     after its kernels have completed (its scratch of 16 bytes per hit is freed on return).
+ *   - stats: lf_steps = LF steps walked, hits = records written, kernel_ms = the locate kernel alone. */
+int fmgpu_locate_hits(fmgpu_index_t h, const fmgpu_hit* hits, uint64_t count, fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                      fmgpu_stats* stats, void* stream);
+
 /* the 16-byte transport form of hit records (what a rank sends to the gathering rank): out[2k] = qidx:32 | lb:32,
  * out[2k+1] = len:32 | errors:8 | seq:24; lb_rev is dropped (it only serves further extension of the cursor).  Needs qidx, lb, len < 2^32,
  * errors < 256, seq < 2^24; a record that does not fit makes the call return FMGPU_ERR_UNSUPPORTED (checked on the device; the call

@@ -1,0 +1,30 @@
+"""tests/cpp/test_locate_hits.cpp: index.locateHits and fmc::Search (include/fmc_gpu.hpp) against the per-cursor LocateLinear loop, and one
+fmgpu_locate_hits call per batch — counted by wrapping the ABI symbols at link time (-Wl,--wrap)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "fmindex-collection_amd")
+EXE = os.path.join(ROOT, "tests", "cpp", "test_locate_hits")
+
+
+def _build():
+    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j4", "-s"], check=True)
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", os.path.join(ROOT, "tests", "cpp", "test_locate_hits.cpp"), "-o", EXE,
+                    "-L" + PKG, "-lfmgpu", "-Wl,-rpath," + PKG, "-Wl,--wrap=fmgpu_locate,--wrap=fmgpu_locate_hits"], check=True)
+
+
+def test_locate_hits_cpp_compiles():
+    _build()
+    r = subprocess.run([EXE], capture_output=True, text=True, timeout=600)
+    assert r.returncode in (0, 77), r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+def test_locate_hits_cpp_on_gpu():
+    _build()
+    r = subprocess.run([EXE], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all checks passed" in r.stdout
