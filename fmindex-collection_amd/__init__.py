@@ -14,10 +14,10 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import FmgpuError, DeviceBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE
+from .capi import FmgpuError, DeviceBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE
 from . import search_scheme  # noqa: F401
 
-__all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "LocateLinear", "search_locate",
+__all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options"]
 
 
@@ -377,6 +377,57 @@ class FMIndex:
         capi.check(rc)
         res = res[: cnt.value]
         return (res, st) if want_stats else res
+
+
+    # -------------------------------------------------------------- text extraction (utils.h:672-703 as LF walks on the device)
+    def accelerate_extract(self, enable=True):
+        """build / drop the text map and the sampled rows in text order (fmgpu_index_accelerate_extract) that extract() and sequence_lengths() read.
+        Not saved with the index and not cloned: build it again after load() / clone()"""
+        capi.check(capi.lib().fmgpu_index_accelerate_extract(self._h, 1 if enable else 0))
+        return self._refresh_bytes()
+
+    def sequence_lengths(self):
+        """(seq_ids, lengths): every seqId of the text map, ascending, and its length without its last delimiter"""
+        cnt = C.c_uint64()
+        rc = capi.lib().fmgpu_sequence_lengths(self._h, None, None, 0, C.byref(cnt))
+        if rc != capi.FMGPU_ERR_CAPACITY:
+            capi.check(rc)
+        ids, lens = np.zeros(cnt.value, dtype=np.uint64), np.zeros(cnt.value, dtype=np.uint64)
+        capi.check(capi.lib().fmgpu_sequence_lengths(self._h, capi.ptr(ids), capi.ptr(lens), cnt.value, C.byref(cnt)))
+        return ids, lens
+
+    def extract(self, seq_ids, pos=None, lens=None, out=None, want_stats=False):
+        """the text symbols of ranges (fmgpu_extract): extract(seq_ids, pos, lens) with three arrays, or extract(ranges) with a TEXT_RANGE_DTYPE array,
+        DeviceBuffer or torch tensor of records (in HBM: used in place).  Returns (symbols uint8, offsets uint64[count + 1]): range i is
+        symbols[offsets[i]:offsets[i + 1]].  out = a device buffer / tensor to write the symbols into instead (then (symbol count, offsets) is returned)."""
+        if pos is None:
+            ranges = seq_ids
+            if isinstance(ranges, np.ndarray):
+                ranges = np.ascontiguousarray(ranges, dtype=TEXT_RANGE_DTYPE)
+            rp, rbytes = _buffer(ranges)
+            count = rbytes // TEXT_RANGE_DTYPE.itemsize
+            if isinstance(ranges, np.ndarray):
+                host = ranges
+            elif isinstance(ranges, DeviceBuffer):
+                host = ranges.to_array(TEXT_RANGE_DTYPE, count)
+            else:
+                host = np.frombuffer(ranges.cpu().numpy().tobytes(), dtype=TEXT_RANGE_DTYPE)[:count]
+        else:
+            host = np.zeros(np.size(seq_ids), dtype=TEXT_RANGE_DTYPE)
+            host["seq_id"], host["pos"], host["len"] = _u64(seq_ids).reshape(-1), _u64(pos).reshape(-1), _u64(lens).reshape(-1)
+            rp, count = capi.ptr(host), host.size
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        np.cumsum(host["len"], out=offsets[1:])
+        total = int(offsets[-1])
+        st, cnt = capi.Stats(), C.c_uint64()
+        if out is not None:
+            op, obytes = _buffer(out)
+            capi.check(capi.lib().fmgpu_extract(self._h, rp, count, op, obytes, C.byref(cnt), C.byref(st) if want_stats else None, None))
+            return (cnt.value, offsets, st) if want_stats else (cnt.value, offsets)
+        res = np.zeros(max(total, 1), dtype=np.uint8)
+        capi.check(capi.lib().fmgpu_extract(self._h, rp, count, capi.ptr(res), total, C.byref(cnt), C.byref(st) if want_stats else None, None))
+        res = res[: cnt.value]
+        return (res, offsets, st) if want_stats else (res, offsets)
 
 
 class BiFMIndex(FMIndex):
@@ -777,3 +828,33 @@ def search_locate(index, queries, errors, n=UINT64_MAX, edit=True, compat_auto_s
     if len(parts) > 1:
         pos = pos[np.argsort(pos["qidx"], kind="stable")]     # the two length classes hold different queries: ascending qidx, each query's rows in order
     return pos[fields]
+
+
+def reconstruct_text(index, seq_nbr=None):
+    """reconstructText(index, seqNbr) / reconstructText(index) (utils.h:672-703).  seq_nbr = a sentinel ROW (0 .. C[1] - 1): the symbols from the previous
+    delimiter of that row's seqId (or pos 0) up to the row's delimiter.  None: one text per sentinel row, ordered by (seqId, row).  The sentinel rows are
+    located on the host side's behalf by fmgpu_locate; the symbols come from ONE fmgpu_extract call (the table is built for the call if the index lacks
+    it, and dropped again).  Returns a uint8 array, or a list of them."""
+    nsent = int(index.rank(np.array([index.n], dtype=np.uint64), 0)[0])          # rank(size(), 0) + C[0] (C[0] = 0)
+    if seq_nbr is not None and not 0 <= int(seq_nbr) < nsent:
+        raise ValueError(f"seq_nbr {seq_nbr}: the index has {nsent} sentinel rows")
+    rows = np.arange(nsent, dtype=np.uint64)
+    seq, pos, steps = index.locate(rows)
+    pos = pos + steps
+    order = np.lexsort((pos, seq))                                                 # the delimiters of every seqId in text order
+    prev = np.zeros(nsent, dtype=np.uint64)                                        # pos just behind the previous delimiter of the same seqId
+    same = np.zeros(nsent, dtype=bool)
+    if nsent > 1:
+        same[order[1:]] = seq[order[1:]] == seq[order[:-1]]
+        prev[order[1:]] = np.where(same[order[1:]], pos[order[:-1]] + 1, 0)
+    pick = np.array([seq_nbr], dtype=np.int64) if seq_nbr is not None else np.lexsort((rows, seq))
+    built = not (index.formats & capi.FMT_EXTRACT)
+    if built:
+        index.accelerate_extract()
+    try:
+        sym, off = index.extract(seq[pick], prev[pick], pos[pick] - prev[pick])
+    finally:
+        if built:
+            index.accelerate_extract(False)
+    texts = [sym[int(off[i]): int(off[i + 1])] for i in range(len(pick))]
+    return texts[0] if seq_nbr is not None else texts

@@ -82,6 +82,15 @@ POSITION_DTYPE = np.dtype([("qidx", "<u8"), ("seq_id", "<u8"), ("pos", "<u8"), (
 assert POSITION_DTYPE.itemsize == C.sizeof(Position) == 32
 
 
+class TextRange(C.Structure):
+    """fmgpu_text_range: symbols pos .. pos + len - 1 of sequence seq_id (fmgpu_extract)"""
+    _fields_ = [("seq_id", C.c_uint64), ("pos", C.c_uint64), ("len", C.c_uint64)]
+
+
+TEXT_RANGE_DTYPE = np.dtype([("seq_id", "<u8"), ("pos", "<u8"), ("len", "<u8")])
+assert TEXT_RANGE_DTYPE.itemsize == C.sizeof(TextRange) == 24
+
+
 class Scheme(C.Structure):
     _fields_ = [("n_searches", C.c_int32), ("n_parts", C.c_int32), ("pi", u64p), ("l", u64p), ("u", u64p),
                 ("partition", u64p), ("edit", C.c_int32), ("reserved", C.c_int32)]
@@ -109,6 +118,7 @@ EXPORTS = [
     "fmgpu_replicas_load", "fmgpu_replicas_destroy", "fmgpu_replicas_info", "fmgpu_replicas_search_exact", "fmgpu_replicas_search_scheme",
     "fmgpu_replicas_search_ng21", "fmgpu_replicas_locate",
     "fmgpu_set_option", "fmgpu_get_option", "fmgpu_index_formats", "fmgpu_index_clone", "fmgpu_replicas_peer_copies",
+    "fmgpu_index_accelerate_extract", "fmgpu_sequence_lengths", "fmgpu_extract",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -122,6 +132,7 @@ SEL_EXACT_ON_TREE, SEL_EXACT_ONE_SYMBOL, SEL_LOCATE_PER_LANE, SEL_NO_SHARING, SE
 SEL_NO_BOARD = 1 << 26
 # fmgpu_index_formats bits: what a handle holds beside (or as) the layout it was given
 FMT_BLOCKS, FMT_PAIRS, FMT_DENSE, FMT_PLANES, FMT_TREE, FMT_REFERENCE, FMT_LF, FMT_KSTEP, FMT_INTERVALS, FMT_WALK, FMT_PREFIX, FMT_LOCATE, FMT_FUSED = (1 << k for k in range(13))
+FMT_EXTRACT = 1 << 13
 
 _lib = None
 
@@ -182,6 +193,9 @@ def lib():
     L.fmgpu_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(Stats), C.c_void_p]
     L.fmgpu_locate_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.POINTER(Stats), C.c_void_p]
+    L.fmgpu_index_accelerate_extract.argtypes = [C.c_void_p, C.c_int32]
+    L.fmgpu_sequence_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fmgpu_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.POINTER(Stats), C.c_void_p]
     if hasattr(L, "fmgpu_index_accelerate"):
         L.fmgpu_index_accelerate.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(L, "fmgpu_hits_pack16"):

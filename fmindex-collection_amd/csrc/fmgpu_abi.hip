@@ -283,6 +283,15 @@ int fmgpu_locate_hits(fmgpu_index_t h, const fmgpu_hit* hits, uint64_t count, fm
     if (count && (!hits || !out || !out_count)) return fail(FMGPU_ERR_INVALID, "hits / out / out_count is null");
     ROUTE(h, fmgpu_locate_hits(h, hits, count, out, capacity, out_count, stats, stream));
 }
+int fmgpu_index_accelerate_extract(fmgpu_index_t h, int32_t enable) { ROUTE(h, fmgpu_index_accelerate_extract(h, enable)); }
+int fmgpu_sequence_lengths(fmgpu_index_t h, uint64_t* seq_ids, uint64_t* lengths, uint64_t capacity, uint64_t* out_count) {
+    ROUTE(h, fmgpu_sequence_lengths(h, seq_ids, lengths, capacity, out_count));
+}
+int fmgpu_extract(fmgpu_index_t h, const fmgpu_text_range* ranges, uint64_t count, uint8_t* out, uint64_t capacity, uint64_t* out_count,
+                  fmgpu_stats* stats, void* stream) {
+    if (count && (!ranges || !out || !out_count)) return fail(FMGPU_ERR_INVALID, "ranges / out / out_count is null");
+    ROUTE(h, fmgpu_extract(h, ranges, count, out, capacity, out_count, stats, stream));
+}
 int fmgpu_cursor_extend(fmgpu_index_t h, int32_t direction, uint64_t count, const uint64_t* lb, const uint64_t* lb_rev, const uint64_t* len, const uint8_t* symb,
                         uint64_t* out_lb, uint64_t* out_lb_rev, uint64_t* out_len, void* stream) {
     ROUTE(h, fmgpu_cursor_extend(h, direction, count, lb, lb_rev, len, symb, out_lb, out_lb_rev, out_len, stream));

@@ -727,6 +727,20 @@ constexpr uint32_t flat_count_bits(uint32_t sigma) { return sigma == 0u ? 28u : 
 int build_flat_table(Index* x, hipStream_t stream);
 void free_string(DevString& s);
 
+// fmgpu_index_accelerate_extract (fmgpu_extract.hip): the text map and the sampled rows in text order, in ONE device allocation.  Global coordinate of
+// (seqId, pos) = start[s] + pos, start = exclusive prefix sum of len + 1 over the map (len = pos of the seqId's last delimiter).
+struct ExtractTable {
+    void* dev = nullptr; size_t bytes = 0;
+    uint64_t nseq = 0, nsamp = 0;
+    const uint64_t* seq_id = nullptr;   // [nseq] ascending
+    const uint64_t* len = nullptr;      // [nseq]
+    const uint64_t* start = nullptr;    // [nseq]
+    const idx_t* end_row = nullptr;     // [nseq] the sentinel row of the last delimiter
+    const uint64_t* key = nullptr;      // [nsamp] global coordinate of every sampled row, ascending
+    const idx_t* row = nullptr;         // [nsamp] the sampled row itself
+    std::vector<uint64_t> host_seq, host_len;   // (fmgpu_sequence_lengths)
+};
+
 struct Index {
     IndexHeader hdr;
     DevString bwt, rev;
@@ -739,6 +753,8 @@ struct Index {
     ViewSA vsa{};
     // fmgpu_index_accelerate_locate: the (seqId, pos, steps) answer of every row, 3 x u32 per row (or null)
     uint32_t* loc_tab = nullptr;
+    // fmgpu_index_accelerate_extract (not saved, not cloned)
+    ExtractTable ext;
     size_t device_bytes = 0;
     // prefix table (fmgpu_index_accelerate_search): lut[code(w)] = { lb, lbRev, len, symbols consumed before the interval emptied (or L) }
     uint4* lut = nullptr; uint32_t lut_len = 0; uint64_t lut_entries = 0;

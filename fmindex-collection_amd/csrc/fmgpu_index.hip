@@ -945,7 +945,7 @@ int fmgpu_index_destroy(fmgpu_index_t h) {
     Index* x = reinterpret_cast<Index*>(h);
     if (!x) return 0;
     free_string(x->bwt); free_string(x->rev);
-    for (void* p : {(void*)x->dC, x->sa_l0, x->sa_l1, x->sa_bits, x->sa_f0, x->sa_f1, (void*)x->lut, (void*)x->loc_tab}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)x->dC, x->sa_l0, x->sa_l1, x->sa_bits, x->sa_f0, x->sa_f1, (void*)x->lut, (void*)x->loc_tab, x->ext.dev}) if (p) (void)hipFree(p);
     x->hdr.magic = 0;
     delete x;
     return 0;
@@ -1269,6 +1269,7 @@ int fmgpu_index_formats(fmgpu_index_t h, uint32_t* mask) {
     if (x->lut) m |= FMGPU_FMT_PREFIX;
     if (x->loc_tab) m |= FMGPU_FMT_LOCATE;
     if (s.va.fused) m |= FMGPU_FMT_FUSED;
+    if (x->ext.dev) m |= FMGPU_FMT_EXTRACT;
     *mask = m;
     return 0;
 }

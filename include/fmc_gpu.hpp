@@ -133,6 +133,18 @@ struct GpuIndexBase {
         out.resize(count);
         return out;
     }
+    // fmgpu_index_accelerate_extract: the text map and sample table that extract() reads (not saved, not cloned)
+    void accelerateExtract(bool enable = true) { detail::check(fmgpu_index_accelerate_extract(handle, enable ? 1 : 0)); }
+    // the symbols of every range, concatenated in the given order (fmgpu_extract); needs accelerateExtract()
+    auto extract(std::vector<fmgpu_text_range> const& ranges) const -> std::vector<uint8_t> {
+        uint64_t total = 0;
+        for (auto const& r : ranges) total += r.len;
+        std::vector<uint8_t> out(std::max<uint64_t>(total, 1));
+        uint64_t count = 0;
+        detail::check(fmgpu_extract(handle, ranges.data(), ranges.size(), out.data(), total, &count, nullptr, nullptr));
+        out.resize(count);
+        return out;
+    }
 };
 
 template <size_t TSigma, template <size_t> class String = string::FlattenedBitvectors_512_64k>   // fmindex/FMIndex.h:14
@@ -159,6 +171,62 @@ auto loadIndex(std::string const& fileName) -> Index {
     if (static_cast<size_t>(sigma) != Index::Sigma || (bidir != 0) != Index::IsBidirectional)
         throw std::runtime_error("loadIndex: " + fileName + " holds an index of Sigma " + std::to_string(sigma) + (bidir ? " (BiFMIndex)" : " (FMIndex)"));
     return index;
+}
+
+// reconstructText(index, seqNbr) / reconstructText(index) (utils.h:672-703): the sentinel rows (rank(size(), 0) of them) are located, each one's text runs from
+// the previous delimiter of its seqId (or pos 0) up to its own, and the symbols come from ONE fmgpu_extract call.  The extract table is built for the call
+// if the index lacks it, and dropped again.
+namespace detail {
+inline auto sentinelRanges(fmgpu_index_t h, uint64_t n) -> std::vector<fmgpu_text_range> {
+    uint64_t idx = n, nsent = 0;
+    uint8_t symb = 0, what = 0;
+    check(fmgpu_string_query(h, 0, &idx, &symb, &what, 1, &nsent, nullptr));
+    std::vector<uint64_t> rows(nsent), seq(nsent), pos(nsent), steps(nsent);
+    for (uint64_t i = 0; i < nsent; ++i) rows[i] = i;
+    if (nsent) check(fmgpu_locate(h, rows.data(), nsent, seq.data(), pos.data(), steps.data(), nullptr, nullptr));
+    for (uint64_t i = 0; i < nsent; ++i) pos[i] += steps[i];
+    std::vector<uint64_t> order(rows);
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return std::tie(seq[a], pos[a]) < std::tie(seq[b], pos[b]); });
+    std::vector<fmgpu_text_range> out(nsent);
+    for (uint64_t k = 0; k < nsent; ++k) {
+        const uint64_t i = order[k];
+        const uint64_t from = k > 0 && seq[order[k - 1]] == seq[i] ? pos[order[k - 1]] + 1 : 0;
+        out[i] = fmgpu_text_range{seq[i], from, pos[i] - from};
+    }
+    return out;
+}
+template <typename Index>
+auto extractWithTable(Index const& index, std::vector<fmgpu_text_range> const& ranges) -> std::vector<uint8_t> {
+    uint32_t mask = 0;
+    check(fmgpu_index_formats(index.handle, &mask));
+    const bool build = !(mask & FMGPU_FMT_EXTRACT);
+    if (build) check(fmgpu_index_accelerate_extract(index.handle, 1));
+    std::vector<uint8_t> out;
+    try { out = index.extract(ranges); } catch (...) { if (build) fmgpu_index_accelerate_extract(index.handle, 0); throw; }
+    if (build) check(fmgpu_index_accelerate_extract(index.handle, 0));
+    return out;
+}
+}  // namespace detail
+
+template <typename Index>
+auto reconstructText(Index const& index, size_t seqNbr) -> std::vector<uint8_t> {
+    auto const ranges = detail::sentinelRanges(index.handle, index.n);
+    if (seqNbr >= ranges.size()) throw std::out_of_range("reconstructText: seqNbr " + std::to_string(seqNbr) + " is not a sentinel row");
+    return detail::extractWithTable(index, {ranges[seqNbr]});
+}
+template <typename Index>
+auto reconstructText(Index const& index) -> std::vector<std::vector<uint8_t>> {
+    auto const ranges = detail::sentinelRanges(index.handle, index.n);
+    std::vector<size_t> order(ranges.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return std::tie(ranges[a].seq_id, a) < std::tie(ranges[b].seq_id, b); });   // (seqId, i)
+    std::vector<fmgpu_text_range> sorted;
+    for (size_t i : order) sorted.push_back(ranges[i]);
+    auto const sym = detail::extractWithTable(index, sorted);
+    std::vector<std::vector<uint8_t>> res;
+    size_t at = 0;
+    for (auto const& r : sorted) { res.emplace_back(sym.begin() + at, sym.begin() + at + r.len); at += r.len; }
+    return res;
 }
 
 // ------------------------------------------------------------------------------------------------ cursors

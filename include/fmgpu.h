@@ -234,6 +234,7 @@ int fmgpu_index_row_bits(fmgpu_index_t h, int32_t* bits);   /* 32 or 64: the wid
 #define FMGPU_FMT_PREFIX     (1u << 10)  /* prefix table of fmgpu_index_accelerate_search */
 #define FMGPU_FMT_LOCATE     (1u << 11)  /* locate answer table */
 #define FMGPU_FMT_FUSED      (1u << 12)  /* presence bits of the sampled suffix array fused into the blocks */
+#define FMGPU_FMT_EXTRACT    (1u << 13)  /* text map and sample table of fmgpu_index_accelerate_extract */
 int fmgpu_index_formats(fmgpu_index_t h, uint32_t* mask);
 
 /* The library's own index file — replaces saveIndex / loadIndex (fmindex/diskStorage.h:12-27) for a handle of this library: a header, a description of
@@ -284,6 +285,37 @@ int fmgpu_index_accelerate_search(fmgpu_index_t h, int32_t prefix_len, int32_t w
 /* Optional accelerator for fmgpu_locate (results unchanged): every row is located once and its (seqId, pos, steps) answer kept,
  * 12 bytes per row — one load per located row instead of ~samplingRate/2 LF steps with a presence-bit probe each.  enable = 0 drops it. */
 int fmgpu_index_accelerate_locate(fmgpu_index_t h, int32_t enable);
+
+/* Optional table for fmgpu_extract and fmgpu_sequence_lengths, built on the device from what the handle holds; enable = 0 drops it.
+ *   - Text map: the sentinel rows 0 .. C[1]-1 are located; per seqId (ascending) its length = the pos of its LAST delimiter, its end row = that
+ *     delimiter's sentinel row.  An earlier delimiter of the same seqId is an ordinary symbol 0 of the text.
+ *   - Sample table: every sampled row, ordered by (seqId, pos).  Sampling may be irregular.  About 12 bytes per sample with 32-bit rows.
+ * Returns FMGPU_ERR_UNSUPPORTED, and keeps nothing, if a sampled entry names a seqId no sentinel row gave (e.g. an index built without delimiters) or a
+ * pos beyond that seqId's length.  The table counts in device_bytes and sets FMGPU_FMT_EXTRACT.  fmgpu_index_save does not store it and
+ * fmgpu_index_clone does not carry it: call this again after a load or a clone.  Like the other accelerate calls it modifies the handle: not
+ * concurrently with other calls on the same handle. */
+int fmgpu_index_accelerate_extract(fmgpu_index_t h, int32_t enable);
+
+/* The text map of fmgpu_index_accelerate_extract: seqIds in ascending order and each one's length (without its last delimiter).  *out_count = the
+ * number of seqIds; FMGPU_ERR_CAPACITY (nothing written) if it exceeds `capacity`.  FMGPU_ERR_UNSUPPORTED without the table.  Host buffers. */
+int fmgpu_sequence_lengths(fmgpu_index_t h, uint64_t* seq_ids, uint64_t* lengths, uint64_t capacity, uint64_t* out_count);
+
+/* one text range of fmgpu_extract: symbols pos .. pos + len - 1 of sequence seq_id */
+typedef struct fmgpu_text_range {
+    uint64_t seq_id, pos, len;
+} fmgpu_text_range;     /* 24 bytes */
+
+/* Text symbols (ranks 0 .. sigma-1) of every range, concatenated in the given order, read from the index by LF walks on the device (the range is cut
+ * into pieces at the sampled positions inside it; each piece walks back from a sampled row or from the sequence's end row).  What the reference's
+ * reconstructText (utils.h:672-703) walks serially from each sequence's end.
+ *   - *out_count = the sum of len, on success and on FMGPU_ERR_CAPACITY alike; above `capacity` the call returns FMGPU_ERR_CAPACITY and writes nothing.
+ *   - FMGPU_ERR_INVALID: an unknown seq_id or pos + len beyond the sequence's length (checked on the device), a null ranges / out / out_count while
+ *     count > 0.  count == 0 returns 0.  FMGPU_ERR_UNSUPPORTED without fmgpu_index_accelerate_extract's table.
+ *   - ranges and out may be host or device memory; the call returns after completion (its scratch is freed).
+ *   - stats: lf_steps = LF steps walked (the symbols of every piece, including those a range's last piece walks past beyond its end), hits = symbols
+ *     written, kernel_ms = the walk kernel alone. */
+int fmgpu_extract(fmgpu_index_t h, const fmgpu_text_range* ranges, uint64_t count, uint8_t* out, uint64_t capacity, uint64_t* out_count,
+                  fmgpu_stats* stats, void* stream);
 
 /* String_c batch evaluation (string/concepts.h:25-87): what[i] selects 0 = rank(idx,symb), 1 = prefix_rank(idx,symb),
  * 2 = symbol(idx); which = 0 -> bwt, 1 -> bwtRev */
