@@ -103,7 +103,10 @@ __global__ __launch_bounds__(256) void k_exact_a(OccA<SIGMA> occ, const uint8_t*
 // ---- exact search in two-symbol steps on Format P (fmgpu_common.h): one 128-byte line per interval end and PAIR of symbols.  An exact search is bound
 // by the random line fills it causes (tools/membench.hip: 52-55 G dependent lines/s, whatever is read of a line), so halving the lines of a read halves
 // its time.  A pair whose interval comes out empty is taken again in one-symbol steps (Format A), which yields the row and the step count a
-// one-symbol search ends with; so is a pair that holds a delimiter or a byte outside the alphabet, and the last symbol of a read of odd length.
+// one-symbol search ends with; so is a pair that holds a delimiter or a byte outside the alphabet.  A read of odd length takes its LAST symbol c first, as
+// one step from [0, n) to [C[c], C[c + 1]) that reads no memory, and the pairs after it (backward search composes step by step: the same interval and step
+// count as any other order); with the interval table its first symbol is the one-symbol step at the end instead.  The read itself is loaded once, whole,
+// into registers (QueryWindow): no query byte is read inside the loop but every 63rd pass of a read of more than 127 symbols, which loads the next ones.
 constexpr uint32_t kPairFilterBits = 32768;          // line number mod this: the ~50 listed rows of a genome mark 0.15 % of the lines
 // ---- lines fetched by the eight lanes of an octet together (k_exact_p, k_exact_s).  A lane that reads 44-68 bytes of its own random line with four or five load
 // instructions pays as many address translations and passes through the texture path per line, and that — not the line fills — bounds such a kernel
@@ -169,12 +172,11 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
     const lds_word* const own = wave_lds + (lane & 7u) * (kCoopRegion / 4u) + (lane >> 3) * 32u;
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t steps = 0, acc = 0, acc2 = 0, m = 0;
+    uint64_t o = 0;
     idx_t lb = 0, len = n;
-    QueryReader qr;
     if (q < nq) {
-        const uint64_t o = qoff[q];
+        o = qoff[q];
         m = (uint32_t)(qoff[q + 1] - o);
-        if (m) qr.init(qbuf, o, m);
     }
     // one symbol, as k_exact_a does it; false once the search is over
     auto single = [&](uint32_t c) -> bool {
@@ -196,24 +198,42 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
     };
     bool alive = m != 0;
     uint32_t done = 0, lut_steps = 0, acc3 = 0;                     // symbols of the read consumed so far; steps an interval-table entry stood for; such entries read
-    if (slut && alive && m >= lutL && n > 1) {
-        uint32_t code = 0; bool valid = true;
-        for (uint32_t t = 0; t < lutL; ++t) { const uint32_t c = qr.next(); valid = valid && c - 1u < 4u; code |= ((c - 1u) & 3u) << (2u * t); }
-        idx_t elb = 0, elen = 0;
-        if (valid) {
-            if constexpr (kWide) { const ulonglong2 en = reinterpret_cast<const ulonglong2*>(slut)[code]; elb = (idx_t)en.x; elen = (idx_t)en.y; }
-            else { const uint2 en = reinterpret_cast<const uint2*>(slut)[code]; elb = en.x; elen = en.y; }
-            ++acc3;
+    const idx_t C1 = occ.v.C[1], C2 = occ.v.C[2], C3 = occ.v.C[3], C4 = occ.v.C[4], C5 = occ.v.C[5];     // (wave-uniform: for the odd symbol)
+    QueryWindow win;
+    win.fill(qbuf, o, m, 0u, 5u);
+    uint32_t d = 0, k = 0;                                          // the lane's next symbol: nibble 8 (k mod 4) + d of w[0]:w[1] (d = 1 after the odd symbol); k: passes since the fill
+    if (slut) {
+        if (alive && m >= lutL && n > 1) {                          // (lutL <= 16: 4^lutL entries)
+            const uint64_t first16 = (uint64_t)win.w[0] | ((uint64_t)win.w[1] << 32);
+            uint32_t code = 0; bool valid = true;
+            for (uint32_t t = 0; t < lutL; ++t) { const uint32_t c = (uint32_t)(first16 >> (4u * t)) & 15u; valid = valid && c - 1u < 4u; code |= ((c - 1u) & 3u) << (2u * t); }
+            idx_t elb = 0, elen = 0;
+            if (valid) {
+                if constexpr (kWide) { const ulonglong2 en = reinterpret_cast<const ulonglong2*>(slut)[code]; elb = (idx_t)en.x; elen = (idx_t)en.y; }
+                else { const uint2 en = reinterpret_cast<const uint2*>(slut)[code]; elb = en.x; elen = en.y; }
+                ++acc3;
+            }
+            if (elen != 0) { lb = elb; len = elen; done = lutL; steps = lutL; lut_steps = lutL; }
+            // (else a foreign byte among the symbols, or a string the text does not hold: from the start, step by step)
         }
-        if (elen != 0) { lb = elb; len = elen; done = lutL; steps = lutL; lut_steps = lutL; }
-        else qr.init(qbuf, qoff[q], m);                             // (a foreign byte among the symbols, or a string the text does not hold: from the start, step by step)
+        if (__ballot(done != 0u)) win.fill(qbuf, o, m, done, 5u);
+    } else if (m & 1u) {                                            // the odd symbol first
+        const uint32_t c = win.w[0] & 15u;
+        if (c - 1u < 4u) {
+            const idx_t c0 = c == 1u ? C1 : (c == 2u ? C2 : (c == 3u ? C3 : C4)), c1 = c == 1u ? C2 : (c == 2u ? C3 : (c == 3u ? C4 : C5));
+            ++steps; lb = c0; len = c1 - c0; alive = len != 0;
+        } else alive = single(c);                                   // (a delimiter or a byte outside the alphabet, as before)
+        done = 1; d = 1;
     }
     for (;;) {                                                      // every lane of the wave takes its next two symbols (or is done)
         if (done >= m) alive = false;
         if (!__ballot(alive)) break;
+        if (k == 63u) { win.fill(qbuf, o, m, done, 5u); d = 0; k = 0; }     // (a read of more than 127 symbols: its next 128)
         const bool two = alive && done + 2u <= m;
-        uint32_t y = 0, x = 0;
-        if (alive) { y = qr.next(); if (two) x = qr.next(); }
+        const uint32_t yx = __builtin_amdgcn_alignbit(win.w[1], win.w[0], 8u * (k & 3u) + 4u * d);
+        const uint32_t y = alive ? yx & 15u : 0u, x = two ? (yx >> 4) & 15u : 0u;
+        if ((k & 3u) == 3u) win.shift();
+        ++k;
         done += 2u;
         const bool pairable = two && y - 1u < 4u && x - 1u < 4u;
         bool stepped = false;

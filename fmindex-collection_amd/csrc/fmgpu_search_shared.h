@@ -78,6 +78,58 @@ struct QueryReader {
     }
 };
 
+// eight query bytes -> eight nibbles (a byte >= sigma, sigma <= 15, becomes 15 = "not a symbol"), with word operations
+__device__ __forceinline__ uint32_t pack_nibbles8(uint64_t x, uint32_t sigma) {
+    const uint64_t k1 = 0x0101010101010101ull;
+    const uint64_t t = (((x & (0x7full * k1)) + (uint64_t)(0x80u - sigma) * k1) | x) & (0x80ull * k1);   // bit 7 of a byte set <=> byte >= sigma
+    uint64_t y = (x | ((t >> 7) * 0xffull)) & (0x0full * k1);
+    y = (y | (y >> 4)) & 0x00ff00ff00ff00ffull;
+    y = (y | (y >> 8)) & 0x0000ffff0000ffffull;
+    y = (y | (y >> 16)) & 0x00000000ffffffffull;
+    return (uint32_t)y;
+}
+
+// ---- a read's symbols in registers (k_exact_p): 128 of them as nibbles in the order backward search consumes them — symbol `from` of that order (the read's
+// byte m - 1 - from) in the low nibble of w[0] — a byte >= sigma as 15.  A QueryReader loads one 8-byte word per lane every eight symbols, each time from a line the
+// lanes of the wave share (they are ~m bytes apart) and that the search's own random lines have pushed out of L2 since the last word: the same query line is
+// fetched again and again.  fill() takes the read's bytes at once instead, with nine aligned 16-byte loads that stay inside the read's own 16-byte chunks.
+// The words are only ever indexed by constants (shift() moves them down), so the window stays in registers.
+constexpr uint32_t kWindowWords = 16;
+struct QueryWindow {
+    uint32_t w[kWindowWords];
+    __device__ __forceinline__ void fill(const uint8_t* qbuf, uint64_t off, uint32_t m, uint32_t from, uint32_t sigma) {
+        const bool any = from < m;
+        const uint64_t first = (uint64_t)qbuf + off, last = first + (any ? m - 1u - from : 0u);    // the read's first byte; the byte consumed first
+        const uint4* const top = reinterpret_cast<const uint4*>(last & ~(uint64_t)15);             // the 16-byte chunk of `last`
+        const uint32_t span = (uint32_t)((last >> 4) - (first >> 4));                              // chunks below it that hold bytes of the read
+        uint4 v[9];                                                                                // (chunk top - k, or the read's lowest one)
+#pragma unroll
+        for (uint32_t k = 0; k < 9u; ++k) v[k] = make_uint4(0u, 0u, 0u, 0u);
+        if (any) {
+#pragma unroll
+            for (uint32_t k = 0; k < 9u; ++k) v[k] = *(top - min(k, span));
+        }
+        uint32_t p[18];                                              // the nibbles of the 8-byte words downwards from the top of chunk `top`, highest byte first
+#pragma unroll
+        for (uint32_t k = 0; k < 9u; ++k) {
+            p[2u * k] = pack_nibbles8(__builtin_bswap64((uint64_t)v[k].z | ((uint64_t)v[k].w << 32)), sigma);
+            p[2u * k + 1u] = pack_nibbles8(__builtin_bswap64((uint64_t)v[k].x | ((uint64_t)v[k].y << 32)), sigma);
+        }
+        const uint32_t upper = (last & 8u) ? ~0u : 0u;               // `last` is in the upper word of its chunk
+        uint32_t r[17];                                              // r[j]: the nibbles of the j-th word down from the one holding `last` (a mask, not an index:
+#pragma unroll                                                       //  a select between neighbours became a per-lane index into a scratch array)
+        for (uint32_t j = 0; j < 17u; ++j) r[j] = (p[j] & upper) | (p[j + 1u] & ~upper);
+        const uint32_t sh = 4u * (7u - ((uint32_t)last & 7u));       // the bytes of r[0] above `last`
+#pragma unroll
+        for (uint32_t i = 0; i < kWindowWords; ++i) w[i] = __builtin_amdgcn_alignbit(r[i + 1u], r[i], sh);
+    }
+    __device__ __forceinline__ void shift() {                        // the next eight symbols into w[0]
+#pragma unroll
+        for (uint32_t i = 0; i + 1u < kWindowWords; ++i) w[i] = w[i + 1u];
+        w[kWindowWords - 1u] = 0u;
+    }
+};
+
 // ------------------------------------------------------------------ DFS machinery
 constexpr int kMaxParts = 16;
 constexpr int kMaxSearches = 16;
@@ -463,16 +515,6 @@ __device__ __forceinline__ uint32_t symbol_of_lf_lds(const idx_t* sC, uint32_t s
     return lo;
 }
 
-// eight query bytes -> eight nibbles (a byte >= sigma, sigma <= 15, becomes 15 = "not a symbol"), with word operations
-__device__ __forceinline__ uint32_t pack_nibbles8(uint64_t x, uint32_t sigma) {
-    const uint64_t k1 = 0x0101010101010101ull;
-    const uint64_t t = (((x & (0x7full * k1)) + (uint64_t)(0x80u - sigma) * k1) | x) & (0x80ull * k1);   // bit 7 of a byte set <=> byte >= sigma
-    uint64_t y = (x | ((t >> 7) * 0xffull)) & (0x0full * k1);
-    y = (y | (y >> 4)) & 0x00ff00ff00ff00ffull;
-    y = (y | (y >> 8)) & 0x0000ffff0000ffffull;
-    y = (y | (y >> 16)) & 0x00000000ffffffffull;
-    return (uint32_t)y;
-}
 // ---- per-lane query staging in LDS ------------------------------------------------------------------------------
 // A DFS visits a few hundred nodes per query; reading the query symbol of every node from global memory costs a
 // second random line per node (half a million lanes' query lines do not survive in L2).  Each lane therefore copies
