@@ -18,7 +18,8 @@ from .capi import FmgpuError, DeviceBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSI
 from . import search_scheme  # noqa: F401
 
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "LocateLinear", "search_locate", "reconstruct_text",
-           "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options"]
+           "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
+           "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device"]
 
 
 class _Options:
@@ -434,7 +435,106 @@ class BiFMIndex(FMIndex):
     bidirectional = True
 
 
+class PackedQueries:
+    """a batch in the 4-bit packed query form (include/fmgpu.h): symbol i = nibble i & 1 of byte i >> 1 of `packed`, the even index in the low nibble; `qoff` as in the
+    byte form (nq + 1 symbol offsets).  Both are numpy arrays or DeviceBuffers.  Accepted wherever (qbuf, qoff) is: the `_q4` entry points serve it."""
+
+    def __init__(self, packed, qoff, nq=None):
+        self.packed, self.qoff = packed, qoff
+        self.nq = int(nq) if nq is not None else len(qoff) - 1
+
+    def host(self):
+        """(packed, qoff) as numpy arrays (copied back where they are DeviceBuffers)"""
+        qoff = self.qoff if isinstance(self.qoff, np.ndarray) else self.qoff.to_array(np.uint64, self.nq + 1)
+        packed = self.packed if isinstance(self.packed, np.ndarray) else self.packed.to_array(np.uint8, (int(qoff[-1]) + 1) // 2)
+        return packed, qoff
+
+
+def _host_batch(queries):
+    if isinstance(queries, tuple):
+        return np.asarray(queries[0], dtype=np.uint8), np.asarray(queries[1], dtype=np.uint64)
+    return flatten(queries)
+
+
+def pack_queries(queries, sigma, complement=None):
+    """(qbuf, qoff) or a list of sequences -> PackedQueries of numpy arrays, byte for byte what fmgpu_queries_pack4 makes: a byte >= sigma becomes 15, the batch starts
+    at symbol 0, a nibble left over in the last byte is 0.  complement (sigma entries): 2 nq reads, read 2q = read q, read 2q + 1 = read q reversed with
+    complement[c] for c < sigma and 15 for the rest."""
+    if not 2 <= sigma <= 15:
+        raise ValueError("4-bit packed queries need 2 <= sigma <= 15")
+    qbuf, qoff = _host_batch(queries)
+    nq = len(qoff) - 1
+    first, last = (int(qoff[0]), int(qoff[-1])) if nq >= 0 and len(qoff) else (0, 0)
+    sym = qbuf[first:last].astype(np.uint8)
+    start = (qoff[:-1] - qoff[0]).astype(np.int64)
+    lens = np.diff(qoff.astype(np.int64))
+    fwd = np.where(sym < sigma, sym, 15).astype(np.uint8)
+    if complement is None:
+        nib, out_qoff = fwd, (qoff - qoff[0]).astype(np.uint64)
+    else:
+        comp = np.full(256, 15, dtype=np.uint8)
+        comp[:sigma] = np.asarray(complement, dtype=np.uint8)[:sigma]
+        comp[comp >= sigma] = 15
+        rid = np.repeat(np.arange(nq), lens)
+        j = np.arange(sym.size, dtype=np.int64) - start[rid]
+        nib = np.zeros(2 * sym.size, dtype=np.uint8)
+        nib[2 * start[rid] + j] = fwd
+        nib[2 * start[rid] + 2 * lens[rid] - 1 - j] = comp[sym]
+        out_qoff = np.zeros(2 * nq + 1, dtype=np.uint64)
+        out_qoff[0:-1:2] = 2 * start
+        out_qoff[1::2] = 2 * start + lens
+        out_qoff[-1] = 2 * sym.size
+    if nib.size & 1:
+        nib = np.concatenate([nib, np.zeros(1, dtype=np.uint8)])
+    packed = (nib[0::2] | (nib[1::2] << 4)).astype(np.uint8)
+    return PackedQueries(packed, out_qoff)
+
+
+def unpack_queries(queries):
+    """PackedQueries or (packed, qoff) -> (qbuf, qoff) of the byte form, starting at symbol 0: nibble 15 comes back as 255 (what fmgpu_queries_unpack4 writes)"""
+    packed, qoff = queries.host() if isinstance(queries, PackedQueries) else (np.asarray(queries[0], dtype=np.uint8), np.asarray(queries[1], dtype=np.uint64))
+    first, last = int(qoff[0]), int(qoff[-1])
+    at = np.arange(first, last, dtype=np.int64)
+    nib = (packed[at >> 1] >> (4 * (at & 1)).astype(np.uint8)) & 15
+    qbuf = np.where(nib == 15, 255, nib).astype(np.uint8)
+    return qbuf, (qoff - qoff[0]).astype(np.uint64)
+
+
+def pack_queries_device(queries, sigma, complement=None, stream=None):
+    """fmgpu_queries_pack4: the batch ((qbuf, qoff) of numpy arrays or DeviceBuffers, or a list of sequences) packed on the device -> PackedQueries of DeviceBuffers"""
+    qbuf, qoff, nq = _queries(queries)
+    ends = qoff if isinstance(qoff, np.ndarray) else qoff.to_array(np.uint64, nq + 1)
+    total = (int(ends[-1]) - int(ends[0])) * (2 if complement is not None else 1)
+    nreads = 2 * nq if complement is not None else nq
+    packed, out_qoff = DeviceBuffer(max((total + 1) // 2, 8)), DeviceBuffer((nreads + 1) * 8)
+    comp = None if complement is None else np.ascontiguousarray(np.asarray(complement, dtype=np.uint8))
+    if nq == 0:
+        capi.check(capi.lib().fmgpu_memcpy_h2d(capi.ptr(out_qoff), capi.ptr(np.zeros(1, dtype=np.uint64)), 8))
+    capi.check(capi.lib().fmgpu_queries_pack4(capi.ptr(qbuf), capi.ptr(qoff), nq, sigma, capi.ptr(comp), capi.ptr(packed), capi.ptr(out_qoff), stream))
+    return PackedQueries(packed, out_qoff, nreads)
+
+
+def _q4(queries, byte_call, q4_call):
+    """the entry point that takes `queries`: the `_q4` one for a PackedQueries"""
+    return q4_call if isinstance(queries, PackedQueries) else byte_call
+
+
+def _host_bytes(queries):
+    """the batch as host (qbuf, qoff, nq) of the byte form, for the facades that split a batch by length on the host"""
+    if isinstance(queries, PackedQueries):
+        qbuf, qoff = unpack_queries(queries)
+        return qbuf, qoff, queries.nq
+    qbuf, qoff, nq = _queries(queries)
+    if not isinstance(qoff, np.ndarray):
+        qoff = qoff.to_array(np.uint64, nq + 1) if isinstance(qoff, DeviceBuffer) else np.asarray(qoff)
+    if not isinstance(qbuf, np.ndarray):
+        qbuf = qbuf.to_array(np.uint8, int(qoff[-1]))
+    return qbuf, qoff, nq
+
+
 def _queries(queries):
+    if isinstance(queries, PackedQueries):
+        return queries.packed, queries.qoff, queries.nq
     if isinstance(queries, tuple):
         qbuf, qoff = queries
         nq = (qoff.nbytes // 8 if not hasattr(qoff, "__len__") else len(qoff)) - 1
@@ -457,8 +557,8 @@ class search_no_errors:
         else:
             lb, ln = out
         st = capi.Stats()
-        capi.check(capi.lib().fmgpu_search_exact(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, capi.ptr(lb), capi.ptr(ln),
-                                                 C.byref(st) if want_stats else None, None))
+        call = _q4(queries, capi.lib().fmgpu_search_exact, capi.lib().fmgpu_search_exact_q4)
+        capi.check(call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, capi.ptr(lb), capi.ptr(ln), C.byref(st) if want_stats else None, None))
         return (lb, ln, st) if want_stats else (lb, ln)
 
 
@@ -524,7 +624,8 @@ class search_ng26:
         sc.partition = part.ctypes.data_as(capi.u64p) if part is not None else None
         sc.edit = 1 if edit else 0
         cap = capacity if capacity is not None else max(1024, 4 * nq)
-        hits, st = _run_hits(lambda out, c, cnt, st: capi.lib().fmgpu_search_scheme(
+        call = _q4(queries, capi.lib().fmgpu_search_scheme, capi.lib().fmgpu_search_scheme_q4)
+        hits, st = _run_hits(lambda out, c, cnt, st: call(
             index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(sc), n, capi.ptr(out), c, C.byref(cnt), C.byref(st), None), cap)
         return (hits, st) if want_stats else hits
 
@@ -616,7 +717,8 @@ class search_ng21:
         sc.n_searches, sc.length = (pi.shape if pi.ndim == 2 else (0, 0))
         sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
         cap = capacity if capacity is not None else max(1024, 4 * nq)
-        hits, st = _run_hits(lambda out, c, cnt, st: capi.lib().fmgpu_search_ng21(
+        call = _q4(queries, capi.lib().fmgpu_search_ng21, capi.lib().fmgpu_search_ng21_q4)
+        hits, st = _run_hits(lambda out, c, cnt, st: call(
             index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(sc), n, capi.ptr(out), c, C.byref(cnt), C.byref(st), None), cap)
         return (hits, st) if want_stats else hits
 
@@ -659,11 +761,7 @@ class search_ng21:
 def _auto_scheme_search(index, queries, errors, n, edit, compat_auto_scheme):
     """search_ng26::search<Edit>(index, queries, maxErrors, delegate, n) (search/SearchNg26.h:436-444): per query length the cached scheme
     h2(maxErrors + (length == 2 ? 1 : 2), 0, maxErrors) (CachedSearchScheme.h:16-36) with a uniform partition"""
-    qbuf, qoff, nq = _queries(queries)
-    if not isinstance(qoff, np.ndarray):                      # the facade splits the batch by length on the host
-        qoff = qoff.to_array(np.uint64, nq + 1) if isinstance(qoff, DeviceBuffer) else np.asarray(qoff)
-    if not isinstance(qbuf, np.ndarray):
-        qbuf = qbuf.to_array(np.uint8, int(qoff[-1]))
+    qbuf, qoff, nq = _host_bytes(queries)                     # the facade splits the batch by length on the host
     lens = np.diff(qoff.astype(np.int64))
 
     def scheme_for(short):
@@ -676,8 +774,8 @@ def _auto_scheme_search(index, queries, errors, n, edit, compat_auto_scheme):
         if sel.size == 0:
             continue
         sub = [qbuf[int(qoff[i]): int(qoff[i + 1])] for i in sel] if sel.size != nq else None
-        qb, qo = (qbuf, qoff) if sub is None else flatten(sub)
-        hits = search_ng26.search(index, (qb, qo), scheme_for(short), None, n, edit=edit)
+        batch = (queries if isinstance(queries, PackedQueries) else (qbuf, qoff)) if sub is None else flatten(sub)     # (a packed batch of one length class goes down as it is)
+        hits = search_ng26.search(index, batch, scheme_for(short), None, n, edit=edit)
         if sub is not None:
             hits = hits.copy()
             hits["qidx"] = sel.astype(np.uint64)[hits["qidx"].astype(np.int64)]
@@ -756,7 +854,7 @@ class LocateLinear:
         return self.owner, seq, pos, steps
 
 
-def _device_hits(index, qbuf, qoff, nq, scheme, n, edit):
+def _device_hits(index, qbuf, qoff, nq, scheme, n, edit, q4=False):
     """search_ng26 over one batch with the hit records left in HBM and put into callback order there: (DeviceBuffer, count)"""
     pi, l, u = (_u64(x) for x in scheme)
     sc = capi.Scheme()
@@ -766,7 +864,8 @@ def _device_hits(index, qbuf, qoff, nq, scheme, n, edit):
     cap, cnt = max(1024, 4 * nq), C.c_uint64()
     for _ in range(2):
         buf = DeviceBuffer(cap * HIT_DTYPE.itemsize)
-        rc = capi.lib().fmgpu_search_scheme(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(sc), n, capi.ptr(buf), cap, C.byref(cnt), None, None)
+        call = capi.lib().fmgpu_search_scheme_q4 if q4 else capi.lib().fmgpu_search_scheme
+        rc = call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(sc), n, capi.ptr(buf), cap, C.byref(cnt), None, None)
         if rc != capi.FMGPU_ERR_CAPACITY:
             break
         buf.free()
@@ -801,11 +900,7 @@ def search_locate(index, queries, errors, n=UINT64_MAX, edit=True, compat_auto_s
     if errors == 0 and n == UINT64_MAX:                       # search_no_errors: one cursor per query, its {lb, len} come back anyway
         hits = search(index, queries, 0)
         return index.locate_hits(hits)[fields]
-    qbuf, qoff, nq = _queries(queries)
-    if not isinstance(qoff, np.ndarray):                      # the length classes are split on the host, as in _auto_scheme_search
-        qoff = qoff.to_array(np.uint64, nq + 1) if isinstance(qoff, DeviceBuffer) else np.asarray(qoff)
-    if not isinstance(qbuf, np.ndarray):
-        qbuf = qbuf.to_array(np.uint8, int(qoff[-1]))
+    qbuf, qoff, nq = _host_bytes(queries)                     # the length classes are split on the host, as in _auto_scheme_search
     lens = np.diff(qoff.astype(np.int64))
     parts = []
     for short in (False, True):
@@ -815,8 +910,11 @@ def search_locate(index, queries, errors, n=UINT64_MAX, edit=True, compat_auto_s
         sc = search_scheme.h2(errors + (1 if short else 2), 0, errors)
         if compat_auto_scheme and not edit:
             sc = search_scheme.limitToHamming(sc)
-        qb, qo = (qbuf, qoff) if sel.size == nq else flatten([qbuf[int(qoff[i]): int(qoff[i + 1])] for i in sel])
-        hits, count = _device_hits(index, qb, qo, sel.size, sc, n, edit)
+        whole = sel.size == nq
+        qb, qo = (qbuf, qoff) if whole else flatten([qbuf[int(qoff[i]): int(qoff[i + 1])] for i in sel])
+        if whole and isinstance(queries, PackedQueries):      # (a packed batch of one length class goes down as it is)
+            qb, qo = queries.packed, queries.qoff
+        hits, count = _device_hits(index, qb, qo, sel.size, sc, n, edit, q4=whole and isinstance(queries, PackedQueries))
         pos = _device_positions(index, hits, count)
         hits.free()
         if sel.size != nq:

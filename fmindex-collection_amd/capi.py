@@ -119,6 +119,7 @@ EXPORTS = [
     "fmgpu_replicas_search_ng21", "fmgpu_replicas_locate",
     "fmgpu_set_option", "fmgpu_get_option", "fmgpu_index_formats", "fmgpu_index_clone", "fmgpu_replicas_peer_copies",
     "fmgpu_index_accelerate_extract", "fmgpu_sequence_lengths", "fmgpu_extract",
+    "fmgpu_queries_pack4", "fmgpu_queries_unpack4", "fmgpu_search_exact_q4", "fmgpu_search_scheme_q4", "fmgpu_search_ng21_q4",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -130,6 +131,7 @@ OPTION_DEFAULTS = {"pair_table": 1, "dense_dna": 1, "symbol_planes": 1, "expand_
 SEL_GENERAL_DFS, SEL_NO_PREFIX_TABLE, SEL_NO_LF3, SEL_NO_LF_GENERAL, SEL_NO_WALK_TABLE, SEL_NO_LENGTH_BUCKETS = 2, 4, 8, 16, 32, 64
 SEL_EXACT_ON_TREE, SEL_EXACT_ONE_SYMBOL, SEL_LOCATE_PER_LANE, SEL_NO_SHARING, SEL_NO_EXACT_LUT, SEL_LEAN_FORMAT_A, SEL_NO_LEAN = 1 << 21, 1 << 22, 1 << 23, 1 << 24, 1 << 25, 1 << 29, 1 << 30
 SEL_NO_BOARD = 1 << 26
+SEL_UNPACK_QUERIES = 1 << 27
 # fmgpu_index_formats bits: what a handle holds beside (or as) the layout it was given
 FMT_BLOCKS, FMT_PAIRS, FMT_DENSE, FMT_PLANES, FMT_TREE, FMT_REFERENCE, FMT_LF, FMT_KSTEP, FMT_INTERVALS, FMT_WALK, FMT_PREFIX, FMT_LOCATE, FMT_FUSED = (1 << k for k in range(13))
 FMT_EXTRACT = 1 << 13
@@ -225,6 +227,11 @@ def lib():
         L.fmgpu_replicas_search_scheme.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Scheme), C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.POINTER(Stats)]
         L.fmgpu_replicas_search_ng21.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ExpandedScheme), C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.POINTER(Stats)]
         L.fmgpu_replicas_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    L.fmgpu_queries_pack4.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmgpu_queries_unpack4.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.fmgpu_search_exact_q4.argtypes = L.fmgpu_search_exact.argtypes
+    L.fmgpu_search_scheme_q4.argtypes = L.fmgpu_search_scheme.argtypes
+    L.fmgpu_search_ng21_q4.argtypes = L.fmgpu_search_ng21.argtypes
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

@@ -271,6 +271,17 @@ int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff
                       fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
     ROUTE(h, fmgpu_search_ng21(h, qbuf, qoff, nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream));
 }
+int fmgpu_search_exact_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats, void* stream) {
+    ROUTE(h, fmgpu_search_exact_q4(h, packed, qoff, nq, out_lb, out_len, stats, stream));
+}
+int fmgpu_search_scheme_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* scheme, uint64_t max_hits_per_query,
+                           fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
+    ROUTE(h, fmgpu_search_scheme_q4(h, packed, qoff, nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream));
+}
+int fmgpu_search_ng21_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, const fmgpu_expanded_scheme* scheme, uint64_t max_hits_per_query,
+                         fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
+    ROUTE(h, fmgpu_search_ng21_q4(h, packed, qoff, nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream));
+}
 int fmgpu_search_backtracking(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint64_t max_errors, fmgpu_hit* out, uint64_t capacity,
                               uint64_t* out_count, fmgpu_stats* stats, void* stream) {
     ROUTE(h, fmgpu_search_backtracking(h, qbuf, qoff, nq, max_errors, out, capacity, out_count, stats, stream));

@@ -179,6 +179,19 @@ struct Staged {
     ~Staged();
 };
 
+// A batch in the 4-bit packed query form (include/fmgpu.h) unpacked for a launcher that reads one byte per symbol (fmgpu_queries.hip): the offsets and the packed
+// bytes are staged where they are host memory, a device pass writes byte qoff[0] + i of a scratch for symbol qoff[0] + i, and the launcher is handed qbuf() / qoff(), both
+// device memory.  The scratch lives as long as this object, whose end waits for the stream (the launcher's kernels read it).
+struct UnpackedQueries {
+    Staged off, packed;
+    DBuf bytes;
+    hipStream_t stream = nullptr;
+    const uint8_t* qbuf() const { return bytes.as<uint8_t>(); }
+    const uint64_t* qoff() const { return reinterpret_cast<const uint64_t*>(off.dev); }
+    ~UnpackedQueries() { if (bytes.p) (void)hipStreamSynchronize(stream); }
+};
+int unpack_queries(const uint8_t* packed, const uint64_t* qoff, uint64_t nq, hipStream_t stream, UnpackedQueries* out);    // nq > 0, neither pointer null
+
 struct Built {   // host copies of construction by-products (fmgpu_build_index with keep_host)
     std::vector<std::vector<uint8_t>> part;
 };

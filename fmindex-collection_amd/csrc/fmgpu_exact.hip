@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void k_exact_depth(Occ occ, const uint8_t* __r
 
 template <int SIGMA>
 __device__ __noinline__ void lf0_pair(const OccA<SIGMA>& occ, idx_t a, idx_t b, idx_t& ra, idx_t& rb) { ra = occ.lf0_fused(a); rb = occ.lf0_fused(b); }
-template <int SIGMA>
+template <int SIGMA, class Q>
 __global__ __launch_bounds__(256) void k_exact_a(OccA<SIGMA> occ, const uint8_t* __restrict__ qbuf, const uint64_t* __restrict__ qoff,
                                                  uint64_t nq, idx_t n, uint64_t* __restrict__ out_lb, uint64_t* __restrict__ out_len,
                                                  unsigned long long* __restrict__ steps_total) {
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void k_exact_a(OccA<SIGMA> occ, const uint8_t*
         const uint32_t sigma = occ.sigma();
         idx_t lb = 0, len = n;
         if (m) {
-            QueryReader qr; qr.init(qbuf, o, m);
+            QueryReader<Q> qr; qr.init(qbuf, o, m);
             for (uint32_t i = 0; i < m; ++i) {
                 uint32_t c = qr.next();
                 ++steps;
@@ -142,6 +142,8 @@ __device__ __forceinline__ uint32_t pair_rank_lds(const lds_word* own, uint32_t 
 // slut != null (fmgpu_index_accelerate_exact(h, 1, lutL, 0) on a handle with the pair table): a read whose last lutL symbols are all in 1..4 starts from the interval-table
 // entry of those symbols (one 8 / 16-byte load from a table of 4^lutL entries — 12 symbols: 134 MB, Infinity-Cache resident — instead of lutL / 2 pair steps whose two interval
 // ends lie in two lines each); an empty entry is walked from the start instead, so the miss row and the step count stay the one-symbol search's.
+// Q: the query source (ByteQueries, or NibbleQueries for fmgpu_search_exact_q4: the window is filled from the packed form, everything after the fill is the same).
+template <class Q>
 __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __restrict__ pairs, const idx_t* __restrict__ ex, uint32_t nex, const idx_t* __restrict__ psuper,
                                                  const void* __restrict__ slut, uint32_t lutL,
                                                  const uint8_t* __restrict__ qbuf, const uint64_t* __restrict__ qoff,
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
     uint32_t done = 0, lut_steps = 0, acc3 = 0;                     // symbols of the read consumed so far; steps an interval-table entry stood for; such entries read
     const idx_t C1 = occ.v.C[1], C2 = occ.v.C[2], C3 = occ.v.C[3], C4 = occ.v.C[4], C5 = occ.v.C[5];     // (wave-uniform: for the odd symbol)
     QueryWindow win;
-    win.fill(qbuf, o, m, 0u, 5u);
+    win.template fill<Q>(qbuf, o, m, 0u, 5u);
     uint32_t d = 0, k = 0;                                          // the lane's next symbol: nibble 8 (k mod 4) + d of w[0]:w[1] (d = 1 after the odd symbol); k: passes since the fill
     if (slut) {
         if (alive && m >= lutL && n > 1) {                          // (lutL <= 16: 4^lutL entries)
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
             if (elen != 0) { lb = elb; len = elen; done = lutL; steps = lutL; lut_steps = lutL; }
             // (else a foreign byte among the symbols, or a string the text does not hold: from the start, step by step)
         }
-        if (__ballot(done != 0u)) win.fill(qbuf, o, m, done, 5u);
+        if (__ballot(done != 0u)) win.template fill<Q>(qbuf, o, m, done, 5u);
     } else if (m & 1u) {                                            // the odd symbol first
         const uint32_t c = win.w[0] & 15u;
         if (c - 1u < 4u) {
@@ -228,7 +230,7 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
     for (;;) {                                                      // every lane of the wave takes its next two symbols (or is done)
         if (done >= m) alive = false;
         if (!__ballot(alive)) break;
-        if (k == 63u) { win.fill(qbuf, o, m, done, 5u); d = 0; k = 0; }     // (a read of more than 127 symbols: its next 128)
+        if (k == 63u) { win.template fill<Q>(qbuf, o, m, done, 5u); d = 0; k = 0; }     // (a read of more than 127 symbols: its next 128)
         const bool two = alive && done + 2u <= m;
         const uint32_t yx = __builtin_amdgcn_alignbit(win.w[1], win.w[0], 8u * (k & 3u) + 4u * d);
         const uint32_t y = alive ? yx & 15u : 0u, x = two ? (yx >> 4) & 15u : 0u;
@@ -350,7 +352,7 @@ __global__ __launch_bounds__(BLOCK) void k_exact_s(const uint8_t* __restrict__ f
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t steps = 0, acc = 0, m = 0;
     idx_t lb = 0, len = n;
-    QueryReader qr;
+    QueryReader<> qr;
     if (q < nq) {
         const uint64_t o = qoff[q];
         m = (uint32_t)(qoff[q + 1] - o);
@@ -660,8 +662,20 @@ __global__ __launch_bounds__(256) void k_exact_kstep(Occ occ, ExactAccel ac, uin
 namespace api {
 #include "fmgpu_api_decl.h"
 
+// the pair table with an interval table in front of it (and no other table): k_exact_p starts from the entry of the read's last symbols
+static bool exact_pair_lut(const Index* x) {
+    return x->bwt.sigma == 5 && x->bwt.pairs && x->bwt.slut && !x->bwt.kblk && !x->bwt.walkj && x->bwt.search_family() == FAM_A &&
+           !(kernel_flags() & (FMGPU_SEL_EXACT_ONE_SYMBOL | FMGPU_SEL_NO_EXACT_LUT));
+}
+// 4-bit packed queries are read as they are by k_exact_p and k_exact_a (no k-step / walk table in front); every other kernel gets them unpacked
+static bool exact_reads_nibbles(const Index* x) {
+    const bool tables = x->bwt.kblk || x->bwt.slut || x->bwt.walkj;
+    return x->bwt.search_family() == FAM_A && (!tables || exact_pair_lut(x)) && !(kernel_flags() & FMGPU_SEL_UNPACK_QUERIES);
+}
+
+// q4: qbuf is the 4-bit packed form (only where exact_reads_nibbles(x) holds)
 static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
-                        uint64_t* out_lb, uint64_t* out_len, bool packed, fmgpu_stats* stats, void* stream_) {
+                        uint64_t* out_lb, uint64_t* out_len, bool packed, fmgpu_stats* stats, void* stream_, bool q4 = false) {
     size_t dev_extra_lds = 0;                                      // dev knob: unused dynamic LDS per block, to limit the resident blocks per CU
     { const char* ev = dev_env("FMGPU_DEV_EXACT_LDS"); if (ev) dev_extra_lds = (size_t)atoi(ev); }
     Index* x = reinterpret_cast<Index*>(h);
@@ -680,7 +694,7 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
     bool have_shape = false;                                     // offsets in HBM: total and length range come back in one copy
     if (is_device_pointer(qoff)) { if ((rc = query_shape((const uint64_t*)soff.dev, nq, stream, &shape_max, &shape_min, &total))) return rc; have_shape = true; }
     else total = qoff[nq];
-    if ((rc = sbuf.in(qbuf, total, stream))) return rc;
+    if ((rc = sbuf.in(qbuf, q4 ? (total + 1) / 2 : total, stream))) return rc;
     if ((rc = slb.out(out_lb, nq * 8, stream))) return rc;
     if (out_len && (rc = slen.out(out_len, nq * 8, stream))) return rc;   // (packed form: slen.dev stays null and the kernels write one word per query)
     unsigned long long* dsteps = nullptr;
@@ -691,9 +705,7 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
     const idx_t n = (idx_t)x->bwt.n;
     timer.start();
     uint32_t kq_words = 0, kq_max = 0, kq_nib = x->bwt.sigma <= 15 ? 1u : 0u;
-    // the pair table with an interval table in front of it (and no other table): k_exact_p starts from the entry of the read's last symbols
-    const bool pair_lut = x->bwt.sigma == 5 && x->bwt.pairs && x->bwt.slut && !x->bwt.kblk && !x->bwt.walkj && x->bwt.search_family() == FAM_A &&
-                          !(kernel_flags() & (FMGPU_SEL_EXACT_ONE_SYMBOL | FMGPU_SEL_NO_EXACT_LUT));
+    const bool pair_lut = exact_pair_lut(x);
     // ... and so does k_exact_s behind the symbol planes
     const bool flat_lut = x->bwt.flat && x->bwt.search_family() != FAM_A && x->bwt.slut && !x->bwt.kblk && !x->bwt.walkj && !(kernel_flags() & (FMGPU_SEL_EXACT_ON_TREE | FMGPU_SEL_NO_EXACT_LUT));
     const bool accel = (x->bwt.kblk || x->bwt.slut || x->bwt.walkj) && !pair_lut && !flat_lut;
@@ -720,11 +732,15 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
         // k_exact_a runs best with 5 resident blocks per CU, not the 8 its 28 registers allow (measured on the 3.09 Gbp index, 10 M x 101 bp: 8 / 6 / 5 / 4 / 3
         // blocks = 19.53 / 19.23 / 18.92 / 19.10 / 18.95 ms — more waves only queue up at the memory system): 28 KB of unused dynamic LDS set the residency
         const size_t lds_a = dev_env("FMGPU_DEV_EXACT_LDS") ? dev_extra_lds : (size_t)28 * 1024;
-        if (x->bwt.sigma == 5 && x->bwt.pairs && !(kernel_flags() & (1 << 22)))
-            k_exact_p<<<grid, block, 4 * 8 * kCoopRegion + dev_extra_lds, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super,
-                                                                                    pair_lut ? (const void*)x->bwt.slut : nullptr, x->bwt.slut_len, qb, qo, nq, n, ol, on, dsteps);
-        else if (x->bwt.sigma == 5) k_exact_a<5><<<grid, block, lds_a, stream>>>(OccA<5>{x->bwt.va}, qb, qo, nq, n, ol, on, dsteps);
-        else k_exact_a<0><<<grid, block, lds_a, stream>>>(OccA<0>{x->bwt.va}, qb, qo, nq, n, ol, on, dsteps);
+        auto launch = [&](auto src) {                            // the kernel of the byte form or of the 4-bit packed form
+            using Q = decltype(src);
+            if (x->bwt.sigma == 5 && x->bwt.pairs && !(kernel_flags() & (1 << 22)))
+                k_exact_p<Q><<<grid, block, 4 * 8 * kCoopRegion + dev_extra_lds, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super,
+                                                                                           pair_lut ? (const void*)x->bwt.slut : nullptr, x->bwt.slut_len, qb, qo, nq, n, ol, on, dsteps);
+            else if (x->bwt.sigma == 5) k_exact_a<5, Q><<<grid, block, lds_a, stream>>>(OccA<5>{x->bwt.va}, qb, qo, nq, n, ol, on, dsteps);
+            else k_exact_a<0, Q><<<grid, block, lds_a, stream>>>(OccA<0>{x->bwt.va}, qb, qo, nq, n, ol, on, dsteps);
+        };
+        if (q4) launch(NibbleQueries{}); else launch(ByteQueries{});
     } else if (x->bwt.flat && x->bwt.search_family() != FAM_A && !(kernel_flags() & (1 << 21))) {
         const uint32_t entries = x->bwt.flat_nsb * (uint32_t)x->bwt.sigma;
         size_t lds_max = kFlatSuperLdsMax;
@@ -792,6 +808,21 @@ int fmgpu_search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qof
 int fmgpu_search_exact_packed(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
                               uint64_t* out_interval, fmgpu_stats* stats, void* stream) {
     return search_exact(h, qbuf, qoff, nq, out_interval, nullptr, true, stats, stream);
+}
+
+// fmgpu_search_exact for a batch in the 4-bit packed query form.  k_exact_p and k_exact_a read the nibbles themselves; in front of every other kernel (k-step / walk
+// tables, symbol planes, the wavelet tree, reference blocks) the batch is unpacked into a per-call byte scratch, which is freed on return, after the stream has drained.
+int fmgpu_search_exact_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq,
+                          uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats, void* stream) {
+    Index* x = reinterpret_cast<Index*>(h);
+    if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
+    if (x->bwt.sigma > 15) return fail(FMGPU_ERR_UNSUPPORTED, "4-bit packed queries need sigma <= 15, this index has sigma = " + std::to_string(x->bwt.sigma));
+    if (exact_reads_nibbles(x)) return search_exact(h, packed, qoff, nq, out_lb, out_len, false, stats, stream, true);
+    if (!nq || !packed || !qoff || !out_lb || !out_len) return search_exact(h, packed, qoff, nq, out_lb, out_len, false, stats, stream);     // (the byte call's own answer)
+    if (int drc = on_handle_device(x)) return drc;
+    UnpackedQueries u;
+    if (int rc = unpack_queries(packed, qoff, nq, (hipStream_t)stream, &u)) return rc;
+    return search_exact(h, u.qbuf(), u.qoff(), nq, out_lb, out_len, false, stats, stream);
 }
 
 int fmgpu_search_exact_depth(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint32_t* out_depth, void* stream_) {

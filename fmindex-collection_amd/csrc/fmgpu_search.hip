@@ -3111,6 +3111,35 @@ int fmgpu_search_scheme(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
     return run_dfs(x, true, qbuf, qoff, nq, scheme, max_hits_per_query, 0, out, capacity, out_count, stats, (hipStream_t)stream);
 }
 
+// ---- the same two searches for a batch in the 4-bit packed query form: the batch is unpacked into a per-call byte scratch and the byte launcher runs unchanged
+// (a k-mismatch read visits hundreds of nodes: the scratch's 1.5 bytes per symbol of device traffic do not show).  The scratch is freed on return, after the stream has drained.
+static int q4_index(fmgpu_index_t h, Index** out) {
+    Index* x = reinterpret_cast<Index*>(h);
+    if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
+    if (x->bwt.sigma > 15) return fail(FMGPU_ERR_UNSUPPORTED, "4-bit packed queries need sigma <= 15, this index has sigma = " + std::to_string(x->bwt.sigma));
+    if (int drc = on_handle_device(x)) return drc;
+    *out = x;
+    return 0;
+}
+int fmgpu_search_scheme_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* scheme,
+                           uint64_t max_hits_per_query, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
+    Index* x = nullptr;
+    if (int rc = q4_index(h, &x)) return rc;
+    if (!nq || !packed || !qoff) return api::fmgpu_search_scheme(h, packed, qoff, nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream);   // (the byte call's own answer)
+    UnpackedQueries u;
+    if (int rc = unpack_queries(packed, qoff, nq, (hipStream_t)stream, &u)) return rc;
+    return api::fmgpu_search_scheme(h, u.qbuf(), u.qoff(), nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream);
+}
+int fmgpu_search_ng21_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, const fmgpu_expanded_scheme* scheme,
+                         uint64_t max_hits_per_query, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
+    Index* x = nullptr;
+    if (int rc = q4_index(h, &x)) return rc;
+    if (!nq || !packed || !qoff) return api::fmgpu_search_ng21(h, packed, qoff, nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream);
+    UnpackedQueries u;
+    if (int rc = unpack_queries(packed, qoff, nq, (hipStream_t)stream, &u)) return rc;
+    return api::fmgpu_search_ng21(h, u.qbuf(), u.qoff(), nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream);
+}
+
 int fmgpu_search_backtracking(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint64_t max_errors,
                               fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
     Index* x = reinterpret_cast<Index*>(h);

@@ -54,6 +54,13 @@ __device__ __forceinline__ void add_counters(unsigned long long* __restrict__ ct
 // The query symbols are fetched as aligned 64-bit words one word ahead of use, so that the only load on the
 // dependent chain of an LF step is the occurrence-table entry; the second interval end re-uses the first end's
 // entry when both fall into the same 64-row block (the common case once the interval is short).
+// Where a kernel's query symbols come from: one byte per symbol (the form every entry point has taken so far), or the 4-bit packed form of include/fmgpu.h
+// (symbol i of the batch = nibble i & 1 of byte i >> 1, the even index in the low nibble; the `_q4` entry points).  QueryReader and QueryWindow::fill are
+// written once per source; the kernels on top of them (k_exact_a, k_exact_p) take the source as a template parameter and are otherwise the same code.
+struct ByteQueries {};
+struct NibbleQueries {};
+
+template <class Q = ByteQueries>
 struct QueryReader {
     const uint64_t* base;   // 8-byte aligned
     uint64_t pos;           // absolute byte position (relative to base) of the next symbol to hand out (moving down)
@@ -72,6 +79,32 @@ struct QueryReader {
             uint64_t w = pos >> 3;
             cw = nw;
             nw = w >= 2 ? base[w - 2] : 0;
+        }
+        --pos;
+        return c;
+    }
+};
+// the packed source: 16 symbols per word.  The word ahead is fetched only while it still holds nibbles of the read (a neighbour's words are never loaded).
+template <>
+struct QueryReader<NibbleQueries> {
+    const uint64_t* base;   // 8-byte aligned
+    uint64_t pos, low;      // absolute nibble position (relative to base) of the next symbol to hand out (moving down); the word of the read's first symbol
+    uint64_t cw, nw;
+    __device__ __forceinline__ void init(const uint8_t* qbuf, uint64_t off, uint32_t m) {
+        uint64_t mis = (uint64_t)qbuf & 7ull;
+        base = reinterpret_cast<const uint64_t*>((uint64_t)qbuf - mis);
+        pos = off + 2ull * mis + m - 1;                // m >= 1
+        low = (off + 2ull * mis) >> 4;
+        uint64_t w = pos >> 4;
+        cw = base[w];
+        nw = w > low ? base[w - 1] : 0;
+    }
+    __device__ __forceinline__ uint32_t next() {
+        uint32_t c = (uint32_t)(cw >> ((pos & 15ull) * 4ull)) & 0xfu;
+        if ((pos & 15ull) == 0) {
+            uint64_t w = pos >> 4;
+            cw = nw;
+            nw = w >= low + 2 ? base[w - 2] : 0;
         }
         --pos;
         return c;
@@ -97,7 +130,9 @@ __device__ __forceinline__ uint32_t pack_nibbles8(uint64_t x, uint32_t sigma) {
 constexpr uint32_t kWindowWords = 16;
 struct QueryWindow {
     uint32_t w[kWindowWords];
+    template <class Q = ByteQueries>
     __device__ __forceinline__ void fill(const uint8_t* qbuf, uint64_t off, uint32_t m, uint32_t from, uint32_t sigma) {
+        if constexpr (std::is_same<Q, NibbleQueries>::value) { fill_nibbles(qbuf, off, m, from); return; }
         const bool any = from < m;
         const uint64_t first = (uint64_t)qbuf + off, last = first + (any ? m - 1u - from : 0u);    // the read's first byte; the byte consumed first
         const uint4* const top = reinterpret_cast<const uint4*>(last & ~(uint64_t)15);             // the 16-byte chunk of `last`
@@ -120,6 +155,36 @@ struct QueryWindow {
 #pragma unroll                                                       //  a select between neighbours became a per-lane index into a scratch array)
         for (uint32_t j = 0; j < 17u; ++j) r[j] = (p[j] & upper) | (p[j + 1u] & ~upper);
         const uint32_t sh = 4u * (7u - ((uint32_t)last & 7u));       // the bytes of r[0] above `last`
+#pragma unroll
+        for (uint32_t i = 0; i < kWindowWords; ++i) w[i] = __builtin_amdgcn_alignbit(r[i + 1u], r[i], sh);
+    }
+    // The same window from the packed form.  128 symbols lie in at most five aligned 16-byte chunks (32 nibbles each) whatever the alignment: five loads that stay inside the
+    // read's own chunks (chunk top - k, or the read's lowest one).  The packed form holds the symbols in ascending order, the window wants them descending: every word is
+    // nibble-reversed (byte swap + nibble swap) and the words are taken from the top down.  A nibble >= sigma is left as it is: a kernel treats it like 15.
+    __device__ __forceinline__ void fill_nibbles(const uint8_t* qbuf, uint64_t off, uint32_t m, uint32_t from) {
+        const bool any = from < m;
+        const uint64_t first = 2ull * (uint64_t)qbuf + off, last = first + (any ? m - 1u - from : 0u);   // absolute nibble addresses: the read's first symbol; the one consumed first
+        const uint4* const top = reinterpret_cast<const uint4*>((last >> 5) << 4);                   // the 16-byte chunk of `last`
+        const uint32_t span = (uint32_t)((last >> 5) - (first >> 5));                                // chunks below it that hold nibbles of the read
+        uint4 v[5];
+#pragma unroll
+        for (uint32_t k = 0; k < 5u; ++k) v[k] = make_uint4(0u, 0u, 0u, 0u);
+        if (any) {
+#pragma unroll
+            for (uint32_t k = 0; k < 5u; ++k) v[k] = *(top - min(k, span));
+        }
+        auto rev = [](uint32_t x) -> uint32_t { x = __builtin_bswap32(x); return ((x & 0x0f0f0f0fu) << 4) | ((x >> 4) & 0x0f0f0f0fu); };
+        uint32_t p[20];                                              // the words downwards from the top of chunk `top`, highest nibble first
+#pragma unroll
+        for (uint32_t k = 0; k < 5u; ++k) { p[4u * k] = rev(v[k].w); p[4u * k + 1u] = rev(v[k].z); p[4u * k + 2u] = rev(v[k].y); p[4u * k + 3u] = rev(v[k].x); }
+        const uint32_t skip = 31u - ((uint32_t)last & 31u);          // nibbles of the stream above `last`: skip >> 3 whole words (masks, not an index), the rest by the funnel shift
+        const uint32_t s1 = (skip & 8u) ? ~0u : 0u, s2 = (skip & 16u) ? ~0u : 0u;
+        uint32_t t[19], r[17];
+#pragma unroll
+        for (uint32_t j = 0; j < 19u; ++j) t[j] = (p[j + 1u] & s1) | (p[j] & ~s1);
+#pragma unroll
+        for (uint32_t j = 0; j < 17u; ++j) r[j] = (t[j + 2u] & s2) | (t[j] & ~s2);
+        const uint32_t sh = 4u * (skip & 7u);
 #pragma unroll
         for (uint32_t i = 0; i < kWindowWords; ++i) w[i] = __builtin_amdgcn_alignbit(r[i + 1u], r[i], sh);
     }

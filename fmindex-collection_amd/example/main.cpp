@@ -9,7 +9,9 @@
 //   * --algo: `ng21` (all four modes, main.cpp:176-185), `noerror` (:213-215), and `ng26` (search_ng26::search, Edit = true, over the
 //     un-expanded scheme with a uniform partition) are available; the other research variants are not part of this build;
 //   * --gen: backtracking, pigeon, pigeon_opt, h2-k1, h2-k2, h2-k3 (generator/all.h:35-96); `<name>_dyn` stretches the scheme to the read length by expandByWNC (Edit = true, sigma 4, 3e9 rows: main.cpp:116) instead of uniformly;
-//   * locating is one batched call over all rows of all cursors (the rows and their order are the reference's).
+//   * locating is one batched call over all rows of all cursors (the rows and their order are the reference's);
+//   * --packed (not in the reference): the reads are packed once, 4 bits per symbol, and searched in that form (the `_q4` entry points); the reverse
+//     complements are made on the device while packing (fmgpu_queries_pack4) instead of on the host.  The output is the same, byte for byte.
 #include "../../include/fmc_gpu.hpp"
 
 #include <algorithm>
@@ -40,7 +42,7 @@ struct Options {
     bool schemeDyn = false;
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false;
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -79,6 +81,7 @@ FlagRule const kFlags[] = {
     {"--no-reverse", false, [](Options& o, char const*) { o.withReverseComplement = false; }},
     {"--convertUnknownChar", false, [](Options& o, char const*) { o.unknownToA = true; }},
     {"--help", false, [](Options& o, char const*) { o.wantHelp = true; }},
+    {"--packed", false, [](Options& o, char const*) { o.packed = true; }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
     {"--ext", true, [](Options&, char const*) {}},
     {"--threads", true, [](Options&, char const*) {}},
@@ -231,7 +234,9 @@ struct Run {
         return config.schemeDyn ? fmc::search_scheme::expandByWNC<true>(scheme, len, 4, 3'000'000'000) : fmc::search_scheme::expand(scheme, len);
     }
 
-    std::vector<Hit> search(Algorithm kind, size_t k, std::vector<std::vector<uint8_t>> const& reads) const {
+    // Queries: the reads as Sequences, or as fmc::PackedQueries (--packed); firstLength = the length of read 0
+    template <typename Queries>
+    std::vector<Hit> search(Algorithm kind, size_t k, Queries const& reads, size_t firstLength) const {
         std::vector<Hit> hits;
         auto collect = [&](size_t read, auto const& cursor, size_t errors) { hits.push_back({read, cursor.lb, cursor.len, errors}); };
         size_t const perRead = config.hitsPerRead == 0 ? std::numeric_limits<size_t>::max() : config.hitsPerRead;
@@ -247,20 +252,20 @@ struct Run {
             break;
         case Algorithm::ng26: {
             if (config.hitMode == HitMode::all) fmc::search_ng26::search<true>(index, reads, schemeByName(config.schemeName, 0, k), {}, collect, perRead);
-            else fmc::search_ng26::search_best<true>(index, reads, schemesUpTo([&](size_t j) {
+            else fmc::search_ng26::search_best<true>(index, sequencesOf(reads), schemesUpTo([&](size_t j) {
                      return std::tuple<fmc::search_scheme::Scheme, std::vector<size_t>>{schemeByName(config.schemeName, j, j), {}}; }), collect, perRead);
             break;
         }
         case Algorithm::ng21: {
-            size_t const len = reads[0].size();
+            size_t const len = firstLength;
             if (config.hitMode == HitMode::all) {
                 auto const expanded = stretch(schemeByName(config.schemeName, 0, k), len);
                 if (config.hitsPerRead == 0) fmc::search_ng21::search(index, reads, expanded, collect);
                 else fmc::search_ng21::search_n(index, reads, expanded, config.hitsPerRead, collect);
             } else {
                 auto const ladder = schemesUpTo([&](size_t j) { return stretch(schemeByName(config.schemeName, j, j), len); });
-                if (config.hitsPerRead == 0) fmc::search_ng21::search_best(index, reads, ladder, collect);
-                else fmc::search_ng21::search_best_n(index, reads, ladder, config.hitsPerRead, collect);
+                if (config.hitsPerRead == 0) fmc::search_ng21::search_best(index, sequencesOf(reads), ladder, collect);
+                else fmc::search_ng21::search_best_n(index, sequencesOf(reads), ladder, config.hitsPerRead, collect);
             }
             break;
         }
@@ -281,9 +286,14 @@ struct Run {
         return placed;
     }
 
-    void oneErrorBudget(Algorithm kind, size_t k, std::vector<std::vector<uint8_t>> const& reads) const {
+    // (the best-hit modes pick reads out of the batch scheme by scheme: they take a packed batch back as Sequences)
+    static auto sequencesOf(std::vector<std::vector<uint8_t>> const& reads) -> std::vector<std::vector<uint8_t>> const& { return reads; }
+    static auto sequencesOf(fmc::PackedQueries const& reads) -> std::vector<std::vector<uint8_t>> { return reads.unpack(); }
+
+    template <typename Queries>
+    void oneErrorBudget(Algorithm kind, size_t k, Queries const& reads, size_t firstLength) const {
         StopWatch clock;
-        auto const hits = search(kind, k, reads);
+        auto const hits = search(kind, k, reads, firstLength);
         double const tSearch = clock.reset();
         auto const placed = locate(hits);
         double const tLocate = clock.reset();
@@ -324,24 +334,39 @@ int main(int argc, char const* const* argv) try {
                     "          --stepSize_k <int> (steps of errors)\\\n"
                     "          --no-reverse (don't use reverse compliment)\\\n"
                     "          --mode [all, besthits] (all: all hits with k errors (default), besthits: all hits with the lowest hit)\\\n"
+                    "          --packed (search the reads in the 4-bit packed form; reverse complements are made on the device)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }
     auto reads = readFasta(config.readsFasta, Sigma, config.unknownToA);
-    if (config.withReverseComplement) reads = withReverseComplements(reads);
+    // --packed: both strands come out of the device packer, unless reads get trimmed (the reference trims the doubled batch, and a trimmed reverse
+    // complement is not the reverse complement of the trimmed read: then the strands are made here and only packed)
+    bool const trims = config.trimTo != 0 && std::any_of(reads.begin(), reads.end(), [&](auto const& r) { return r.size() > config.trimTo; });
+    bool const strandsOnDevice = config.packed && config.withReverseComplement && !trims;
+    size_t const strands = strandsOnDevice ? 2 : 1;
+    if (config.withReverseComplement && !strandsOnDevice) reads = withReverseComplements(reads);
     if (!reads.empty()) {
-        std::printf("loaded %zu queries (incl reverse complements)\n", reads.size());
+        std::printf("loaded %zu queries (incl reverse complements)\n", strands * reads.size());
         std::printf("%-15s: %10s  (%10s +%10s ) %10s    - results: %10s/%10s/%10s/%10s - mem: %13s\n", "name", "time_search + time_locate", "time_search",
                     "time_locate", "(time_search+time_locate)/queries.size()", "resultCt", "results.size()", "uniqueResults.size()", "readIds.size()", "memory");
     }
     Run run{config, openIndex(config)};
-    if (config.readLimit != 0 && reads.size() > config.readLimit) reads.resize(config.readLimit);
+    size_t const limit = config.readLimit != 0 ? config.readLimit : std::numeric_limits<size_t>::max();     // (of the doubled batch)
+    if (strands * reads.size() > limit) reads.resize((limit + strands - 1) / strands);
     if (config.trimTo != 0) for (auto& r : reads) if (r.size() > config.trimTo) r.resize(config.trimTo);
+    fmc::PackedQueries packed;
+    if (config.packed) {
+        packed = strandsOnDevice ? fmc::PackedQueries::packOnDevice(reads, Sigma, {0, 4, 3, 2, 1}) : fmc::PackedQueries::pack(reads, Sigma);
+        if (packed.size() > limit) packed.qoff.resize(limit + 1);      // (an odd limit ends the batch on a forward read)
+    }
     for (auto const& algorithm : config.algorithms) {
         std::printf("using algorithm %s\n", algorithm.c_str());
         auto const kind = algorithmByName(algorithm);
         if (reads.empty()) continue;
-        for (size_t k = config.firstK; k <= config.lastK; k += config.stepK) run.oneErrorBudget(kind, k, reads);
+        for (size_t k = config.firstK; k <= config.lastK; k += config.stepK) {
+            if (config.packed) run.oneErrorBudget(kind, k, packed, reads[0].size());
+            else run.oneErrorBudget(kind, k, reads, reads[0].size());
+        }
     }
     return 0;
 } catch (std::exception const& e) {

@@ -559,7 +559,74 @@ std::vector<fmgpu_hit> run_hits(size_t nq, Call&& call) {
 }
 }  // namespace detail
 
+// A batch in the 4-bit packed query form (include/fmgpu.h): symbol i of the batch = nibble i & 1 of byte i >> 1, the even index in the low nibble; qoff as in the
+// byte form.  pack() is the host packer (the same bytes as fmgpu_queries_pack4): a symbol >= sigma becomes 15; with a complement table (sigma entries) every read is
+// followed by its reverse complement.  The search entry points below take it in place of a Sequences object and call the `_q4` entry points.
+struct PackedQueries {
+    std::vector<uint8_t> packed;
+    std::vector<uint64_t> qoff{0};
+    auto size() const -> size_t { return qoff.size() - 1; }
+    auto unpack() const -> std::vector<std::vector<uint8_t>> {       // the byte form: nibble 15 comes back as 255
+        std::vector<std::vector<uint8_t>> out(size());
+        for (size_t q = 0; q < size(); ++q)
+            for (uint64_t i = qoff[q]; i < qoff[q + 1]; ++i) {
+                uint8_t c = (packed[i >> 1] >> (4 * (i & 1))) & 15;
+                out[q].push_back(c == 15 ? 255 : c);
+            }
+        return out;
+    }
+    template <typename Seqs>
+    static auto pack(Seqs const& seqs, size_t sigma, std::vector<uint8_t> const& complement = {}) -> PackedQueries {
+        if (sigma < 2 || sigma > 15) throw std::runtime_error("fmindex-collection (gpu): 4-bit packed queries need 2 <= sigma <= 15");
+        if (!complement.empty() && complement.size() < sigma) throw std::runtime_error("fmindex-collection (gpu): the complement table needs sigma entries");
+        PackedQueries out;
+        uint64_t at = 0;
+        auto put = [&](size_t c) {
+            if ((at & 1) == 0) out.packed.push_back(static_cast<uint8_t>(c)); else out.packed.back() |= static_cast<uint8_t>(c << 4);
+            ++at;
+        };
+        for (auto const& q : seqs) {
+            for (auto c : q) put(static_cast<size_t>(c) < sigma ? static_cast<size_t>(c) : 15);
+            out.qoff.push_back(at);
+            if (complement.empty()) continue;
+            for (auto it = q.rbegin(); it != q.rend(); ++it) {
+                size_t c = static_cast<size_t>(*it) < sigma ? complement[static_cast<size_t>(*it)] : 15;
+                put(c < sigma ? c : 15);
+            }
+            out.qoff.push_back(at);
+        }
+        return out;
+    }
+    // the same batch made by fmgpu_queries_pack4: the reads go to the device as bytes once, the packing and the second strand happen there
+    template <typename Seqs>
+    static auto packOnDevice(Seqs const& seqs, size_t sigma, std::vector<uint8_t> const& complement = {}) -> PackedQueries {
+        if (!complement.empty() && complement.size() < sigma) throw std::runtime_error("fmindex-collection (gpu): the complement table needs sigma entries");
+        std::vector<uint8_t> buf; std::vector<uint64_t> off;
+        detail::flatten(seqs, buf, off);
+        size_t const nq = off.size() - 1, strands = complement.empty() ? 1 : 2;
+        PackedQueries out;
+        out.qoff.assign(strands * nq + 1, 0);
+        out.packed.assign((strands * off.back() + 1) / 2, 0);
+        detail::check(fmgpu_queries_pack4(buf.data(), off.data(), nq, static_cast<int32_t>(sigma), complement.empty() ? nullptr : complement.data(),
+                                          out.packed.data(), out.qoff.data(), nullptr));
+        return out;
+    }
+};
+
 namespace search_no_errors {
+template <typename Index, typename Delegate>
+void search(Index const& index, PackedQueries const& queries, Delegate&& delegate) {
+    size_t nq = queries.size();
+    std::vector<uint64_t> lb(nq), len(nq);
+    detail::check(fmgpu_search_exact_q4(index.handle, queries.packed.data(), queries.qoff.data(), nq, lb.data(), len.data(), nullptr, nullptr));
+    using cursor_t = select_cursor_t<Index>;
+    for (size_t q = 0; q < nq; ++q) {
+        if (len[q] == 0) continue;
+        cursor_t cur{};
+        cur.index = &index; cur.lb = lb[q]; cur.len = len[q];
+        delegate(q, cur);
+    }
+}
 // search(index, queries, delegate(qidx, cursor)) — search/SearchNoErrors.h:28-86; only non-empty cursors are reported
 template <typename Index, typename Queries, typename Delegate>
 void search(Index const& index, Queries const& queries, Delegate&& delegate, size_t /*BatchSize*/ = 32) {
@@ -594,10 +661,10 @@ void search(Index const& index, Queries const& queries, size_t maxError, Delegat
 
 namespace search_ng26 {
 namespace detail2 {
-// one scheme over one batch; qmap (optional) renames the batch's query numbers
+// one scheme over one batch; qmap (optional) renames the batch's query numbers; q4: buf is the 4-bit packed form
 template <bool Edit, typename Index>
 std::vector<fmgpu_hit> run(Index const& index, std::vector<uint8_t> const& buf, std::vector<uint64_t> const& off, search_scheme::Scheme const& scheme,
-                           std::vector<size_t> const& partition, size_t n, std::vector<uint64_t> const* qmap) {
+                           std::vector<size_t> const& partition, size_t n, std::vector<uint64_t> const* qmap, bool q4 = false) {
     size_t nq = off.size() - 1;
     if (scheme.empty() || nq == 0 || n == 0) return {};
     size_t P = scheme[0].pi.size();
@@ -609,7 +676,7 @@ std::vector<fmgpu_hit> run(Index const& index, std::vector<uint8_t> const& buf, 
     fmgpu_scheme sc{static_cast<int32_t>(scheme.size()), static_cast<int32_t>(P), pi.data(), l.data(), u.data(), part.empty() ? nullptr : part.data(),
                     Edit ? 1 : 0, 0};
     auto hits = detail::run_hits(nq, [&](fmgpu_hit* out, uint64_t cap, uint64_t* count) {
-        return fmgpu_search_scheme(index.handle, buf.data(), off.data(), nq, &sc, n, out, cap, count, nullptr, nullptr);
+        return (q4 ? fmgpu_search_scheme_q4 : fmgpu_search_scheme)(index.handle, buf.data(), off.data(), nq, &sc, n, out, cap, count, nullptr, nullptr);
     });
     if (qmap) for (auto& h : hits) h.qidx = (*qmap)[h.qidx];
     return hits;
@@ -624,6 +691,12 @@ void search(Index const& index, Queries const& queries, search_scheme::Scheme co
     std::vector<uint8_t> buf; std::vector<uint64_t> off;
     detail::flatten(queries, buf, off);
     auto hits = detail2::run<Edit>(index, buf, off, scheme, partition, n, nullptr);
+    detail::report(index, hits, delegate);
+}
+template <bool Edit = true, typename Index, typename Delegate>
+void search(Index const& index, PackedQueries const& queries, search_scheme::Scheme const& scheme, std::vector<size_t> const& partition,
+            Delegate&& delegate, size_t n = std::numeric_limits<size_t>::max()) {
+    auto hits = detail2::run<Edit>(index, queries.packed, queries.qoff, scheme, partition, n, nullptr, true);
     detail::report(index, hits, delegate);
 }
 // search<Edit>(index, queries, maxErrors, delegate, n) — search/SearchNg26.h:436-444: per query length the cached scheme
@@ -644,6 +717,16 @@ void search(Index const& index, Queries const& queries, size_t maxErrors, Delega
         all.insert(all.end(), hits.begin(), hits.end());
     }
     detail::report(index, all, delegate);
+}
+// the same for a packed batch: a batch of one length class (no read of length 2, or only such reads) goes down as it is, a mixed one is split in the byte form
+template <bool Edit = true, typename Index, typename Delegate>
+void search(Index const& index, PackedQueries const& queries, size_t maxErrors, Delegate&& delegate, size_t n = std::numeric_limits<size_t>::max()) {
+    size_t shortReads = 0;
+    for (size_t q = 0; q < queries.size(); ++q) shortReads += queries.qoff[q + 1] - queries.qoff[q] == 2;
+    if (shortReads != 0 && shortReads != queries.size()) { search<Edit>(index, queries.unpack(), maxErrors, std::forward<Delegate>(delegate), n); return; }
+    if (queries.size() == 0) return;
+    auto hits = detail2::run<Edit>(index, queries.packed, queries.qoff, search_scheme::generator::h2(maxErrors + (shortReads ? 1 : 2), 0, maxErrors), {}, n, nullptr, true);
+    detail::report(index, hits, delegate);
 }
 // search_best<Edit>(index, queries, {(scheme, partition), ...}, delegate, n) — search/SearchNg26.h:447-473: per query the first scheme
 // that reports anything wins
@@ -683,7 +766,7 @@ namespace search_ng21 {
 namespace detail2 {
 template <typename Index>
 std::vector<fmgpu_hit> run(Index const& index, std::vector<uint8_t> const& buf, std::vector<uint64_t> const& off, search_scheme::Scheme const& scheme,
-                           size_t n, std::vector<uint64_t> const* qmap) {
+                           size_t n, std::vector<uint64_t> const* qmap, bool q4 = false) {
     size_t nq = off.size() - 1;
     if (scheme.empty() || nq == 0) return {};                                         // :205
     size_t M = scheme[0].pi.size();
@@ -694,7 +777,7 @@ std::vector<fmgpu_hit> run(Index const& index, std::vector<uint8_t> const& buf, 
     }
     fmgpu_expanded_scheme sc{static_cast<int32_t>(scheme.size()), 0, M, pi.data(), l.data(), u.data()};
     auto hits = detail::run_hits(nq, [&](fmgpu_hit* out, uint64_t cap, uint64_t* count) {
-        return fmgpu_search_ng21(index.handle, buf.data(), off.data(), nq, &sc, n, out, cap, count, nullptr, nullptr);
+        return (q4 ? fmgpu_search_ng21_q4 : fmgpu_search_ng21)(index.handle, buf.data(), off.data(), nq, &sc, n, out, cap, count, nullptr, nullptr);
     });
     if (qmap) for (auto& h : hits) h.qidx = (*qmap)[h.qidx];
     return hits;
@@ -734,6 +817,16 @@ void search_n(Index const& index, Queries const& queries, search_scheme::Scheme 
     std::vector<uint8_t> buf; std::vector<uint64_t> off;
     detail::flatten(queries, buf, off);
     auto hits = detail2::run(index, buf, off, scheme, n, nullptr);
+    detail::report(index, hits, delegate);
+}
+template <typename Index, typename Delegate>
+void search(Index const& index, PackedQueries const& queries, search_scheme::Scheme const& scheme, Delegate&& delegate) {
+    auto hits = detail2::run(index, queries.packed, queries.qoff, scheme, std::numeric_limits<size_t>::max(), nullptr, true);
+    detail::report(index, hits, delegate);
+}
+template <typename Index, typename Delegate>
+void search_n(Index const& index, PackedQueries const& queries, search_scheme::Scheme const& scheme, size_t n, Delegate&& delegate) {
+    auto hits = detail2::run(index, queries.packed, queries.qoff, scheme, n, nullptr, true);
     detail::report(index, hits, delegate);
 }
 // search_best(index, queries, search_schemes, delegate) — :242-264: per query the first scheme of the list that reports any row

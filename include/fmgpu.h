@@ -200,10 +200,11 @@ typedef enum fmgpu_option {
 #define FMGPU_SEL_NO_SHARING       (1 << 24)  /* no work sharing between the lanes of a wave */
 #define FMGPU_SEL_NO_EXACT_LUT     (1 << 25)  /* exact search does not start from the interval table in front of the pair table */
 #define FMGPU_SEL_NO_BOARD         (1 << 26)  /* no work sharing between the waves of a launch (the lanes of a wave still share) */
+#define FMGPU_SEL_UNPACK_QUERIES   (1 << 27)  /* every `_q4` call unpacks its batch into a byte scratch and runs the byte kernels, also where a kernel reads the packed form itself */
 #define FMGPU_SEL_LEAN_FORMAT_A    (1 << 29)  /* k_scheme_lean on the one-symbol blocks although dense DNA blocks exist */
 #define FMGPU_SEL_NO_LEAN          (1 << 30)  /* k_scheme_fast<PLAIN> instead of k_scheme_lean */
 #define FMGPU_SEL_ALL (FMGPU_SEL_GENERAL_DFS | FMGPU_SEL_NO_PREFIX_TABLE | FMGPU_SEL_NO_LF3 | FMGPU_SEL_NO_LF_GENERAL | FMGPU_SEL_NO_WALK_TABLE | FMGPU_SEL_NO_LENGTH_BUCKETS | \
-                       FMGPU_SEL_EXACT_ON_TREE | FMGPU_SEL_EXACT_ONE_SYMBOL | FMGPU_SEL_LOCATE_PER_LANE | FMGPU_SEL_NO_SHARING | FMGPU_SEL_NO_EXACT_LUT | FMGPU_SEL_NO_BOARD | FMGPU_SEL_LEAN_FORMAT_A | FMGPU_SEL_NO_LEAN)
+                       FMGPU_SEL_EXACT_ON_TREE | FMGPU_SEL_EXACT_ONE_SYMBOL | FMGPU_SEL_LOCATE_PER_LANE | FMGPU_SEL_NO_SHARING | FMGPU_SEL_NO_EXACT_LUT | FMGPU_SEL_NO_BOARD | FMGPU_SEL_UNPACK_QUERIES | FMGPU_SEL_LEAN_FORMAT_A | FMGPU_SEL_NO_LEAN)
 int         fmgpu_set_option(int32_t option, int64_t value);
 int         fmgpu_get_option(int32_t option, int64_t* value);
 
@@ -331,6 +332,40 @@ int fmgpu_search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qof
  * intervals travel to the gathering rank ("only an RCCL gather of the resulting SA intervals") */
 int fmgpu_search_exact_packed(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
                               uint64_t* out_interval, fmgpu_stats* stats, void* stream);
+
+/* ---- 4-bit packed query batches ------------------------------------------------------------------------------------------------------
+ * The packed form of a batch holds one symbol per nibble instead of one per byte:
+ *   - symbol i of the batch (i = qoff[q] + j for symbol j of read q) is nibble i & 1 of byte i >> 1 of the packed buffer; the EVEN index is the LOW nibble;
+ *   - qoff is the array of the byte form: nq + 1 entries, counted in symbols, non-decreasing; qoff[0] need not be 0 and may be odd, so two reads may share a byte;
+ *   - nibble 15 means "not a symbol"; any nibble >= sigma behaves like a byte >= sigma does in the byte form;
+ *   - only indices with sigma <= 15 take packed queries (FMGPU_ERR_UNSUPPORTED otherwise, nothing written);
+ *   - a kernel loads only the aligned 16-byte chunks that hold nibbles of the read it serves; a host buffer is staged with half the bytes of the byte form.
+ * Calls that take this form end in `_q4` (fmgpu_search_exact_packed means packed OUTPUT and is not one of them).
+ *
+ * fmgpu_queries_pack4 packs a byte batch on the device; qbuf / qoff and out_packed / out_qoff may each be host or device memory.
+ *   - a byte >= sigma becomes 15; the output batch starts at symbol 0 (out_qoff[0] = 0, nq + 1 entries); it takes (out_qoff[last] + 1) / 2 bytes, and a
+ *     nibble left over in the last byte is 0;
+ *   - complement != NULL (sigma entries, host or device): the output holds 2 nq reads and out_qoff 2 nq + 1 entries.  Read 2q is read q; read 2q + 1 is read q
+ *     reversed, with complement[c] for c < sigma and 15 for the rest — a read followed by its reverse complement, the batch a both-strand search takes;
+ *   - sigma outside 2 .. 15: FMGPU_ERR_UNSUPPORTED; a null pointer while nq > 0: FMGPU_ERR_INVALID; nq == 0 returns 0.
+ * fmgpu_queries_unpack4 writes symbols qoff[0] .. qoff[nq] - 1 of a packed batch as bytes out_bytes[0 ..] (nibble 15 -> 255); the same errors. */
+int fmgpu_queries_pack4(const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, int32_t sigma, const uint8_t* complement,
+                        uint8_t* out_packed, uint64_t* out_qoff, void* stream);
+int fmgpu_queries_unpack4(const uint8_t* packed, const uint64_t* qoff, uint64_t nq, uint8_t* out_bytes, void* stream);
+
+/* fmgpu_search_exact / fmgpu_search_scheme / fmgpu_search_ng21 for a packed batch: every result (intervals and miss rows, hit records, out_count,
+ * stats.lf_steps / hits / table_*) is exactly what the byte call returns for fmgpu_queries_unpack4(packed).  Exact search on the pair table (with or without
+ * the interval table in front) and on the one-symbol blocks reads the packed form itself and stays asynchronous for device buffers; exact search behind k-step /
+ * walk tables, on symbol planes, the wavelet tree or reference blocks, and both scheme searches unpack the batch into a per-call byte scratch first, which is
+ * freed on return: those calls synchronise `stream`. */
+int fmgpu_search_exact_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq,
+                          uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats, void* stream);
+int fmgpu_search_scheme_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq,
+                           const fmgpu_scheme* scheme, uint64_t max_hits_per_query,
+                           fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream);
+int fmgpu_search_ng21_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq,
+                         const fmgpu_expanded_scheme* scheme, uint64_t max_hits_per_query,
+                         fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream);
 
 /* A profile of the same search: out_depth[q] = query symbols consumed until the cursor holds at most one row (0 rows included), or
  * length + 1 if it still holds several rows at the end.  (Tells how much of a batch the one-row walk tables can serve; bench.py reports
