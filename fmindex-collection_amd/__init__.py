@@ -597,6 +597,26 @@ def _run_hits(call, capacity):
         return hits, st
 
 
+def _run_best(call, nq, n_schemes, capacity, want_stratum, want_stats):
+    """a best-stratum call into host records in callback order.  On FMGPU_ERR_CAPACITY the count is a lower bound of the total (the records up to the stratum
+    that overflowed): growing to max(count, 2 x capacity) ends within n_schemes rounds."""
+    capacity = capacity if capacity is not None else max(1024, 4 * nq)
+    stratum = np.full(max(nq, 1), 255, dtype=np.uint8)
+    stats = (capi.Stats * max(n_schemes, 1))()
+    while True:
+        out = np.zeros(max(capacity, 1), dtype=HIT_DTYPE)
+        cnt = C.c_uint64()
+        rc = call(out, capacity, cnt, stratum, stats)
+        if rc == capi.FMGPU_ERR_CAPACITY:
+            capacity = max(int(cnt.value), 2 * capacity)
+            continue
+        capi.check(rc)
+        hits = np.ascontiguousarray(out[: cnt.value])
+        capi.check(capi.lib().fmgpu_hits_sort(capi.ptr(hits), hits.size, None))     # all records of a read come from one stratum: the reference's callback order
+        res = (hits,) + ((stratum[:nq],) if want_stratum else ()) + (([stats[i] for i in range(n_schemes)],) if want_stats else ())
+        return res if len(res) > 1 else hits
+
+
 class search_backtracking:
     """search/Backtracking.h"""
 
@@ -728,34 +748,24 @@ class search_ng21:
         return search_ng21.search(index, queries, scheme, capacity, want_stats, n)
 
     @staticmethod
-    def search_best(index, queries, schemes, n=UINT64_MAX):
-        """search_ng21::search_best (:242-264): per query the first scheme of the list that reports any row"""
+    def search_best(index, queries, schemes, n=UINT64_MAX, capacity=None, want_stratum=False, want_stats=False):
+        """search_ng21::search_best (:242-264): per query the first scheme of the list that reports any row — one fmgpu_search_best_ng21 call: the ladder is cut on
+        the device, so `queries` may be DeviceBuffers or a PackedQueries as they are.  want_stratum: also the uint8 array out_stratum (255 = no scheme found the
+        read); want_stats: also the list of the strata's Stats.  Returned as (hits[, stratum][, stats])."""
         qbuf, qoff, nq = _queries(queries)
-        if not isinstance(qoff, np.ndarray):
-            qoff = qoff.to_array(np.uint64, nq + 1) if isinstance(qoff, DeviceBuffer) else np.asarray(qoff)
-        if not isinstance(qbuf, np.ndarray):
-            qbuf = qbuf.to_array(np.uint8, int(qoff[-1]))
-        todo = np.arange(nq)
-        parts = []
-        for rank, sch in enumerate(schemes):
-            if todo.size == 0:
-                break
-            qb, qo = flatten([qbuf[int(qoff[i]): int(qoff[i + 1])] for i in todo])
-            hits = search_ng21.search(index, (qb, qo), sch, n=n).copy()
-            rows = np.bincount(hits["qidx"].astype(np.int64), weights=hits["len"].astype(np.float64), minlength=todo.size)
-            hits["qidx"] = todo.astype(np.uint64)[hits["qidx"].astype(np.int64)]
-            parts.append((rank, hits))
-            todo = todo[rows == 0]                                    # `if (ct > 0) break;` (:261)
-        if not parts:
-            return np.zeros(0, dtype=HIT_DTYPE)
-        hits = np.concatenate([h for _, h in parts])
-        order = np.concatenate([np.full(len(h), r) for r, h in parts])
-        return hits[np.lexsort((hits["seq"], order, hits["qidx"]))]
+        keep = [tuple(_u64(x) for x in sch) for sch in schemes]
+        arr = (capi.ExpandedScheme * max(len(keep), 1))()
+        for sc, (pi, l, u) in zip(arr, keep):
+            sc.n_searches, sc.length = (pi.shape if pi.ndim == 2 else (0, 0))
+            sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
+        call = _q4(queries, capi.lib().fmgpu_search_best_ng21, capi.lib().fmgpu_search_best_ng21_q4)
+        return _run_best(lambda out, c, cnt, stratum, st: call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, arr, len(keep), n, capi.ptr(out), c, C.byref(cnt),
+                                                               capi.ptr(stratum), st, None), nq, len(keep), capacity, want_stratum, want_stats)
 
     @staticmethod
-    def search_best_n(index, queries, schemes, n):
+    def search_best_n(index, queries, schemes, n, **kw):
         """search_ng21::search_best_n (:267-293)"""
-        return search_ng21.search_best(index, queries, schemes, n)
+        return search_ng21.search_best(index, queries, schemes, n, **kw)
 
 
 def _auto_scheme_search(index, queries, errors, n, edit, compat_auto_scheme):
@@ -805,11 +815,13 @@ def search_n(index, queries, errors, n, edit=True, compat_auto_scheme=False):
     return _auto_scheme_search(index, queries, errors, n, edit, compat_auto_scheme)
 
 
-def search_best(index, queries, max_errors, n=UINT64_MAX, edit=True, schemes=None):
+def search_best(index, queries, max_errors, n=UINT64_MAX, edit=True, schemes=None, capacity=None, want_stratum=False, want_stats=False):
     """search_ng26::search_best (search/SearchNg26.h:447-487).
     schemes=None: the convenience overload (:476-487) — the whole batch is searched with 0, 1, ... max_errors - 1 errors (the loop ends
-    BEFORE max_errors, as in the reference) and stops at the first error count for which ANY query reports a hit.
-    schemes=[(scheme, partition), ...]: the explicit overload (:447-473) — per query the first scheme that reports anything wins."""
+    BEFORE max_errors, as in the reference) and stops at the first error count for which ANY query reports a hit: a host loop, nothing is cut per read.
+    schemes=[(scheme, partition), ...]: the explicit overload (:447-473) — per query the first scheme that reports anything wins: one fmgpu_search_best call, the
+    ladder is cut on the device, so `queries` may be DeviceBuffers or a PackedQueries as they are.  want_stratum: also the uint8 array out_stratum (255 = no scheme
+    found the read); want_stats: also the list of the strata's Stats.  Returned as (hits[, stratum][, stats])."""
     if schemes is None:
         for k in range(int(max_errors)):
             hits = _auto_scheme_search(index, queries, k, n, edit, False)
@@ -817,25 +829,16 @@ def search_best(index, queries, max_errors, n=UINT64_MAX, edit=True, schemes=Non
                 return hits
         return np.zeros(0, dtype=HIT_DTYPE)
     qbuf, qoff, nq = _queries(queries)
-    if not isinstance(qoff, np.ndarray):
-        qoff = qoff.to_array(np.uint64, nq + 1) if isinstance(qoff, DeviceBuffer) else np.asarray(qoff)
-    if not isinstance(qbuf, np.ndarray):
-        qbuf = qbuf.to_array(np.uint8, int(qoff[-1]))
-    todo = np.arange(nq)
-    parts = []
-    for sch, part in schemes:
-        if todo.size == 0:
-            break
-        qb, qo = flatten([qbuf[int(qoff[i]): int(qoff[i + 1])] for i in todo])
-        hits = search_ng26.search(index, (qb, qo), sch, part, n, edit=edit).copy()
-        found = np.unique(hits["qidx"].astype(np.int64))
-        hits["qidx"] = todo.astype(np.uint64)[hits["qidx"].astype(np.int64)]
-        parts.append(hits)
-        todo = np.delete(todo, found)
-    if not parts:
-        return np.zeros(0, dtype=HIT_DTYPE)
-    hits = np.concatenate(parts)
-    return hits[np.lexsort((hits["seq"], hits["qidx"]))]
+    keep = [tuple(_u64(x) for x in sch) + ((_u64(part),) if part is not None else (None,)) for sch, part in schemes]
+    arr = (capi.Scheme * max(len(keep), 1))()
+    for sc, (pi, l, u, part) in zip(arr, keep):
+        sc.n_searches, sc.n_parts = pi.shape
+        sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
+        sc.partition = part.ctypes.data_as(capi.u64p) if part is not None else None
+        sc.edit = 1 if edit else 0
+    call = _q4(queries, capi.lib().fmgpu_search_best, capi.lib().fmgpu_search_best_q4)
+    return _run_best(lambda out, c, cnt, stratum, st: call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, arr, len(keep), n, capi.ptr(out), c, C.byref(cnt),
+                                                           capi.ptr(stratum), st, None), nq, len(keep), capacity, want_stratum, want_stats)
 
 
 class LocateLinear:

@@ -120,6 +120,7 @@ EXPORTS = [
     "fmgpu_set_option", "fmgpu_get_option", "fmgpu_index_formats", "fmgpu_index_clone", "fmgpu_replicas_peer_copies",
     "fmgpu_index_accelerate_extract", "fmgpu_sequence_lengths", "fmgpu_extract",
     "fmgpu_queries_pack4", "fmgpu_queries_unpack4", "fmgpu_search_exact_q4", "fmgpu_search_scheme_q4", "fmgpu_search_ng21_q4",
+    "fmgpu_search_best", "fmgpu_search_best_ng21", "fmgpu_search_best_q4", "fmgpu_search_best_ng21_q4",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -232,6 +233,12 @@ def lib():
     L.fmgpu_search_exact_q4.argtypes = L.fmgpu_search_exact.argtypes
     L.fmgpu_search_scheme_q4.argtypes = L.fmgpu_search_scheme.argtypes
     L.fmgpu_search_ng21_q4.argtypes = L.fmgpu_search_ng21.argtypes
+    L.fmgpu_search_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Scheme), C.c_int32, C.c_uint64,
+                                    C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(Stats), C.c_void_p]
+    L.fmgpu_search_best_ng21.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ExpandedScheme), C.c_int32, C.c_uint64,
+                                         C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(Stats), C.c_void_p]
+    L.fmgpu_search_best_q4.argtypes = L.fmgpu_search_best.argtypes
+    L.fmgpu_search_best_ng21_q4.argtypes = L.fmgpu_search_best_ng21.argtypes
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

@@ -159,6 +159,11 @@ static inline const IndexHeader* header_of(fmgpu_index_t h) {
         return hd_->wide ? fmgpu64::api::call : fmgpu32::api::call;                      \
     } while (0)
 
+namespace fmgpu {
+int check_scheme(fmgpu_index_t h, const fmgpu_scheme* scheme, uint64_t max_hits_per_query) { ROUTE(h, check_scheme(h, scheme, max_hits_per_query)); }
+int check_expanded_scheme(fmgpu_index_t h, const fmgpu_expanded_scheme* scheme) { ROUTE(h, check_expanded_scheme(h, scheme)); }
+}  // namespace fmgpu
+
 extern "C" {
 
 int fmgpu_abi_version(void) { return FMGPU_ABI_VERSION; }

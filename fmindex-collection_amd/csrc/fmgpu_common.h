@@ -192,6 +192,11 @@ struct UnpackedQueries {
 };
 int unpack_queries(const uint8_t* packed, const uint64_t* qoff, uint64_t nq, hipStream_t stream, UnpackedQueries* out);    // nq > 0, neither pointer null
 
+// The argument checks of fmgpu_search_scheme / fmgpu_search_ng21 alone, routed by the handle's row width (fmgpu_abi.hip): what the best-stratum calls
+// (fmgpu_best.hip) run over every scheme of a ladder before the first stratum starts.  The single-scheme calls' codes and messages.
+int check_scheme(fmgpu_index_t h, const fmgpu_scheme* scheme, uint64_t max_hits_per_query);
+int check_expanded_scheme(fmgpu_index_t h, const fmgpu_expanded_scheme* scheme);
+
 struct Built {   // host copies of construction by-products (fmgpu_build_index with keep_host)
     std::vector<std::vector<uint8_t>> part;
 };

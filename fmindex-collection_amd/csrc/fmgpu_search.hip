@@ -2691,6 +2691,41 @@ static void launch_lean(const Index* x, const uint32_t* d_steps, uint32_t S, uin
     if (board) launch(k_scheme_lean<kLeanWaves, kLeanSteps, false, false, true>); else launch(k_scheme_lean<kLeanWaves, kLeanSteps, false>);
 }
 
+// a caller's search_ng26 scheme checked and flattened into the kernels' form; `nothing`: the search reports nothing whatever the batch (SearchNg26.h:408-409)
+static int parse_scheme(const Index* x, const fmgpu_scheme* scheme, uint64_t max_hits, SchemeDev& sd, uint32_t& max_u, bool& nothing) {
+    nothing = false;
+    if (!x->bidirectional) return fail(FMGPU_ERR_INVALID, "search_ng26 needs a BiFMIndex (bwt_rev)");
+    if (!scheme || !scheme->pi || !scheme->l || !scheme->u) return fail(FMGPU_ERR_INVALID, "scheme is null");
+    if (scheme->n_searches < 0 || scheme->n_searches > kMaxSearches || scheme->n_parts < 1 || scheme->n_parts > kMaxParts)
+        return fail(FMGPU_ERR_UNSUPPORTED, "scheme larger than 16 searches x 16 parts");
+    if (max_hits == 0 || scheme->n_searches == 0) { nothing = true; return 0; }
+    sd.S = scheme->n_searches; sd.P = scheme->n_parts; sd.uniform = scheme->partition ? 0 : 1;
+    sd.dev_flags = kernel_flags();
+    sd.use_key = 0; sd.sharing = 0;                              // set by the launcher for the general Hamming kernel
+    for (int s = 0; s < sd.S; ++s) {
+        uint32_t seen = 0;
+        for (int p = 0; p < sd.P; ++p) {
+            uint64_t pi = scheme->pi[s * sd.P + p], l = scheme->l[s * sd.P + p], u = scheme->u[s * sd.P + p];
+            if (pi >= (uint64_t)sd.P || l > 255 || u > 254) return fail(FMGPU_ERR_INVALID, "scheme entry out of range");
+            seen |= 1u << pi; max_u = std::max<uint32_t>(max_u, (uint32_t)u);
+            sd.pi[s * kMaxParts + p] = (uint8_t)pi; sd.l[s * kMaxParts + p] = (uint8_t)l; sd.u[s * kMaxParts + p] = (uint8_t)u;
+        }
+        if (seen != (1u << sd.P) - 1u) return fail(FMGPU_ERR_INVALID, "scheme pi is not a permutation of the parts");
+        // connectivity (search_scheme/isValid.h:18-33): the kernel's cursor only grows at its two ends
+        uint32_t lo = sd.pi[s * kMaxParts], hi = lo;
+        for (int p = 1; p < sd.P; ++p) {
+            uint32_t v = sd.pi[s * kMaxParts + p];
+            if (v == hi + 1) hi = v; else if (v + 1 == lo) lo = v; else return fail(FMGPU_ERR_INVALID, "scheme pi is not contiguous");
+        }
+    }
+    if (scheme->partition) for (int p = 0; p < sd.P; ++p) {
+        if (scheme->partition[p] == 0 || scheme->partition[p] > 0xffffu) return fail(FMGPU_ERR_INVALID, "partition entries must be in [1, 65535]");
+        sd.partition[p] = (uint32_t)scheme->partition[p];
+        sd.psum += sd.partition[p];
+    }
+    return 0;
+}
+
 static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* scheme,
                    uint64_t max_hits, uint32_t K, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, hipStream_t stream) {
     if (stats) *stats = fmgpu_stats{};
@@ -2701,36 +2736,10 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
     bool edit = false;
     uint32_t max_u = 0;
     if (scheme_mode) {
-        if (!x->bidirectional) return fail(FMGPU_ERR_INVALID, "search_ng26 needs a BiFMIndex (bwt_rev)");
-        if (!scheme || !scheme->pi || !scheme->l || !scheme->u) return fail(FMGPU_ERR_INVALID, "scheme is null");
-        if (scheme->n_searches < 0 || scheme->n_searches > kMaxSearches || scheme->n_parts < 1 || scheme->n_parts > kMaxParts)
-            return fail(FMGPU_ERR_UNSUPPORTED, "scheme larger than 16 searches x 16 parts");
-        if (max_hits == 0 || scheme->n_searches == 0) return 0;                       // SearchNg26.h:408-409
-        sd.S = scheme->n_searches; sd.P = scheme->n_parts; sd.uniform = scheme->partition ? 0 : 1;
+        bool nothing = false;
+        if (int prc = parse_scheme(x, scheme, max_hits, sd, max_u, nothing)) return prc;
+        if (nothing) return 0;
         edit = scheme->edit != 0;
-        sd.dev_flags = kernel_flags();
-        sd.use_key = 0; sd.sharing = 0;                              // set below for the general Hamming kernel
-        for (int s = 0; s < sd.S; ++s) {
-            uint32_t seen = 0;
-            for (int p = 0; p < sd.P; ++p) {
-                uint64_t pi = scheme->pi[s * sd.P + p], l = scheme->l[s * sd.P + p], u = scheme->u[s * sd.P + p];
-                if (pi >= (uint64_t)sd.P || l > 255 || u > 254) return fail(FMGPU_ERR_INVALID, "scheme entry out of range");
-                seen |= 1u << pi; max_u = std::max<uint32_t>(max_u, (uint32_t)u);
-                sd.pi[s * kMaxParts + p] = (uint8_t)pi; sd.l[s * kMaxParts + p] = (uint8_t)l; sd.u[s * kMaxParts + p] = (uint8_t)u;
-            }
-            if (seen != (1u << sd.P) - 1u) return fail(FMGPU_ERR_INVALID, "scheme pi is not a permutation of the parts");
-            // connectivity (search_scheme/isValid.h:18-33): the kernel's cursor only grows at its two ends
-            uint32_t lo = sd.pi[s * kMaxParts], hi = lo;
-            for (int p = 1; p < sd.P; ++p) {
-                uint32_t v = sd.pi[s * kMaxParts + p];
-                if (v == hi + 1) hi = v; else if (v + 1 == lo) lo = v; else return fail(FMGPU_ERR_INVALID, "scheme pi is not contiguous");
-            }
-        }
-        if (scheme->partition) for (int p = 0; p < sd.P; ++p) {
-            if (scheme->partition[p] == 0 || scheme->partition[p] > 0xffffu) return fail(FMGPU_ERR_INVALID, "partition entries must be in [1, 65535]");
-            sd.partition[p] = (uint32_t)scheme->partition[p];
-            sd.psum += sd.partition[p];
-        }
     }
     Staged soff, sbuf, sout;
     int rc;
@@ -3149,26 +3158,20 @@ int fmgpu_search_backtracking(fmgpu_index_t h, const uint8_t* qbuf, const uint64
     return run_dfs(x, false, qbuf, qoff, nq, nullptr, ~0ull, (uint32_t)max_errors, out, capacity, out_count, stats, (hipStream_t)stream);
 }
 
-int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_expanded_scheme* scheme,
-                      uint64_t max_hits_per_query, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream_) {
-    Index* x = reinterpret_cast<Index*>(h);
-    if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
-    if (int drc = on_handle_device(x)) return drc;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (stats) *stats = fmgpu_stats{};
-    if (out_count) *out_count = 0;
+// a caller's expanded scheme checked (what does not depend on its arrays first: an empty scheme or batch ends the call between the two) and turned into the kernel's step table
+static int check_expanded_head(const Index* x, const fmgpu_expanded_scheme* scheme) {
     if (!x->bidirectional) return fail(FMGPU_ERR_INVALID, "search_ng21 needs a BiFMIndex (bwt_rev)");
     if (!scheme) return fail(FMGPU_ERR_INVALID, "scheme is null");
     if (scheme->n_searches < 0 || scheme->n_searches > 4096) return fail(FMGPU_ERR_UNSUPPORTED, "more than 4096 searches");
-    if (nq == 0 || scheme->n_searches == 0) return 0;                                  // SearchNg21.h:205
-    if (!qbuf || !qoff || (!out && capacity) || !out_count) return fail(FMGPU_ERR_INVALID, "qbuf / qoff / out / out_count is null");
+    return 0;
+}
+static int parse_expanded(const Index* x, const fmgpu_expanded_scheme* scheme, std::vector<uint32_t>& tab, uint32_t& max_u) {
     if (!scheme->pi || !scheme->l || !scheme->u) return fail(FMGPU_ERR_INVALID, "scheme arrays are null");
     const uint64_t M = scheme->length;
     if (M == 0 || M > 0xfffeu) return fail(FMGPU_ERR_INVALID, "expanded scheme length must be in [1, 65534]");
     const uint32_t S = (uint32_t)scheme->n_searches;
     if ((uint64_t)S * M > (1ull << 24)) return fail(FMGPU_ERR_UNSUPPORTED, "expanded scheme with more than 2^24 entries");
-    std::vector<uint32_t> tab((size_t)S * M);
-    uint32_t max_u = 0;
+    tab.assign((size_t)S * M, 0u);
     for (uint32_t s = 0; s < S; ++s) {
         const uint64_t *pi = scheme->pi + (size_t)s * M, *l = scheme->l + (size_t)s * M, *u = scheme->u + (size_t)s * M;
         uint64_t lo = pi[0], hi = pi[0];
@@ -3189,6 +3192,46 @@ int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff
         for (uint64_t k = 0; ok && k < LL; ++k) ok = u[k] == 0 && l[k] == 0 && pi[k] == pi[0] + k;
         if (ok) tab[(size_t)s * M] |= 1u << 31;
     }
+    return 0;
+}
+
+// what the best-stratum calls (fmgpu_best.hip) ask before they run anything: would the single-scheme call accept this scheme on this handle?  The same codes and messages.
+int check_scheme(fmgpu_index_t h, const fmgpu_scheme* scheme, uint64_t max_hits_per_query) {
+    Index* x = reinterpret_cast<Index*>(h);
+    if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
+    if (int drc = on_handle_device(x)) return drc;
+    SchemeDev sd{};
+    uint32_t max_u = 0;
+    bool nothing = false;
+    return parse_scheme(x, scheme, max_hits_per_query, sd, max_u, nothing);
+}
+int check_expanded_scheme(fmgpu_index_t h, const fmgpu_expanded_scheme* scheme) {
+    Index* x = reinterpret_cast<Index*>(h);
+    if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
+    if (int drc = on_handle_device(x)) return drc;
+    if (int hrc = check_expanded_head(x, scheme)) return hrc;
+    if (scheme->n_searches == 0) return 0;
+    std::vector<uint32_t> tab;
+    uint32_t max_u = 0;
+    return parse_expanded(x, scheme, tab, max_u);
+}
+
+int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_expanded_scheme* scheme,
+                      uint64_t max_hits_per_query, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream_) {
+    Index* x = reinterpret_cast<Index*>(h);
+    if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
+    if (int drc = on_handle_device(x)) return drc;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (stats) *stats = fmgpu_stats{};
+    if (out_count) *out_count = 0;
+    if (int hrc = check_expanded_head(x, scheme)) return hrc;
+    if (nq == 0 || scheme->n_searches == 0) return 0;                                  // SearchNg21.h:205
+    if (!qbuf || !qoff || (!out && capacity) || !out_count) return fail(FMGPU_ERR_INVALID, "qbuf / qoff / out / out_count is null");
+    std::vector<uint32_t> tab;
+    uint32_t max_u = 0;
+    if (int prc = parse_expanded(x, scheme, tab, max_u)) return prc;
+    const uint64_t M = scheme->length;
+    const uint32_t S = (uint32_t)scheme->n_searches;
     Staged soff, sbuf, sout;
     int rc;
     if ((rc = soff.in(qoff, (nq + 1) * 8, stream))) return rc;

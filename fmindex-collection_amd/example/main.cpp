@@ -252,7 +252,7 @@ struct Run {
             break;
         case Algorithm::ng26: {
             if (config.hitMode == HitMode::all) fmc::search_ng26::search<true>(index, reads, schemeByName(config.schemeName, 0, k), {}, collect, perRead);
-            else fmc::search_ng26::search_best<true>(index, sequencesOf(reads), schemesUpTo([&](size_t j) {
+            else fmc::search_ng26::search_best<true>(index, reads, schemesUpTo([&](size_t j) {
                      return std::tuple<fmc::search_scheme::Scheme, std::vector<size_t>>{schemeByName(config.schemeName, j, j), {}}; }), collect, perRead);
             break;
         }
@@ -264,8 +264,8 @@ struct Run {
                 else fmc::search_ng21::search_n(index, reads, expanded, config.hitsPerRead, collect);
             } else {
                 auto const ladder = schemesUpTo([&](size_t j) { return stretch(schemeByName(config.schemeName, j, j), len); });
-                if (config.hitsPerRead == 0) fmc::search_ng21::search_best(index, sequencesOf(reads), ladder, collect);
-                else fmc::search_ng21::search_best_n(index, sequencesOf(reads), ladder, config.hitsPerRead, collect);
+                if (config.hitsPerRead == 0) fmc::search_ng21::search_best(index, reads, ladder, collect);
+                else fmc::search_ng21::search_best_n(index, reads, ladder, config.hitsPerRead, collect);
             }
             break;
         }
@@ -285,10 +285,6 @@ struct Run {
         }
         return placed;
     }
-
-    // (the best-hit modes pick reads out of the batch scheme by scheme: they take a packed batch back as Sequences)
-    static auto sequencesOf(std::vector<std::vector<uint8_t>> const& reads) -> std::vector<std::vector<uint8_t>> const& { return reads; }
-    static auto sequencesOf(fmc::PackedQueries const& reads) -> std::vector<std::vector<uint8_t>> { return reads.unpack(); }
 
     template <typename Queries>
     void oneErrorBudget(Algorithm kind, size_t k, Queries const& reads, size_t firstLength) const {

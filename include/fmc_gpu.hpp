@@ -545,13 +545,15 @@ void report(Index const& index, std::vector<fmgpu_hit>& hits, Delegate&& delegat
         delegate(static_cast<size_t>(h.qidx), cur, static_cast<size_t>(h.errors));
     }
 }
+// lowerBound: the count a call reports with FMGPU_ERR_CAPACITY is a lower bound of the total (the best-stratum calls: the records up to the stratum that
+// overflowed) — growing to max(count, 2 x capacity) ends within as many rounds as the ladder has schemes
 template <typename Call>
-std::vector<fmgpu_hit> run_hits(size_t nq, Call&& call) {
+std::vector<fmgpu_hit> run_hits(size_t nq, Call&& call, bool lowerBound = false) {
     std::vector<fmgpu_hit> hits(std::max<size_t>(1024, 4 * nq));
     for (;;) {
         uint64_t count = 0;
         int rc = call(hits.data(), hits.size(), &count);
-        if (rc == FMGPU_ERR_CAPACITY) { hits.resize(count); continue; }
+        if (rc == FMGPU_ERR_CAPACITY) { hits.resize(lowerBound ? std::max<size_t>(count, 2 * hits.size()) : count); continue; }
         check(rc);
         hits.resize(count);
         return hits;
@@ -729,26 +731,50 @@ void search(Index const& index, PackedQueries const& queries, size_t maxErrors, 
     detail::report(index, hits, delegate);
 }
 // search_best<Edit>(index, queries, {(scheme, partition), ...}, delegate, n) — search/SearchNg26.h:447-473: per query the first scheme
-// that reports anything wins
+// that reports anything wins.  One fmgpu_search_best call: the ladder is cut per batch on the device (a scheme without a search finds nothing and is left out).
+namespace detail2 {
+template <bool Edit, typename Index>
+std::vector<fmgpu_hit> run_best(Index const& index, std::vector<uint8_t> const& buf, std::vector<uint64_t> const& off,
+                                std::vector<std::tuple<search_scheme::Scheme, std::vector<size_t>>> const& schemes, size_t n, bool q4 = false) {
+    size_t nq = off.size() - 1;
+    if (nq == 0 || n == 0) return {};
+    struct Flat { std::vector<uint64_t> pi, l, u, part; };
+    std::vector<Flat> flat;
+    flat.reserve(schemes.size());
+    std::vector<fmgpu_scheme> ladder;
+    for (auto const& [scheme, partition] : schemes) {
+        if (scheme.empty()) continue;
+        size_t P = scheme[0].pi.size();
+        flat.emplace_back();
+        auto& f = flat.back();
+        f.part.assign(partition.begin(), partition.end());
+        for (auto const& s : scheme) {
+            if (s.pi.size() != P) throw std::runtime_error("fmindex-collection (gpu): searches of a scheme must have the same number of parts");
+            f.pi.insert(f.pi.end(), s.pi.begin(), s.pi.end()); f.l.insert(f.l.end(), s.l.begin(), s.l.end()); f.u.insert(f.u.end(), s.u.begin(), s.u.end());
+        }
+        ladder.push_back(fmgpu_scheme{static_cast<int32_t>(scheme.size()), static_cast<int32_t>(P), f.pi.data(), f.l.data(), f.u.data(),
+                                      f.part.empty() ? nullptr : f.part.data(), Edit ? 1 : 0, 0});
+    }
+    if (ladder.empty()) return {};
+    return detail::run_hits(nq, [&](fmgpu_hit* out, uint64_t cap, uint64_t* count) {
+        return (q4 ? fmgpu_search_best_q4 : fmgpu_search_best)(index.handle, buf.data(), off.data(), nq, ladder.data(), static_cast<int32_t>(ladder.size()), n, out, cap, count,
+                                                               nullptr, nullptr, nullptr);
+    }, true);
+}
+}  // namespace detail2
 template <bool Edit = true, typename Index, typename Queries, typename Delegate>
 void search_best(Index const& index, Queries const& queries, std::vector<std::tuple<search_scheme::Scheme, std::vector<size_t>>> const& schemes,
                  Delegate&& delegate, size_t n = std::numeric_limits<size_t>::max()) {
-    std::vector<uint64_t> todo;
-    for (size_t i = 0; i < queries.size(); ++i) todo.push_back(i);
-    std::vector<fmgpu_hit> all;
-    for (auto const& [scheme, partition] : schemes) {
-        if (todo.empty()) break;
-        std::vector<uint8_t> buf; std::vector<uint64_t> off{0};
-        for (auto qi : todo) { auto const& q = queries[qi]; buf.insert(buf.end(), q.begin(), q.end()); off.push_back(buf.size()); }
-        auto hits = detail2::run<Edit>(index, buf, off, scheme, partition, n, &todo);
-        std::vector<uint8_t> found(queries.size(), 0);
-        for (auto const& h : hits) found[h.qidx] = 1;
-        all.insert(all.end(), hits.begin(), hits.end());
-        std::vector<uint64_t> rest;
-        for (auto qi : todo) if (!found[qi]) rest.push_back(qi);
-        todo.swap(rest);
-    }
-    detail::report(index, all, delegate);
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    auto hits = detail2::run_best<Edit>(index, buf, off, schemes, n);
+    detail::report(index, hits, delegate);
+}
+template <bool Edit = true, typename Index, typename Delegate>
+void search_best(Index const& index, PackedQueries const& queries, std::vector<std::tuple<search_scheme::Scheme, std::vector<size_t>>> const& schemes,
+                 Delegate&& delegate, size_t n = std::numeric_limits<size_t>::max()) {
+    auto hits = detail2::run_best<Edit>(index, queries.packed, queries.qoff, schemes, n, true);
+    detail::report(index, hits, delegate);
 }
 // search_best<Edit>(index, queries, maxErrors, delegate, n) — search/SearchNg26.h:476-487: the whole batch with 0, 1, ... maxErrors - 1
 // errors (the reference's loop ends before maxErrors), stopping at the first error count for which any query reports a hit
@@ -782,24 +808,34 @@ std::vector<fmgpu_hit> run(Index const& index, std::vector<uint8_t> const& buf, 
     if (qmap) for (auto& h : hits) h.qidx = (*qmap)[h.qidx];
     return hits;
 }
-template <typename Index, typename Queries, typename Delegate>
-void best(Index const& index, Queries const& queries, std::vector<search_scheme::Scheme> const& schemes, size_t n, Delegate&& delegate) {
-    std::vector<uint64_t> todo;
-    for (size_t i = 0; i < queries.size(); ++i) todo.push_back(i);
-    std::vector<fmgpu_hit> all;
+// search_best / search_best_n: one fmgpu_search_best_ng21 call, the ladder is cut per batch on the device (`if (ct > 0) break;` :261, :290 is its "found"; a scheme
+// without a search finds nothing and is left out)
+template <typename Index, typename Delegate>
+void best(Index const& index, std::vector<uint8_t> const& buf, std::vector<uint64_t> const& off, std::vector<search_scheme::Scheme> const& schemes, size_t n,
+          Delegate&& delegate, bool q4 = false) {
+    size_t nq = off.size() - 1;
+    struct Flat { std::vector<uint64_t> pi, l, u; };
+    std::vector<Flat> flat;
+    flat.reserve(schemes.size());
+    std::vector<fmgpu_expanded_scheme> ladder;
     for (auto const& scheme : schemes) {
-        if (todo.empty()) break;
-        std::vector<uint8_t> buf; std::vector<uint64_t> off{0};
-        for (auto qi : todo) { auto const& q = queries[qi]; buf.insert(buf.end(), q.begin(), q.end()); off.push_back(buf.size()); }
-        auto hits = run(index, buf, off, scheme, n, &todo);
-        std::vector<uint8_t> found(queries.size(), 0);
-        for (auto const& h : hits) if (h.len) found[h.qidx] = 1;                      // `if (ct > 0) break;` (:261, :290)
-        all.insert(all.end(), hits.begin(), hits.end());
-        std::vector<uint64_t> rest;
-        for (auto qi : todo) if (!found[qi]) rest.push_back(qi);
-        todo.swap(rest);
+        if (scheme.empty()) continue;
+        size_t M = scheme[0].pi.size();
+        flat.emplace_back();
+        auto& f = flat.back();
+        for (auto const& s : scheme) {
+            if (s.pi.size() != M || s.l.size() != M || s.u.size() != M) throw std::runtime_error("fmindex-collection (gpu): searches of an expanded scheme must have the same length");
+            f.pi.insert(f.pi.end(), s.pi.begin(), s.pi.end()); f.l.insert(f.l.end(), s.l.begin(), s.l.end()); f.u.insert(f.u.end(), s.u.begin(), s.u.end());
+        }
+        ladder.push_back(fmgpu_expanded_scheme{static_cast<int32_t>(scheme.size()), 0, M, f.pi.data(), f.l.data(), f.u.data()});
     }
-    detail::report(index, all, delegate);
+    std::vector<fmgpu_hit> hits;
+    if (nq != 0 && !ladder.empty())
+        hits = detail::run_hits(nq, [&](fmgpu_hit* out, uint64_t cap, uint64_t* count) {
+            return (q4 ? fmgpu_search_best_ng21_q4 : fmgpu_search_best_ng21)(index.handle, buf.data(), off.data(), nq, ladder.data(), static_cast<int32_t>(ladder.size()), n, out,
+                                                                             cap, count, nullptr, nullptr, nullptr);
+        }, true);
+    detail::report(index, hits, delegate);
 }
 }  // namespace detail2
 
@@ -832,12 +868,24 @@ void search_n(Index const& index, PackedQueries const& queries, search_scheme::S
 // search_best(index, queries, search_schemes, delegate) — :242-264: per query the first scheme of the list that reports any row
 template <typename Index, typename Queries, typename Delegate>
 void search_best(Index const& index, Queries const& queries, std::vector<search_scheme::Scheme> const& schemes, Delegate&& delegate) {
-    detail2::best(index, queries, schemes, std::numeric_limits<size_t>::max(), std::forward<Delegate>(delegate));
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    detail2::best(index, buf, off, schemes, std::numeric_limits<size_t>::max(), std::forward<Delegate>(delegate));
+}
+template <typename Index, typename Delegate>
+void search_best(Index const& index, PackedQueries const& queries, std::vector<search_scheme::Scheme> const& schemes, Delegate&& delegate) {
+    detail2::best(index, queries.packed, queries.qoff, schemes, std::numeric_limits<size_t>::max(), std::forward<Delegate>(delegate), true);
 }
 // search_best_n(index, queries, search_schemes, n, delegate) — :267-293
 template <typename Index, typename Queries, typename Delegate>
 void search_best_n(Index const& index, Queries const& queries, std::vector<search_scheme::Scheme> const& schemes, size_t n, Delegate&& delegate) {
-    detail2::best(index, queries, schemes, n, std::forward<Delegate>(delegate));
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    detail2::best(index, buf, off, schemes, n, std::forward<Delegate>(delegate));
+}
+template <typename Index, typename Delegate>
+void search_best_n(Index const& index, PackedQueries const& queries, std::vector<search_scheme::Scheme> const& schemes, size_t n, Delegate&& delegate) {
+    detail2::best(index, queries.packed, queries.qoff, schemes, n, std::forward<Delegate>(delegate), true);
 }
 }  // namespace search_ng21
 

@@ -391,10 +391,49 @@ int fmgpu_search_scheme(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
  * edit-distance search over an expanded scheme; BiFMIndex only.  max_hits_per_query = n (UINT64_MAX = search).  Queries shorter than
  * scheme->length (which the reference would read out of bounds) produce nothing; of longer ones the first `length` symbols' positions
  * pi[] are searched, as in the reference.  Records as for fmgpu_search_scheme; errors <= 127.  search_best / search_best_n
- * (:242-293) are host loops over this call (first scheme of a list with any hit), see the host mirrors. */
+ * (:242-293: first scheme of a list with any hit) are fmgpu_search_best_ng21 below. */
 int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
                       const fmgpu_expanded_scheme* scheme, uint64_t max_hits_per_query,
                       fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream);
+
+/* Best-stratum search: a ladder of schemes walked over one batch in one call — what search_ng26::search_best with an explicit scheme list
+ * (search/SearchNg26.h:447-469) and search_ng21::search_best / search_best_n (search/SearchNg21.h:242-293) cut per read, cut per batch on the device.
+ * Marking the found reads, selecting and compacting the others and renaming qidx are device passes; neither the queries nor the found set come back to the host
+ * between strata.  BiFMIndex only.
+ *   - Ladder and found: stratum i is exactly fmgpu_search_scheme / fmgpu_search_ng21 with schemes[i] (its own partition and edit) and max_hits_per_query, over the
+ *     reads still unfound, in batch order.  A read is found in stratum i if that stratum produced a record of it with len > 0; a found read takes no part in later
+ *     strata; the ladder ends early once no read is left.  A read no stratum can search (an empty read; for ng21 a read shorter than that scheme's length) stays unfound.
+ *   - Records: the records of stratum 0 come first, then stratum 1's, and so on (stats[i].hits gives the block sizes); inside a block the order is arbitrary, as for
+ *     the single-scheme calls.  Every field is what the single-scheme call emits except qidx, which is the read's number in the caller's batch.  All records of one
+ *     read come from one stratum: fmgpu_hits_sort on the output gives the reference's callback order, and fmgpu_locate_hits takes the output as it is.
+ *   - out_stratum (nq entries or NULL; host or device memory): out_stratum[q] = the stratum that found read q, 255 if none did.
+ *   - n_schemes: 0 .. 254, anything else returns FMGPU_ERR_INVALID.  n_schemes == 0 or nq == 0 returns 0 with *out_count = 0 and a non-NULL out_stratum all 255
+ *     (decided before the handle is looked at).
+ *   - stats (n_schemes entries or NULL): stats[i] = the stratum's own fmgpu_stats, all zero for a stratum that did not run; kernel_ms = that stratum's search kernel alone.
+ *   - Capacity: stratum i writes to out + produced and may use capacity - produced records.  If a stratum overflows, the call returns FMGPU_ERR_CAPACITY with
+ *     *out_count = the records produced up to and including that stratum — a lower bound of the total that always exceeds `capacity`; later strata do not run and the
+ *     contents of out and out_stratum are unspecified.  A retry loop that grows to max(*out_count, 2 x capacity) ends within n_schemes rounds.
+ *   - Errors: every scheme is checked before anything runs; codes and messages for a bad scheme, a unidirectional handle, null pointers (qbuf / qoff / out_count; out while
+ *     capacity > 0; schemes) and sigma > 15 for `_q4` are those of the single-scheme calls.  More than 2^31 - 1 reads: FMGPU_ERR_UNSUPPORTED.
+ *   - qbuf / qoff / out / out_stratum may each be host or device memory.  One 16-byte read-back per stratum (reads left, symbols left) sizes the next launch; the call
+ *     returns after completion and frees its scratch (25 bytes per read, and the symbols of the reads stratum 0 left) on return.
+ *   - `_q4`: `packed` in place of qbuf, the rules of the other `_q4` calls; the batch is unpacked once into a byte scratch and the ladder continues in bytes. */
+int fmgpu_search_best(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                      const fmgpu_scheme* schemes, int32_t n_schemes, uint64_t max_hits_per_query,
+                      fmgpu_hit* out, uint64_t capacity, uint64_t* out_count,
+                      uint8_t* out_stratum, fmgpu_stats* stats, void* stream);
+int fmgpu_search_best_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                           const fmgpu_expanded_scheme* schemes, int32_t n_schemes, uint64_t max_hits_per_query,
+                           fmgpu_hit* out, uint64_t capacity, uint64_t* out_count,
+                           uint8_t* out_stratum, fmgpu_stats* stats, void* stream);
+int fmgpu_search_best_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq,
+                         const fmgpu_scheme* schemes, int32_t n_schemes, uint64_t max_hits_per_query,
+                         fmgpu_hit* out, uint64_t capacity, uint64_t* out_count,
+                         uint8_t* out_stratum, fmgpu_stats* stats, void* stream);
+int fmgpu_search_best_ng21_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq,
+                              const fmgpu_expanded_scheme* schemes, int32_t n_schemes, uint64_t max_hits_per_query,
+                              fmgpu_hit* out, uint64_t capacity, uint64_t* out_count,
+                              uint8_t* out_stratum, fmgpu_stats* stats, void* stream);
 
 /* search_backtracking::search(index, queries, maxErrors, delegate) (search/Backtracking.h:85-89); FMIndex or BiFMIndex */
 int fmgpu_search_backtracking(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
