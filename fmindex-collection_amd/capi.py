@@ -125,17 +125,19 @@ EXPORTS = [
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
 OPTIONS = {"pair_table": 0, "dense_dna": 1, "symbol_planes": 2, "expand_dna": 3, "lf_table": 4, "fused_locate": 5, "heavy_first": 6,
-           "force_wide": 7, "kernel_select": 8, "fail_scratch": 9, "bucket_rows": 10, "suffix_sorter": 11}
+           "force_wide": 7, "kernel_select": 8, "fail_scratch": 9, "bucket_rows": 10, "suffix_sorter": 11, "sample_chain": 12}
 OPTION_DEFAULTS = {"pair_table": 1, "dense_dna": 1, "symbol_planes": 1, "expand_dna": 1, "lf_table": 1, "fused_locate": 1, "heavy_first": 1,
-                   "force_wide": 0, "kernel_select": 0, "fail_scratch": 0, "bucket_rows": 0, "suffix_sorter": 0}
+                   "force_wide": 0, "kernel_select": 0, "fail_scratch": 0, "bucket_rows": 0, "suffix_sorter": 0, "sample_chain": 1}
 # FMGPU_SEL_* bits of the kernel_select option
 SEL_GENERAL_DFS, SEL_NO_PREFIX_TABLE, SEL_NO_LF3, SEL_NO_LF_GENERAL, SEL_NO_WALK_TABLE, SEL_NO_LENGTH_BUCKETS = 2, 4, 8, 16, 32, 64
 SEL_EXACT_ON_TREE, SEL_EXACT_ONE_SYMBOL, SEL_LOCATE_PER_LANE, SEL_NO_SHARING, SEL_NO_EXACT_LUT, SEL_LEAN_FORMAT_A, SEL_NO_LEAN = 1 << 21, 1 << 22, 1 << 23, 1 << 24, 1 << 25, 1 << 29, 1 << 30
 SEL_NO_BOARD = 1 << 26
 SEL_UNPACK_QUERIES = 1 << 27
+SEL_NO_SAMPLE_CHAIN = 1 << 28
 # fmgpu_index_formats bits: what a handle holds beside (or as) the layout it was given
 FMT_BLOCKS, FMT_PAIRS, FMT_DENSE, FMT_PLANES, FMT_TREE, FMT_REFERENCE, FMT_LF, FMT_KSTEP, FMT_INTERVALS, FMT_WALK, FMT_PREFIX, FMT_LOCATE, FMT_FUSED = (1 << k for k in range(13))
 FMT_EXTRACT = 1 << 13
+FMT_CHAIN = 1 << 14
 
 _lib = None
 

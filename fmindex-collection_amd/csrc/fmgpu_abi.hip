@@ -66,14 +66,14 @@ Staged::~Staged() {
 bool want_wide(uint64_t n) { return n >= kNarrowLimit || opt_on(FMGPU_OPT_FORCE_WIDE); }
 
 // ---- library options (fmgpu_set_option): process-wide, read when a call starts / a handle is made
-static const int64_t kOptionDefaults[FMGPU_OPT_COUNT_] = {1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+static const int64_t kOptionDefaults[FMGPU_OPT_COUNT_] = {1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 1};
 static std::atomic<int64_t> g_options[FMGPU_OPT_COUNT_];
 static std::once_flag g_options_once;
 static void options_init() {
     for (int i = 0; i < FMGPU_OPT_COUNT_; ++i) g_options[i].store(kOptionDefaults[i], std::memory_order_relaxed);
 #ifdef FMGPU_DEV                                                     // (development builds only: the environment names the initial values)
     static const char* const names[FMGPU_OPT_COUNT_] = {"FMGPU_PAIRS", "FMGPU_DENSE_DNA", "FMGPU_FLAT", "FMGPU_SHADOW", "FMGPU_LF_TABLE", "FMGPU_FUSED_LOCATE", "FMGPU_HEAVY_FIRST",
-                                                        "FMGPU_FORCE_WIDE", "FMGPU_DEV_FLAGS", "FMGPU_FAIL_SCRATCH", "FMGPU_BUCKET_ROWS", "FMGPU_SUFFIX_SORTER"};
+                                                        "FMGPU_FORCE_WIDE", "FMGPU_DEV_FLAGS", "FMGPU_FAIL_SCRATCH", "FMGPU_BUCKET_ROWS", "FMGPU_SUFFIX_SORTER", "FMGPU_SAMPLE_CHAIN"};
     for (int i = 0; i < FMGPU_OPT_COUNT_; ++i) if (const char* e = getenv(names[i])) g_options[i].store(atoll(e), std::memory_order_relaxed);
 #endif
 }
@@ -96,7 +96,8 @@ static int set_opt(int option, int64_t value) {
 // tables) leaves nothing half-initialised behind, and the next call simply tries again.  Keyed by device: a host thread that alternates
 // between handles on two devices re-uses both sets.  FMGPU_OPT_FAIL_SCRATCH = k (test hook) fails the k-th allocation of the next creation.
 void CallScratch::drop() {
-    for (void* p : {(void*)ctr, (void*)sink, (void*)len2, frames, dfs_ctr, order, board}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)ctr, (void*)sink, (void*)len2, frames, dfs_ctr, order, board, exact_state}) if (p) (void)hipFree(p);
+    if (exact_state_ev) (void)hipEventDestroy(exact_state_ev);
     if (pinned) (void)hipHostFree(pinned);
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);

@@ -50,6 +50,15 @@
 //     bits: sigma <= 29).  LF(i, c) = flat_super[i >> B][c] + count[c] + popcount(rows of the line below i whose five plane bits spell c).  The multi-ary wavelet
 //     tree takes two lines per step and end for sigma = 28 (two levels); the super table (6.7 KB at 2 x 10^9 rows, 19 KB as 5-byte entries at 4.5 x 10^9) is staged in LDS.  2 bytes per row.
 //
+//  Format C  ("sample chain": the sampled rows of a sigma = 5 index with 32-bit rows in TEXT order, beside Format P — what exact search jumps along once a read is one row):
+//     chain[t] = { u32 row, u32 syms } for the t-th sampled row by global text coordinate (the (key, row) order of fmgpu_index_accelerate_extract): `row` is the sampled row,
+//     `syms` the `rate` text symbols in front of its position as 2-bit codes (symbol - 1), the symbol directly in front in the lowest bits — the order a backward search
+//     consumes them.  chain_of[k] = t for the k-th sampled row in ROW order (the rank the fused block, or sa_rank, gives).  A one-row cursor on sampled row chain[t].row whose
+//     next `rate` query symbols spell chain[t].syms moves to chain[t-1].row: `rate` LF steps for one 8-byte entry, adjacent entries for adjacent windows.  An entry is usable when
+//     `rate` LF steps from its row pass symbols 1..4 only and arrive at chain[t-1].row (the builder walks them: a handle made from reference arrays has no text); the others
+//     (the first sample of every sequence, windows with a delimiter) are listed (`chain_ex`, ascending t) behind a filter on t, as `pairs_ex` is.  `rate` is the common divisor
+//     of the sampled positions.  Built when rate <= 16 and at most 512 entries are unusable; 12 bytes per sample.
+//
 //  Format R  (reference layout as is — InterleavedEPR*, InterleavedEPRV2*): blocks + superBlocks copied verbatim.
 //
 //  Format W  (the reference's binary wavelet tree, one 64-byte line per 384 node bits; built from Wavelet::bitvector[*] at upload and only
@@ -225,6 +234,8 @@ struct CallScratch {
     hipStream_t dfs_streams[8] = {};                              // a ragged batch: the launches of its read lengths run side by side on these (made on first use)
     hipEvent_t dfs_events[9] = {};
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    void* exact_state = nullptr; size_t exact_state_bytes = 0;    // exact search along the sample chain: one word per read between its three kernels, grown on demand and kept between calls
+    hipEvent_t exact_state_ev = nullptr;                          // ... recorded behind the last kernel that used it: a call on another stream waits for it
     void drop();
 };
 int call_scratch(CallScratch** out);          // the calling thread's scratch for its current device (created on first use; all-or-nothing)
@@ -735,6 +746,10 @@ int build_dense_dna(DevString& s, hipStream_t stream);
 int fuse_presence_bits(Index* x, hipStream_t stream);
 // builds Format P beside the bwt of a sigma = 5 index with 32-bit rows (no-op where it does not apply; adds its bytes to device_bytes); defined in fmgpu_index.hip
 int build_pair_table(Index* x, hipStream_t stream);
+// builds Format C beside the pair table of a sigma = 5 index with 32-bit rows and a sampled suffix array (no-op where it does not apply; adds its bytes to device_bytes); drop: the reverse.
+// Defined in fmgpu_extract.hip (the builder of the sample table orders the samples)
+int build_sample_chain(Index* x, hipStream_t stream);
+void drop_sample_chain(Index* x);
 // sigma = 5 strings that arrived in another layout's own format (EPR / EPRV2 blocks read in place, the multi-ary wavelet tree) get the Format A expansion at once, so
 // that every search of the DNA path runs on the same kernels whatever layout the caller's index has (FMGPU_SHADOW=0: only on fmgpu_index_accelerate); adds nothing to
 // device_bytes itself; defined in fmgpu_index.hip
@@ -774,6 +789,9 @@ struct Index {
     // fmgpu_index_accelerate_extract (not saved, not cloned)
     ExtractTable ext;
     size_t device_bytes = 0;
+    // Format C (see the head of this file): the sampled rows in text order, their rank -> chain position map, the ascending list of unusable entries (`chain_nex` of 512, the rest all ones)
+    uint2* chain = nullptr; uint32_t* chain_of = nullptr; uint32_t* chain_ex = nullptr;
+    uint32_t chain_nex = 0, chain_rate = 0; uint64_t chain_n = 0; size_t chain_bytes = 0;
     // prefix table (fmgpu_index_accelerate_search): lut[code(w)] = { lb, lbRev, len, symbols consumed before the interval emptied (or L) }
     uint4* lut = nullptr; uint32_t lut_len = 0; uint64_t lut_entries = 0;
     Index() { hdr.wide = kWide ? 1 : 0; }

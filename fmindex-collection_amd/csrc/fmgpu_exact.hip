@@ -1,5 +1,6 @@
 // fmgpu_exact.hip — search_no_errors::search (search/SearchNoErrors.h:12-86), one query per lane:
 //  k_exact_p      two symbols per step on the pair lines (Format P), optionally behind an interval table
+//  k_exact_chain  one-row reads that k_exact_p parked: a seek to the next sampled row, then `rate` symbols per 8-byte entry along the sample chain (Format C); k_exact_p resumes them
 //  k_exact_a      one symbol per step on the one-symbol blocks (Format A)
 //  k_exact_s      one line per step on the symbol planes (Format S), optionally behind an interval table
 //  k_exact_m      the multi-ary wavelet tree (Format M)
@@ -143,12 +144,22 @@ __device__ __forceinline__ uint32_t pair_rank_lds(const lds_word* own, uint32_t 
 // entry of those symbols (one 8 / 16-byte load from a table of 4^lutL entries — 12 symbols: 134 MB, Infinity-Cache resident — instead of lutL / 2 pair steps whose two interval
 // ends lie in two lines each); an empty entry is walked from the start instead, so the miss row and the step count stay the one-symbol search's.
 // Q: the query source (ByteQueries, or NibbleQueries for fmgpu_search_exact_q4: the window is filled from the packed form, everything after the fill is the same).
-template <class Q>
+// MODE (the sample chain, 32-bit rows): 0 the whole search.  1 "park": a lane whose interval is one row while at least park_min symbols remain leaves the loop — its interval goes
+// to out_lb[q] (lb | len << 32), the symbols consumed | PARKED to state[q] — and a lane that ends writes its result as in mode 0 and FINISHED.  Once at most `hand` lanes of a wave
+// are left (the reads that take long to reach one row, or never do: 3 of 64 on the genome), the wave hands them over instead of riding on with 61 dummy lines per pass: interval and
+// symbols consumed | CONTINUE as above, the read's number appended to `list`.  3 "continue": one lane per entry of that list, dense again, from where the read stands; parks and ends as
+// in mode 1.  2 "resume": a lane whose state says RESUME (or still PARKED) starts from its interval and the symbols consumed, with the window filled there, and ends as any read
+// does; the others do and write nothing.  k_exact_chain runs between 3 and 2.
+constexpr uint32_t kStContinue = 0u, kStParked = 1u, kStResume = 2u, kStFinished = 3u, kStShift = 30u, kStDoneMask = (1u << kStShift) - 1u;
+template <class Q, int MODE = 0>
 __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __restrict__ pairs, const idx_t* __restrict__ ex, uint32_t nex, const idx_t* __restrict__ psuper,
                                                  const void* __restrict__ slut, uint32_t lutL,
                                                  const uint8_t* __restrict__ qbuf, const uint64_t* __restrict__ qoff,
                                                  uint64_t nq, idx_t n, uint64_t* __restrict__ out_lb, uint64_t* __restrict__ out_len,
-                                                 unsigned long long* __restrict__ steps_total) {
+                                                 unsigned long long* __restrict__ steps_total, uint32_t* __restrict__ state = nullptr, uint32_t park_min = 0u,
+                                                 uint32_t* __restrict__ list_count = nullptr, uint32_t* __restrict__ list = nullptr, uint32_t hand = 0u) {
+    uint32_t listed_reads = 0;
+    if constexpr (MODE == 3) { listed_reads = *list_count; if (blockIdx.x * 256u >= listed_reads) return; }     // (the launch is sized for the longest list there can be)
     extern __shared__ uint32_t s_coop[];                            // 4 waves x 8 regions
     __shared__ uint32_t s_filt[kPairFilterBits / 32u];
     __shared__ idx_t s_ex[512];
@@ -172,7 +183,8 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     lds_word* const wave_lds = (lds_word*)(s_coop + wave * 8u * (kCoopRegion / 4u));
     const lds_word* const own = wave_lds + (lane & 7u) * (kCoopRegion / 4u) + (lane >> 3) * 32u;
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (MODE == 3) q = q < listed_reads ? (uint64_t)list[q] : nq;
     uint32_t steps = 0, acc = 0, acc2 = 0, m = 0;
     uint64_t o = 0;
     idx_t lb = 0, len = n;
@@ -180,6 +192,14 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
         o = qoff[q];
         m = (uint32_t)(qoff[q + 1] - o);
     }
+    uint32_t from = 0;                                              // (mode 2: the symbols consumed before the resume)
+    bool parked = false, handed = false; uint32_t park_done = 0;    // (modes 1, 3; `done` itself goes on counting the wave's passes)
+    if constexpr (MODE == 2) {
+        const uint32_t st = q < nq ? state[q] : kStFinished << kStShift;
+        if ((st >> kStShift) == kStResume || (st >> kStShift) == kStParked) { const uint64_t w = out_lb[q]; lb = (idx_t)w; len = (idx_t)(w >> 32); from = st & kStDoneMask; }
+        else m = 0;                                                 // (finished before: nothing to do, nothing to write)
+    }
+    if constexpr (MODE == 3) if (q < nq) { const uint64_t w = out_lb[q]; lb = (idx_t)w; len = (idx_t)(w >> 32); from = state[q] & kStDoneMask; }
     // one symbol, as k_exact_a does it; false once the search is over
     auto single = [&](uint32_t c) -> bool {
         ++steps;
@@ -199,11 +219,14 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
         return len != 0;
     };
     bool alive = m != 0;
-    uint32_t done = 0, lut_steps = 0, acc3 = 0;                     // symbols of the read consumed so far; steps an interval-table entry stood for; such entries read
+    uint32_t done = from, lut_steps = 0, acc3 = 0;                  // symbols of the read consumed so far; steps an interval-table entry stood for; such entries read
     const idx_t C1 = occ.v.C[1], C2 = occ.v.C[2], C3 = occ.v.C[3], C4 = occ.v.C[4], C5 = occ.v.C[5];     // (wave-uniform: for the odd symbol)
     QueryWindow win;
-    win.template fill<Q>(qbuf, o, m, 0u, 5u);
+    win.template fill<Q>(qbuf, o, m, from, 5u);
     uint32_t d = 0, k = 0;                                          // the lane's next symbol: nibble 8 (k mod 4) + d of w[0]:w[1] (d = 1 after the odd symbol); k: passes since the fill
+    if constexpr (MODE >= 2) {
+        // (a read taken up again goes on in pairs from where it stands; a last single symbol is the loop's own rare path)
+    } else
     if (slut) {
         if (alive && m >= lutL && n > 1) {                          // (lutL <= 16: 4^lutL entries)
             const uint64_t first16 = (uint64_t)win.w[0] | ((uint64_t)win.w[1] << 32);
@@ -229,7 +252,16 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
     }
     for (;;) {                                                      // every lane of the wave takes its next two symbols (or is done)
         if (done >= m) alive = false;
-        if (!__ballot(alive)) break;
+        if constexpr (MODE == 1 || MODE == 3) if (alive && len == 1 && m - done >= park_min) { parked = true; park_done = done; alive = false; }
+        const uint64_t am = __ballot(alive);
+        if (!am) break;
+        if constexpr (MODE == 1) if ((uint32_t)__popcll(am) <= hand) {   // the few lanes left go on in a dense launch
+            uint32_t at = 0;
+            if (lane == (uint32_t)__ffsll((unsigned long long)am) - 1u) at = atomicAdd(list_count, (uint32_t)__popcll(am));
+            at = __shfl(at, __ffsll((unsigned long long)am) - 1, 64);
+            if (alive) { list[at + (uint32_t)__popcll(am & (((uint64_t)1 << lane) - 1u))] = (uint32_t)q; handed = true; park_done = done; alive = false; }
+            break;
+        }
         if (k == 63u) { win.template fill<Q>(qbuf, o, m, done, 5u); d = 0; k = 0; }     // (a read of more than 127 symbols: its next 128)
         const bool two = alive && done + 2u <= m;
         const uint32_t yx = __builtin_amdgcn_alignbit(win.w[1], win.w[0], 8u * (k & 3u) + 4u * d);
@@ -277,8 +309,121 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
             if (alive && two) alive = single(x);
         }
     }
-    if (q < nq) store_interval(out_lb, out_len, q, lb, len);
+    if constexpr (MODE == 0) { if (q < nq) store_interval(out_lb, out_len, q, lb, len); }
+    else if constexpr (MODE == 1 || MODE == 3) {
+        if (q < nq) {
+            if (parked || handed) { out_lb[q] = (uint64_t)lb | ((uint64_t)len << 32); state[q] = park_done | ((parked ? kStParked : kStContinue) << kStShift); }
+            else { store_interval(out_lb, out_len, q, lb, len); state[q] = kStFinished << kStShift; }
+        }
+    } else { if (m) store_interval(out_lb, out_len, q, lb, len); }
     add_counters(steps_total, steps, 12u * acc + 68u * acc2 + (uint32_t)kSlutEntryBytes * acc3, acc + acc2 + acc3, lut_steps);
+}
+
+// ---- one-row reads along the sample chain (Format C, fmgpu_common.h; 32-bit rows).  One lane per read; a lane whose read k_exact_p did not park leaves at once.
+//  seek   at most rate - 1 one-symbol steps on Format A until the row is a sampled one.  The 64-byte block of a step says whether the row is sampled (fused presence bits, else
+//         the presence bitvector), holds the entry of the read's next symbol and the rank of the sampled row; the four lanes of a quad fetch it together, straight into LDS, as
+//         k_locate_coop does (a lane that reads its own block with several loads runs at half the line rate).  A step that would empty the interval, a delimiter or a foreign
+//         byte is not taken: the lane hands over where it stands.
+//  jump   t = chain_of[rank]; while `rate` symbols remain, entry t is usable and its symbols are the read's next `rate`: row = chain[t - 1].row, one 8-byte load each.
+//  The lane never decides a miss and never writes a result: it writes its row and the symbols consumed | RESUME, and k_exact_p (mode 2) ends the read — a mismatch inside a
+//  window is found there, by the pair and single steps that give the reference's miss row and step count.  Jumped symbols count as steps and as table_steps.
+constexpr uint32_t kChainRegion = 1024u + 16u;       // bytes per region of a round (64 pieces + padding that spreads the owners' reads over the LDS banks)
+constexpr uint32_t kChainFilterBits = 32768;         // chain position mod this
+template <class Q>
+__global__ __launch_bounds__(256) void k_exact_chain(OccA<5> occ, ViewSA sa, const uint2* __restrict__ chain, const uint32_t* __restrict__ chain_of, const uint32_t* __restrict__ ex, uint32_t nex,
+                                                     uint32_t rate, const uint8_t* __restrict__ qbuf, const uint64_t* __restrict__ qoff, uint64_t nq,
+                                                     uint64_t* __restrict__ out_lb, uint32_t* __restrict__ state, unsigned long long* __restrict__ steps_total) {
+    extern __shared__ uint32_t s_blk[];                             // 4 waves x 4 regions
+    __shared__ uint32_t s_filt[kChainFilterBits / 32u];
+    __shared__ uint32_t s_ex[512];
+    for (uint32_t t = threadIdx.x; t < kChainFilterBits / 32u; t += 256u) s_filt[t] = 0u;
+    for (uint32_t t = threadIdx.x; t < 512u; t += 256u) s_ex[t] = t < nex ? ex[t] : 0xffffffffu;
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < 512u; t += 256u) {
+        const uint32_t r = s_ex[t];
+        if (r != 0xffffffffu) { const uint32_t bk = r & (kChainFilterBits - 1u); atomicOr(&s_filt[bk >> 5], 1u << (bk & 31u)); }
+    }
+    __syncthreads();
+    auto listed = [&](uint32_t t) -> bool {                         // entry t is unusable
+        const uint32_t bk = t & (kChainFilterBits - 1u);
+        if (!((s_filt[bk >> 5] >> (bk & 31u)) & 1u)) return false;
+        for (uint32_t i = 0; i < 512u && s_ex[i] <= t; ++i) if (s_ex[i] == t) return true;
+        return false;
+    };
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    lds_word* const wave_lds = (lds_word*)(s_blk + wave * 4u * (kChainRegion / 4u));
+    const lds_word* const own = wave_lds + (lane & 3u) * (kChainRegion / 4u) + (lane >> 2) * 16u;
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t row = 0, done = 0, m = 0, cur = 255u;                  // cur: the read's next symbol
+    bool seeking = false;
+    QueryReader<Q> qr;
+    if (q < nq) {
+        const uint32_t st = state[q];
+        if ((st >> kStShift) == kStParked) {
+            const uint64_t o = qoff[q];
+            m = (uint32_t)(qoff[q + 1] - o); done = st & kStDoneMask; row = (uint32_t)out_lb[q];
+            if (done < m) { seeking = true; qr.init(qbuf, o, m - done); cur = qr.next(); }
+        }
+    }
+    const bool mine = seeking;
+    bool found = false;
+    uint32_t rank = 0, walked = 0, steps = 0, tsteps = 0, acc = 0, acc4 = 0, acc8 = 0;
+    for (;;) {                                                      // wave-uniform: a lane that is not seeking rides along with block 0
+        if (!__ballot(seeking)) break;
+        const uint32_t blk = seeking ? row >> 6 : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t l = __shfl(blk, (int)((lane & ~3u) | k), 64);
+            const uint8_t* g = occ.v.blk + (size_t)l * 64u + (lane & 3u) * 16u;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)(wave_lds + k * (kChainRegion / 4u)), 16, 0, 0);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0f70);                         // vmcnt(0): the round's pieces are in LDS
+        asm volatile("" ::: "memory");
+        if (seeking) {
+            ++acc;
+            const uint32_t bit = row & 63u;
+            bool present;
+            if (occ.v.fused) present = ((((uint64_t)own[1] | ((uint64_t)own[2] << 32)) >> bit) & 1ull) != 0;
+            else present = sa_present(sa, (idx_t)row);
+            if (present) {                                          // sampled rows before this one: the block's own count + its presence bits, or the bitvector's rank
+                if (occ.v.fused) rank = own[15] + popc64(((uint64_t)own[1] | ((uint64_t)own[2] << 32)) & lowmask(bit));
+                else rank = (uint32_t)sa_rank(sa, (idx_t)row);
+                found = true; seeking = false;
+            } else if (walked + 1u >= rate || cur - 1u >= 4u) seeking = false;
+            else {
+                const uint64_t bits = (uint64_t)own[3u * cur + 1u] | ((uint64_t)own[3u * cur + 2u] << 32);
+                if (!((bits >> bit) & 1ull)) seeking = false;       // (the step would empty the interval: k_exact_p takes it)
+                else {
+                    row = own[3u * cur] + popc64(bits & lowmask(bit));
+                    ++done; ++steps; ++walked;
+                    cur = done < m ? qr.next() : 255u;
+                }
+            }
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);                         // lgkmcnt(0): the next round overwrites the regions
+        asm volatile("" ::: "memory");
+    }
+    if (found) {
+        uint32_t t = chain_of[rank];
+        uint2 e = chain[t];
+        ++acc4; ++acc8;
+        while (m - done >= rate && !listed(t)) {                    // (entry 0 has no predecessor: listed)
+            const uint2 p = chain[t - 1u];
+            ++acc8;
+            uint32_t code = 0; bool ok = true;
+            for (uint32_t j = 0; j < rate; ++j) {
+                const uint32_t c = j == 0u ? cur : qr.next();
+                ok = ok && c - 1u < 4u;
+                code |= ((c - 1u) & 3u) << (2u * j);
+            }
+            if (!ok || code != e.y) break;
+            row = p.x; e = p; --t;
+            done += rate; steps += rate; tsteps += rate;
+            cur = done < m ? qr.next() : 255u;
+        }
+    }
+    if (mine) { out_lb[q] = (uint64_t)row | (1ull << 32); state[q] = done | (kStResume << kStShift); }
+    add_counters(steps_total, steps, 64u * acc + 4u * acc4 + 8u * acc8, acc + acc4 + acc8, tsteps);
 }
 
 // ---- exact search on Format S (fmgpu_common.h): ONE 128-byte line per LF step and interval end where the multi-ary wavelet tree of sigma = 28 takes two —
@@ -662,6 +807,10 @@ __global__ __launch_bounds__(256) void k_exact_kstep(Occ occ, ExactAccel ac, uin
 namespace api {
 #include "fmgpu_api_decl.h"
 
+// a one-row read is parked for the sample chain while at least this many symbols remain (32 / 48 / 64 measured on the headline)
+constexpr uint32_t kParkMin = 32;
+// ... and a wave of the park launch hands its last lanes over to a dense launch once at most this many are left
+constexpr uint32_t kHandOver = 10;
 // the pair table with an interval table in front of it (and no other table): k_exact_p starts from the entry of the read's last symbols
 static bool exact_pair_lut(const Index* x) {
     return x->bwt.sigma == 5 && x->bwt.pairs && x->bwt.slut && !x->bwt.kblk && !x->bwt.walkj && x->bwt.search_family() == FAM_A &&
@@ -732,8 +881,51 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
         // k_exact_a runs best with 5 resident blocks per CU, not the 8 its 28 registers allow (measured on the 3.09 Gbp index, 10 M x 101 bp: 8 / 6 / 5 / 4 / 3
         // blocks = 19.53 / 19.23 / 18.92 / 19.10 / 18.95 ms — more waves only queue up at the memory system): 28 KB of unused dynamic LDS set the residency
         const size_t lds_a = dev_env("FMGPU_DEV_EXACT_LDS") ? dev_extra_lds : (size_t)28 * 1024;
+        // the sample chain (no table in front, a batch long enough to park): park -> continue -> jump -> resume, four launches under one timer
+        uint32_t park_min = kParkMin;
+        if (const char* ev = dev_env("FMGPU_DEV_EXACT_PARK_MIN")) park_min = std::max(16u, (uint32_t)atoi(ev));      // (dev knob; a parked read holds a whole window)
+        bool along_chain = !kWide && x->chain && x->bwt.sigma == 5 && x->bwt.pairs && !x->bwt.slut && !x->bwt.kblk && !x->bwt.walkj &&
+                           !(kernel_flags() & (FMGPU_SEL_EXACT_ONE_SYMBOL | FMGPU_SEL_NO_SAMPLE_CHAIN));
+        uint32_t hand = kHandOver;
+        if (const char* ev = dev_env("FMGPU_DEV_EXACT_HAND")) hand = std::min(16u, (uint32_t)atoi(ev));               // (dev knob; 0: waves ride on to their last lane)
+        const uint64_t nwaves = (nq + 63) / 64;
+        uint32_t* state = nullptr; uint32_t* list = nullptr;      // state: [nq] | the list's length (16 bytes) | the list: nwaves x 16 at most
+        CallScratch* sc = nullptr;
+        if (along_chain) {
+            if (!have_shape) { uint32_t mn = 0; if ((rc = query_len_range(qo, nq, stream, &shape_max, &mn))) return rc; timer.start(); }
+            along_chain = shape_max >= park_min + 16u && shape_max <= kStDoneMask;
+        }
+        if (along_chain) {
+            if ((rc = call_scratch(&sc))) return rc;
+            const size_t state_words = ((size_t)nq + 3) / 4 * 4;
+            const size_t need = (state_words + 4 + (size_t)nwaves * 16) * 4;
+            if (sc->exact_state_bytes < need) {
+                if (sc->exact_state) { (void)hipFree(sc->exact_state); sc->exact_state = nullptr; sc->exact_state_bytes = 0; }
+                const size_t want = need;
+                hipError_t e = hipMalloc(&sc->exact_state, want);
+                if (e != hipSuccess) { sc->exact_state = nullptr; (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? FMGPU_ERR_NOMEM : FMGPU_ERR_HIP, "hipMalloc(exact search state)"); }
+                sc->exact_state_bytes = want;
+                timer.start();
+            }
+            if (!sc->exact_state_ev) FM_HIP(hipEventCreateWithFlags(&sc->exact_state_ev, hipEventDisableTiming));
+            else FM_HIP(hipStreamWaitEvent(stream, sc->exact_state_ev, 0));      // (the thread's previous call may have run on another stream)
+            state = (uint32_t*)sc->exact_state; list = state + state_words;
+            FM_HIP(hipMemsetAsync(list, 0, 16, stream));
+        }
         auto launch = [&](auto src) {                            // the kernel of the byte form or of the 4-bit packed form
             using Q = decltype(src);
+            if constexpr (!kWide) if (along_chain) {
+                const size_t lds_p = 4 * 8 * kCoopRegion + dev_extra_lds;
+                k_exact_p<Q, 1><<<grid, block, lds_p, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super, nullptr, 0u, qb, qo, nq, n, ol, on, dsteps, state, park_min,
+                                                                list, list + 4, hand);
+                if (hand) k_exact_p<Q, 3><<<dim3((unsigned)((nwaves * hand + 255) / 256)), block, lds_p, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super, nullptr, 0u, qb, qo, nq, n,
+                                                                                                                ol, on, dsteps, state, park_min, list, list + 4, 0u);
+                if (!dev_env("FMGPU_DEV_EXACT_NO_JUMP"))            // (dev knob: park and resume alone — a parked read resumes where it stands)
+                k_exact_chain<Q><<<grid, block, 4 * 4 * kChainRegion, stream>>>(OccA<5>{x->bwt.va}, x->vsa, x->chain, x->chain_of, x->chain_ex, x->chain_nex, x->chain_rate, qb, qo, nq, ol, state, dsteps);
+                k_exact_p<Q, 2><<<grid, block, lds_p, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super, nullptr, 0u, qb, qo, nq, n, ol, on, dsteps, state, park_min);
+                (void)hipEventRecord(sc->exact_state_ev, stream);
+                return;
+            }
             if (x->bwt.sigma == 5 && x->bwt.pairs && !(kernel_flags() & (1 << 22)))
                 k_exact_p<Q><<<grid, block, 4 * 8 * kCoopRegion + dev_extra_lds, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super,
                                                                                            pair_lut ? (const void*)x->bwt.slut : nullptr, x->bwt.slut_len, qb, qo, nq, n, ol, on, dsteps);

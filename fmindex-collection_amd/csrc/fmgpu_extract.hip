@@ -1,5 +1,6 @@
 // fmgpu_extract.hip — text extraction from the index (the reference's reconstructText, utils.h:672-703, as parallel LF walks):
 //  fmgpu_index_accelerate_extract  the text map (per seqId: length, end row, global start) and the sampled rows in text order
+//  build_sample_chain              Format C (fmgpu_common.h) from that sample table: k_chain_fill walks `rate` LF steps back from every sampled row
 //  k_range_pieces                  per range: the sequence, the bounds check, the sampled positions inside it (two binary searches) -> piece count
 //  k_extract                       one piece per lane: an LF walk back from a sampled row (or the end row), symbols buffered into 8-byte stores
 // In global coordinates (start[s] + pos) a range [g0, g1) is cut at every sampled position inside (g0, g1); its last piece starts at the first sample at
@@ -67,6 +68,32 @@ __global__ __launch_bounds__(256) void k_sample_keys(ViewSA sa, uint64_t nwords,
 __global__ void k_iota_rows(uint64_t* __restrict__ out, uint64_t first, uint64_t count) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < count) out[t] = first + t;
+}
+
+// ------------------------------------------------------------------ Format C (fmgpu_common.h)
+constexpr uint32_t kChainMaxListed = 512;            // unusable entries: more than these and the chain is not built
+// entry t from the handle alone: `rate` LF steps back from the t-th sampled row in text order; usable if they pass symbols 1..4 only and arrive at the row of entry t - 1
+template <class Occ>
+__global__ __launch_bounds__(256) void k_chain_fill(Occ occ, ViewSA sa, const idx_t* __restrict__ srow, uint64_t nsamp, uint32_t rate, uint2* __restrict__ chain,
+                                                    uint32_t* __restrict__ chain_of, uint32_t* __restrict__ ex, uint32_t* __restrict__ nex) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nsamp) return;
+    const idx_t row = srow[t];
+    bool usable = t > 0;
+    uint32_t syms = 0;
+    if (usable) {
+        idx_t r = row;
+        for (uint32_t j = 0; j < rate; ++j) {
+            uint32_t c;
+            r = occ.lf_symbol(r, c);
+            if (c - 1u >= 4u) { usable = false; break; }
+            syms |= (c - 1u) << (2u * j);
+        }
+        if (usable && r != srow[t - 1u]) usable = false;
+    }
+    chain[t] = make_uint2((uint32_t)row, usable ? syms : 0u);
+    chain_of[sa_rank(sa, row)] = (uint32_t)t;
+    if (!usable) { const uint32_t k = atomicAdd(nex, 1u); if (k < kChainMaxListed) ex[k] = (uint32_t)t; }
 }
 
 // ------------------------------------------------------------------ extraction
@@ -331,4 +358,51 @@ int fmgpu_extract(fmgpu_index_t h, const fmgpu_text_range* ranges, uint64_t coun
 }
 
 }  // namespace api
+
+// ---- Format C: lifecycle (the builder of the sample table above orders the samples)
+void drop_sample_chain(Index* x) {
+    if (!x->chain) return;
+    (void)hipFree(x->chain); (void)hipFree(x->chain_of); (void)hipFree(x->chain_ex);
+    x->device_bytes -= x->chain_bytes;
+    x->chain = nullptr; x->chain_of = nullptr; x->chain_ex = nullptr; x->chain_nex = 0; x->chain_rate = 0; x->chain_n = 0; x->chain_bytes = 0;
+}
+int build_sample_chain(Index* x, hipStream_t stream) {
+    if constexpr (kWide) return 0;
+    DevString& s = x->bwt;
+    const uint64_t rate = x->has_sa ? x->vsa.div1 : 0;               // the sampled positions are the multiples of the rate: their common divisor
+    if (x->chain || !x->has_sa || s.sigma != 5 || !s.pairs || s.search_family() != FAM_A || s.va.bstride != 64u || rate < 1 || rate > 16 || !opt_on(FMGPU_OPT_SAMPLE_CHAIN)) return 0;
+    FM_HIP(hipStreamSynchronize(stream));
+    // the samples in text order: the extract table's (key, row) arrays — the handle's own, or a temporary
+    const bool temp = !x->ext.dev;
+    const fmgpu_index_t h = reinterpret_cast<fmgpu_index_t>(x);
+    if (temp) {
+        const int erc = api::fmgpu_index_accelerate_extract(h, 1);
+        if (erc == FMGPU_ERR_UNSUPPORTED || erc == FMGPU_ERR_INVALID) { set_error(""); return 0; }      // (no delimiter rows, samples outside the text map: no chain, and no message left behind)
+        if (erc) return erc;                                           // (out of memory, a HIP error: the caller's error)
+    }
+    struct Temp { fmgpu_index_t h; bool on; ~Temp() { if (on) (void)api::fmgpu_index_accelerate_extract(h, 0); } } guard{h, temp};
+    const uint64_t m = x->ext.nsamp;
+    if (m < 2 || m >= 0xffffffffull) return 0;
+    DBuf chain, of, ex, cnt; int rc;
+    if ((rc = chain.alloc(m * 8)) || (rc = of.alloc(m * 4)) || (rc = ex.alloc(kChainMaxListed * 4)) || (rc = cnt.alloc(8))) return rc;
+    FM_HIP(hipMemsetAsync(cnt.p, 0, 8, stream));
+    FM_HIP(hipMemsetAsync(ex.p, 0xff, kChainMaxListed * 4, stream));
+    FM_GRID(grid, m);
+    k_chain_fill<<<grid, dim3(256), 0, stream>>>(OccA<5>{s.va}, x->vsa, x->ext.row, m, (uint32_t)rate, chain.as<uint2>(), of.as<uint32_t>(), ex.as<uint32_t>(), cnt.as<uint32_t>());
+    FM_LAUNCHED("k_chain_fill");
+    uint32_t nex = 0;
+    FM_HIP(hipMemcpyAsync(&nex, cnt.p, 4, hipMemcpyDeviceToHost, stream));
+    FM_HIP(hipStreamSynchronize(stream));
+    if (nex > kChainMaxListed) return 0;                              // many sequences, or samples that are not `rate` apart: exact search stays on the pair table
+    std::vector<uint32_t> list(nex);
+    if (nex) FM_HIP(hipMemcpy(list.data(), ex.p, nex * 4, hipMemcpyDeviceToHost));
+    std::sort(list.begin(), list.end());
+    if (nex) FM_HIP(hipMemcpy(ex.p, list.data(), nex * 4, hipMemcpyHostToDevice));
+    x->chain_bytes = chain.bytes + of.bytes + ex.bytes;
+    x->chain = (uint2*)chain.take(); x->chain_of = (uint32_t*)of.take(); x->chain_ex = (uint32_t*)ex.take();
+    x->chain_nex = nex; x->chain_rate = (uint32_t)rate; x->chain_n = m;
+    x->device_bytes += x->chain_bytes;
+    return 0;
+}
+
 }  // namespace FMGPU_NS

@@ -417,6 +417,7 @@ static int index_assemble(const SavedIndex& m, Source& src, fmgpu_index_t* out) 
     }
     if ((rc = build_pair_table(x.get(), nullptr))) return bail(rc);       // ... and so are Formats P and S
     if ((rc = build_flat_table(x.get(), nullptr))) return bail(rc);
+    if ((rc = build_sample_chain(x.get(), nullptr))) return bail(rc);     // ... and Format C
     { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) return bail(hip_fail(e, "index load")); }     // (an asynchronous fault of a builder surfaces here: nothing is handed out)
     *out = reinterpret_cast<fmgpu_index_t>(x.release());
     return 0;

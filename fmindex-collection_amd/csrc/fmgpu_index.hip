@@ -945,6 +945,7 @@ int fmgpu_index_destroy(fmgpu_index_t h) {
     Index* x = reinterpret_cast<Index*>(h);
     if (!x) return 0;
     free_string(x->bwt); free_string(x->rev);
+    drop_sample_chain(x);
     for (void* p : {(void*)x->dC, x->sa_l0, x->sa_l1, x->sa_bits, x->sa_f0, x->sa_f1, (void*)x->lut, (void*)x->loc_tab, x->ext.dev}) if (p) (void)hipFree(p);
     x->hdr.magic = 0;
     delete x;
@@ -1019,6 +1020,7 @@ int fmgpu_index_create(const fmgpu_index_desc* desc, fmgpu_index_t* out) {
                         sa->field[0].bits, sa->field[1].bits, sa->field[0].common_divisor, sa->field[1].common_divisor};
         x->has_sa = true;
         rc = fuse_presence_bits(x.get(), nullptr); if (rc) return bail(rc);
+        rc = build_sample_chain(x.get(), nullptr); if (rc) return bail(rc);
     }
     *out = reinterpret_cast<fmgpu_index_t>(x.release());
     return 0;
@@ -1048,7 +1050,8 @@ static void drop_shadow(Index* x, DevString& t) {
     x->device_bytes -= t.shadow_bytes;
     t.shadow = nullptr; t.shadow_sup = nullptr; t.shadow_bytes = 0; t.shadow_sup_bytes = 0; t.va = ViewA{};
     if (t.pairs) { (void)hipFree(t.pairs); if (t.pairs_ex) (void)hipFree(t.pairs_ex); if (t.pairs_super) (void)hipFree(t.pairs_super);
-                   x->device_bytes -= t.pairs_bytes; t.pairs = nullptr; t.pairs_ex = nullptr; t.pairs_super = nullptr; t.pairs_bytes = 0; t.pairs_nex = 0; t.pairs_nsb = 0; }
+                   x->device_bytes -= t.pairs_bytes; t.pairs = nullptr; t.pairs_ex = nullptr; t.pairs_super = nullptr; t.pairs_bytes = 0; t.pairs_nex = 0; t.pairs_nsb = 0;
+                   if (&t == &x->bwt) drop_sample_chain(x); }
     if (t.dense) { (void)hipFree(t.dense); if (t.dense_ex) (void)hipFree(t.dense_ex);
                    x->device_bytes -= t.dense_bytes; t.dense = nullptr; t.dense_ex = nullptr; t.dense_bytes = 0; t.dense_nex = 0; }
 }
@@ -1060,7 +1063,8 @@ static int rebuild_derived(Index* x) {
         for (DevString* t : {&x->bwt, &x->rev}) { const size_t had = t->dense_bytes; if ((rc = build_dense_dna(*t, nullptr))) return rc; x->device_bytes += t->dense_bytes - had; }
         if (x->bwt.dense && !x->rev.dense) { (void)hipFree(x->bwt.dense); (void)hipFree(x->bwt.dense_ex); x->device_bytes -= x->bwt.dense_bytes; x->bwt.dense = nullptr; x->bwt.dense_ex = nullptr; x->bwt.dense_bytes = 0; x->bwt.dense_nex = 0; }
     }
-    return build_pair_table(x, nullptr);
+    if ((rc = build_pair_table(x, nullptr))) return rc;
+    return build_sample_chain(x, nullptr);
 }
 
 #if FMGPU_WIDE
@@ -1270,6 +1274,7 @@ int fmgpu_index_formats(fmgpu_index_t h, uint32_t* mask) {
     if (x->loc_tab) m |= FMGPU_FMT_LOCATE;
     if (s.va.fused) m |= FMGPU_FMT_FUSED;
     if (x->ext.dev) m |= FMGPU_FMT_EXTRACT;
+    if (x->chain) m |= FMGPU_FMT_CHAIN;
     *mask = m;
     return 0;
 }

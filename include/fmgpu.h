@@ -32,6 +32,8 @@
  *     or EPR / EPRV2 bwt with 6 <= sigma <= 29: a symbol-plane table (2 bytes per row; exact search takes one memory line per step and interval end instead of
  *     one per tree level); a sigma = 5 string handed over as InterleavedEPR* / InterleavedEPRV2* blocks or as a Wavelet: the one-symbol block table every
  *     other DNA layout is held in (1 byte per row), and with it the two tables above — every layout searches at the same speed.
+ *     A sigma = 5 index with 32-bit rows, the pair table and a sampled suffix array of rate <= 16 also gets a sample chain (12 bytes per sample: exact search moves a one-row read
+ *     `rate` symbols per entry along the sampled rows in text order; FMGPU_OPT_SAMPLE_CHAIN = 0 keeps it out).
  *     Results do not depend on them (fmgpu_set_option: FMGPU_OPT_PAIR_TABLE / _DENSE_DNA / _SYMBOL_PLANES / _EXPAND_DNA = 0 keep them out).
  *   - the library reads no environment variable: what used to be FMGPU_* switches are options set through fmgpu_set_option.
  */
@@ -159,14 +161,15 @@ typedef struct fmgpu_stats {
     /* what the dominant kernel actually asked of the memory system on the index tables, counted by the kernel itself (0 for kernels that do
      * not count): table_bytes = sum over issued table loads of the entry bytes consumed (a 12-byte block entry, an 8-byte walk entry, a
      * 64-byte block of an extend-all, a 16-byte frame ...), table_accesses = number of such accesses that can each touch a different
-     * memory line (two loads into the same 64-byte block count once).  Query and result traffic is coalesced and not included. */
+     * memory line (two loads into the same 64-byte block count once).  Query and result traffic is coalesced and not included.
+     * Exact search along the sample chain: 64 bytes per block of the seek (the whole block is fetched), 4 per rank -> position word, 8 per chain entry. */
     uint64_t table_bytes;
     uint64_t table_accesses;
-    uint64_t table_steps;    /* exact search from an interval table in front of the pair table: LF steps that the entries stood for (entries read x their symbols); else 0 */
+    uint64_t table_steps;    /* exact search from an interval table in front of the pair table, or along the sample chain: LF steps that the entries stood for (entries read x their symbols); else 0 */
 } fmgpu_stats;
 
 /* Library options: process-wide, read when a handle is created / a call starts (set them before, not during, the calls they concern).
- * The first seven and FMGPU_OPT_BUCKET_ROWS choose what a handle holds or how a batch / a construction is prepared — results never depend on them; FORCE_WIDE, KERNEL_SELECT and FAIL_SCRATCH are test hooks. */
+ * The first seven, FMGPU_OPT_BUCKET_ROWS and FMGPU_OPT_SAMPLE_CHAIN choose what a handle holds or how a batch / a construction is prepared — results never depend on them; FORCE_WIDE, KERNEL_SELECT and FAIL_SCRATCH are test hooks. */
 typedef enum fmgpu_option {
     FMGPU_OPT_PAIR_TABLE = 0,      /* 1 (default): a sigma = 5 bwt gets the symbol-pair table (exact search takes two symbols per step) */
     FMGPU_OPT_DENSE_DNA = 1,       /* 1: both strings of a sigma = 5 BiFMIndex with 32-bit rows get dense DNA blocks (equal-length k-mismatch kernel) */
@@ -185,7 +188,9 @@ typedef enum fmgpu_option {
                                     *    its first 12-21 symbols with another): prefix doubling on the ties, the suffix array itself is never held;
                                     * 3: bucket by bucket without any array of n entries (2 bytes per row + one bucket): ties are broken by reading further symbols, a text with
                                     *    very long exact repeats is refused (FMGPU_ERR_UNSUPPORTED) */
-    FMGPU_OPT_COUNT_ = 12
+    FMGPU_OPT_SAMPLE_CHAIN = 12,   /* 1 (default): a sigma = 5 index with 32-bit rows, the pair table and a sampled suffix array of rate <= 16 gets the sample chain (12 bytes per sample:
+                                    * exact search moves a one-row read `rate` symbols per 8-byte entry along the sampled rows in text order) */
+    FMGPU_OPT_COUNT_ = 13
 } fmgpu_option;
 /* bits of FMGPU_OPT_KERNEL_SELECT: each takes a call off the kernel the library would pick (the parity tests run every kernel through them) */
 #define FMGPU_SEL_GENERAL_DFS      (1 << 1)   /* search_ng26 / ng21: the general kernels (k_scheme, k_scheme_edit, k_ng21) */
@@ -201,10 +206,11 @@ typedef enum fmgpu_option {
 #define FMGPU_SEL_NO_EXACT_LUT     (1 << 25)  /* exact search does not start from the interval table in front of the pair table */
 #define FMGPU_SEL_NO_BOARD         (1 << 26)  /* no work sharing between the waves of a launch (the lanes of a wave still share) */
 #define FMGPU_SEL_UNPACK_QUERIES   (1 << 27)  /* every `_q4` call unpacks its batch into a byte scratch and runs the byte kernels, also where a kernel reads the packed form itself */
+#define FMGPU_SEL_NO_SAMPLE_CHAIN  (1 << 28)  /* exact search stays on the pair table for one-row reads although the sample chain exists */
 #define FMGPU_SEL_LEAN_FORMAT_A    (1 << 29)  /* k_scheme_lean on the one-symbol blocks although dense DNA blocks exist */
 #define FMGPU_SEL_NO_LEAN          (1 << 30)  /* k_scheme_fast<PLAIN> instead of k_scheme_lean */
 #define FMGPU_SEL_ALL (FMGPU_SEL_GENERAL_DFS | FMGPU_SEL_NO_PREFIX_TABLE | FMGPU_SEL_NO_LF3 | FMGPU_SEL_NO_LF_GENERAL | FMGPU_SEL_NO_WALK_TABLE | FMGPU_SEL_NO_LENGTH_BUCKETS | \
-                       FMGPU_SEL_EXACT_ON_TREE | FMGPU_SEL_EXACT_ONE_SYMBOL | FMGPU_SEL_LOCATE_PER_LANE | FMGPU_SEL_NO_SHARING | FMGPU_SEL_NO_EXACT_LUT | FMGPU_SEL_NO_BOARD | FMGPU_SEL_UNPACK_QUERIES | FMGPU_SEL_LEAN_FORMAT_A | FMGPU_SEL_NO_LEAN)
+                       FMGPU_SEL_EXACT_ON_TREE | FMGPU_SEL_EXACT_ONE_SYMBOL | FMGPU_SEL_LOCATE_PER_LANE | FMGPU_SEL_NO_SHARING | FMGPU_SEL_NO_EXACT_LUT | FMGPU_SEL_NO_BOARD | FMGPU_SEL_UNPACK_QUERIES | FMGPU_SEL_NO_SAMPLE_CHAIN | FMGPU_SEL_LEAN_FORMAT_A | FMGPU_SEL_NO_LEAN)
 int         fmgpu_set_option(int32_t option, int64_t value);
 int         fmgpu_get_option(int32_t option, int64_t* value);
 
@@ -236,6 +242,7 @@ int fmgpu_index_row_bits(fmgpu_index_t h, int32_t* bits);   /* 32 or 64: the wid
 #define FMGPU_FMT_LOCATE     (1u << 11)  /* locate answer table */
 #define FMGPU_FMT_FUSED      (1u << 12)  /* presence bits of the sampled suffix array fused into the blocks */
 #define FMGPU_FMT_EXTRACT    (1u << 13)  /* text map and sample table of fmgpu_index_accelerate_extract */
+#define FMGPU_FMT_CHAIN      (1u << 14)  /* sample chain: the sampled rows in text order with the symbols between them */
 int fmgpu_index_formats(fmgpu_index_t h, uint32_t* mask);
 
 /* The library's own index file — replaces saveIndex / loadIndex (fmindex/diskStorage.h:12-27) for a handle of this library: a header, a description of
