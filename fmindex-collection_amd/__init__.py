@@ -14,10 +14,10 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import FmgpuError, DeviceBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE
+from .capi import FmgpuError, DeviceBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE
 from . import search_scheme  # noqa: F401
 
-__all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "LocateLinear", "search_locate", "reconstruct_text",
+__all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device"]
 
@@ -839,6 +839,31 @@ def search_best(index, queries, max_errors, n=UINT64_MAX, edit=True, schemes=Non
     call = _q4(queries, capi.lib().fmgpu_search_best, capi.lib().fmgpu_search_best_q4)
     return _run_best(lambda out, c, cnt, stratum, st: call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, arr, len(keep), n, capi.ptr(out), c, C.byref(cnt),
                                                            capi.ptr(stratum), st, None), nq, len(keep), capacity, want_stratum, want_stats)
+
+
+def search_smems(index, queries, min_len=1, max_rows=0, capacity=None, want_lengths=False, want_stats=False):
+    """fmgpu_search_smems: the super-maximal exact matches of every read — seeds for the reads a search scheme left behind.  `queries` as for the other searches
+    (list of reads, (qbuf, qoff) of numpy arrays or DeviceBuffers, PackedQueries).  A seed is kept if it has at least min_len symbols and (max_rows == 0 or) at most
+    max_rows rows.  Returns (hits, spans[, lengths][, stats]): hits = HIT_DTYPE records in ascending (qidx, qbeg) with seq = the seed's index within its read, ready for
+    index.locate_hits; spans = SEED_SPAN_DTYPE records (qbeg, qlen), one per hit; lengths = the match length of every batch symbol (uint32, symbol qoff[0] first)."""
+    qbuf, qoff, nq = _queries(queries)
+    lengths = None
+    if want_lengths:
+        ends = qoff if isinstance(qoff, np.ndarray) else qoff.to_array(np.uint64, nq + 1)
+        lengths = np.zeros(int(ends[-1]) - int(ends[0]) if nq else 0, dtype=np.uint32)
+    call = _q4(queries, capi.lib().fmgpu_search_smems, capi.lib().fmgpu_search_smems_q4)
+    cap = capacity if capacity is not None else max(1024, 4 * nq)
+    st, cnt = capi.Stats(), C.c_uint64()
+    for _ in range(2):                                            # once more with the size the call reported
+        hits, spans = np.zeros(max(cap, 1), dtype=HIT_DTYPE), np.zeros(max(cap, 1), dtype=SEED_SPAN_DTYPE)
+        rc = call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, min_len, max_rows, capi.ptr(hits), capi.ptr(spans), cap, C.byref(cnt),
+                  capi.ptr(lengths) if lengths is not None and lengths.size else None, C.byref(st) if want_stats else None, None)
+        if rc != capi.FMGPU_ERR_CAPACITY:
+            break
+        cap = int(cnt.value)
+    capi.check(rc)
+    res = (np.ascontiguousarray(hits[: cnt.value]), np.ascontiguousarray(spans[: cnt.value]))
+    return res + ((lengths,) if want_lengths else ()) + ((st,) if want_stats else ())
 
 
 class LocateLinear:

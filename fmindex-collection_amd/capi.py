@@ -91,6 +91,15 @@ TEXT_RANGE_DTYPE = np.dtype([("seq_id", "<u8"), ("pos", "<u8"), ("len", "<u8")])
 assert TEXT_RANGE_DTYPE.itemsize == C.sizeof(TextRange) == 24
 
 
+class SeedSpan(C.Structure):
+    """fmgpu_seed_span: where in its read a seed lies (fmgpu_search_smems)"""
+    _fields_ = [("qbeg", C.c_uint32), ("qlen", C.c_uint32)]
+
+
+SEED_SPAN_DTYPE = np.dtype([("qbeg", "<u4"), ("qlen", "<u4")])
+assert SEED_SPAN_DTYPE.itemsize == C.sizeof(SeedSpan) == 8
+
+
 class Scheme(C.Structure):
     _fields_ = [("n_searches", C.c_int32), ("n_parts", C.c_int32), ("pi", u64p), ("l", u64p), ("u", u64p),
                 ("partition", u64p), ("edit", C.c_int32), ("reserved", C.c_int32)]
@@ -121,6 +130,7 @@ EXPORTS = [
     "fmgpu_index_accelerate_extract", "fmgpu_sequence_lengths", "fmgpu_extract",
     "fmgpu_queries_pack4", "fmgpu_queries_unpack4", "fmgpu_search_exact_q4", "fmgpu_search_scheme_q4", "fmgpu_search_ng21_q4",
     "fmgpu_search_best", "fmgpu_search_best_ng21", "fmgpu_search_best_q4", "fmgpu_search_best_ng21_q4",
+    "fmgpu_search_smems", "fmgpu_search_smems_q4",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -241,6 +251,9 @@ def lib():
                                          C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(Stats), C.c_void_p]
     L.fmgpu_search_best_q4.argtypes = L.fmgpu_search_best.argtypes
     L.fmgpu_search_best_ng21_q4.argtypes = L.fmgpu_search_best_ng21.argtypes
+    L.fmgpu_search_smems.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64,
+                                     C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(Stats), C.c_void_p]
+    L.fmgpu_search_smems_q4.argtypes = L.fmgpu_search_smems.argtypes
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

@@ -300,6 +300,16 @@ int fmgpu_locate_hits(fmgpu_index_t h, const fmgpu_hit* hits, uint64_t count, fm
     if (count && (!hits || !out || !out_count)) return fail(FMGPU_ERR_INVALID, "hits / out / out_count is null");
     ROUTE(h, fmgpu_locate_hits(h, hits, count, out, capacity, out_count, stats, stream));
 }
+int fmgpu_search_smems(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint32_t min_len, uint64_t max_rows,
+                       fmgpu_hit* out, fmgpu_seed_span* out_span, uint64_t capacity, uint64_t* out_count, uint32_t* out_match_len, fmgpu_stats* stats, void* stream) {
+    if (nq == 0) { if (out_count) *out_count = 0; if (stats) *stats = fmgpu_stats{}; return 0; }      // (before the handle is looked at)
+    ROUTE(h, fmgpu_search_smems(h, qbuf, qoff, nq, min_len, max_rows, out, out_span, capacity, out_count, out_match_len, stats, stream));
+}
+int fmgpu_search_smems_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, uint32_t min_len, uint64_t max_rows,
+                          fmgpu_hit* out, fmgpu_seed_span* out_span, uint64_t capacity, uint64_t* out_count, uint32_t* out_match_len, fmgpu_stats* stats, void* stream) {
+    if (nq == 0) { if (out_count) *out_count = 0; if (stats) *stats = fmgpu_stats{}; return 0; }
+    ROUTE(h, fmgpu_search_smems_q4(h, packed, qoff, nq, min_len, max_rows, out, out_span, capacity, out_count, out_match_len, stats, stream));
+}
 int fmgpu_index_accelerate_extract(fmgpu_index_t h, int32_t enable) { ROUTE(h, fmgpu_index_accelerate_extract(h, enable)); }
 int fmgpu_sequence_lengths(fmgpu_index_t h, uint64_t* seq_ids, uint64_t* lengths, uint64_t capacity, uint64_t* out_count) {
     ROUTE(h, fmgpu_sequence_lengths(h, seq_ids, lengths, capacity, out_count));

@@ -33,6 +33,10 @@ int fmgpu_search_backtracking(fmgpu_index_t h, const uint8_t* qbuf, const uint64
 int fmgpu_locate(fmgpu_index_t h, const uint64_t* rows, uint64_t count, uint64_t* out_seq, uint64_t* out_pos, uint64_t* out_steps, fmgpu_stats* stats, void* stream);
 int fmgpu_locate_hits(fmgpu_index_t h, const fmgpu_hit* hits, uint64_t count, fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
                       fmgpu_stats* stats, void* stream);
+int fmgpu_search_smems(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint32_t min_len, uint64_t max_rows,
+                       fmgpu_hit* out, fmgpu_seed_span* out_span, uint64_t capacity, uint64_t* out_count, uint32_t* out_match_len, fmgpu_stats* stats, void* stream);
+int fmgpu_search_smems_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, uint32_t min_len, uint64_t max_rows,
+                          fmgpu_hit* out, fmgpu_seed_span* out_span, uint64_t capacity, uint64_t* out_count, uint32_t* out_match_len, fmgpu_stats* stats, void* stream);
 int fmgpu_cursor_extend(fmgpu_index_t h, int32_t direction, uint64_t count, const uint64_t* lb, const uint64_t* lb_rev, const uint64_t* len, const uint8_t* symb,
                         uint64_t* out_lb, uint64_t* out_lb_rev, uint64_t* out_len, void* stream);
 int fmgpu_build_index(const uint8_t* seqs, const uint64_t* seq_off, uint64_t nseq, int32_t sigma, int32_t layout, uint64_t sampling_rate, int32_t bidirectional,

@@ -901,6 +901,46 @@ void search_n(Index const& index, Queries const& queries, size_t errors, size_t 
     search_ng26::search<EditDistance>(index, queries, errors, std::forward<Delegate>(delegate), n);
 }
 
+// fmc::search_smems(index, queries, minLen, maxRows, delegate(qidx, cursor, qbeg, qlen)) — no counterpart in the reference: the super-maximal exact matches of
+// every read (fmgpu_search_smems), reported in ascending (qidx, qbeg).  cursor holds the rows of queries[qidx][qbeg .. qbeg + qlen); it has been extended leftwards
+// only (lbRev = 0 on a BiFMIndex).  A seed is kept if qlen >= minLen and (maxRows == 0 or) it has at most maxRows rows.
+namespace detail {
+template <typename Index, typename Call, typename Delegate>
+void report_smems(Index const& index, size_t nq, Call&& call, Delegate&& delegate) {
+    std::vector<fmgpu_hit> hits(std::max<size_t>(1024, 4 * nq));
+    std::vector<fmgpu_seed_span> spans(hits.size());
+    uint64_t count = 0;
+    int rc = call(hits.data(), spans.data(), hits.size(), &count);
+    if (rc == FMGPU_ERR_CAPACITY) {                               // once more with the size the call reported
+        hits.resize(count); spans.resize(count);
+        rc = call(hits.data(), spans.data(), hits.size(), &count);
+    }
+    check(rc);
+    using cursor_t = select_cursor_t<Index>;
+    for (size_t k = 0; k < count; ++k) {
+        cursor_t cur{};
+        cur.index = &index; cur.lb = hits[k].lb; cur.len = hits[k].len;
+        delegate(static_cast<size_t>(hits[k].qidx), cur, static_cast<size_t>(spans[k].qbeg), static_cast<size_t>(spans[k].qlen));
+    }
+}
+}  // namespace detail
+template <typename Index, typename Queries, typename Delegate>
+void search_smems(Index const& index, Queries const& queries, size_t minLen, size_t maxRows, Delegate&& delegate) {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    size_t nq = off.size() - 1;
+    detail::report_smems(index, nq, [&](fmgpu_hit* out, fmgpu_seed_span* span, uint64_t cap, uint64_t* count) {
+        return fmgpu_search_smems(index.handle, buf.data(), off.data(), nq, static_cast<uint32_t>(minLen), maxRows, out, span, cap, count, nullptr, nullptr, nullptr);
+    }, std::forward<Delegate>(delegate));
+}
+template <typename Index, typename Delegate>
+void search_smems(Index const& index, PackedQueries const& queries, size_t minLen, size_t maxRows, Delegate&& delegate) {
+    detail::report_smems(index, queries.size(), [&](fmgpu_hit* out, fmgpu_seed_span* span, uint64_t cap, uint64_t* count) {
+        return fmgpu_search_smems_q4(index.handle, queries.packed.data(), queries.qoff.data(), queries.size(), static_cast<uint32_t>(minLen), maxRows, out, span, cap, count,
+                                     nullptr, nullptr, nullptr);
+    }, std::forward<Delegate>(delegate));
+}
+
 // LocateLinear{index, cursor}: for (auto [seqId, pos, offset] : LocateLinear{index, cursor}) — locate.h:14-57 (one batched call)
 template <typename Index, typename Cursor>
 struct LocateLinear {

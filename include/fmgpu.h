@@ -478,6 +478,44 @@ typedef struct fmgpu_position {
 int fmgpu_locate_hits(fmgpu_index_t h, const fmgpu_hit* hits, uint64_t count, fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
                       fmgpu_stats* stats, void* stream);
 
+/* ---- seeds: super-maximal exact matches and matching statistics -----------------------------------------------------------------------
+ * For the reads a search scheme leaves behind (more errors than its last stratum, long indels, a chimeric or clipped end): the longest stretches of every read that
+ * occur in the text, with their suffix-array intervals, to be located (fmgpu_locate_hits) and extended by the caller.  A read is q[0 .. m), sigma the index's alphabet size.
+ *   - Break: a query symbol outside 1 .. sigma - 1 (the delimiter 0, or anything >= sigma).  No match contains a break.
+ *   - Match length: for an end e, L[e] = the largest l <= e + 1 such that q[e - l + 1 .. e] holds no break and occurs in the text; 0 if q[e] is a break or does not
+ *     occur.  L[e + 1] <= L[e] + 1 always.
+ *   - SMEM: the pairs (qbeg, qlen) = (e - L[e] + 1, L[e]) over the ends e with L[e] >= 1 and (e == m - 1 or L[e + 1] <= L[e]) — the maximal exact matches of the
+ *     read that no other one contains.  qbeg is strictly increasing with e over the SMEMs of a read.
+ *   - Filters: a seed is reported if qlen >= max(min_len, 1) and (max_rows == 0 or its interval holds at most max_rows rows).  A dropped seed is just dropped:
+ *     nothing shorter is promoted in its place.
+ *   - Records: ascending qidx, inside a read ascending qbeg.  out[k] = {qidx, lb, lb_rev = 0, len = rows of the interval, errors = 0, seq = index of the seed within
+ *     its read}, out_span[k] = {qbeg, qlen}.  lb_rev = 0 is what fmgpu_search_backtracking writes on a unidirectional index: the cursor has been extended leftwards
+ *     only.  `out` goes into fmgpu_locate_hits as it is; fmgpu_position::hit then indexes out_span.
+ *   - out_match_len: NULL, or qoff[nq] - qoff[0] entries: entry i - qoff[0] = L of batch symbol i (the matching statistics).  Written whenever the call gets past
+ *     its argument checks, also on FMGPU_ERR_CAPACITY.
+ *   - *out_count = the seeds after the filters, on success and on FMGPU_ERR_CAPACITY alike; if it exceeds `capacity`, the call returns FMGPU_ERR_CAPACITY and writes
+ *     nothing to out / out_span (the rule of fmgpu_locate_hits; one small read-back).
+ *   - FMGPU_ERR_INVALID: a null handle; a null qbuf / qoff / out_count while nq > 0; a null out / out_span while capacity > 0.  nq == 0 returns 0 with *out_count = 0,
+ *     decided before the handle is looked at (out_count may then be NULL).  A read of 2^32 symbols or more, or a batch of 2^32 symbols or more:
+ *     FMGPU_ERR_UNSUPPORTED.  `_q4` on sigma > 15: FMGPU_ERR_UNSUPPORTED.
+ *   - FMIndex or BiFMIndex, every layout, 32- and 64-bit rows; only the forward bwt is read.  Every buffer may be host or device memory.  The call returns after
+ *     completion and frees its scratch: per query symbol 16 bytes with 32-bit rows, 24 with 64-bit rows (match length 4, interval 8 / 16, selection flag and
+ *     scan 4), 4 fewer where out_match_len is device memory and serves as it is; `_q4` adds the unpacked byte per symbol.
+ *   - stats: lf_steps = the extensions a one-symbol walk executes: the sum of L[e], plus one for every end whose walk stopped on an extension that came out empty
+ *     (L[e] <= e and q[e - L[e]] is not a break; a break costs no step).  hits = records; kernel_ms = the walk kernel alone; table_bytes / table_accesses as
+ *     exact search in one-symbol steps counts them on the one-symbol blocks (12 bytes per entry loaded), 0 on the other layouts.
+ *   - `_q4`: `packed` in place of qbuf; the batch is unpacked into a byte scratch and the byte path runs: the results are those of the byte call on
+ *     fmgpu_queries_unpack4(packed). */
+typedef struct fmgpu_seed_span { uint32_t qbeg, qlen; } fmgpu_seed_span;   /* 8 bytes */
+int fmgpu_search_smems(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                       uint32_t min_len, uint64_t max_rows,
+                       fmgpu_hit* out, fmgpu_seed_span* out_span, uint64_t capacity, uint64_t* out_count,
+                       uint32_t* out_match_len, fmgpu_stats* stats, void* stream);
+int fmgpu_search_smems_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq,
+                          uint32_t min_len, uint64_t max_rows,
+                          fmgpu_hit* out, fmgpu_seed_span* out_span, uint64_t capacity, uint64_t* out_count,
+                          uint32_t* out_match_len, fmgpu_stats* stats, void* stream);
+
 /* the 16-byte transport form of hit records (what a rank sends to the gathering rank): out[2k] = qidx:32 | lb:32,
  * out[2k+1] = len:32 | errors:8 | seq:24; lb_rev is dropped (it only serves further extension of the cursor).  Needs qidx, lb, len < 2^32,
  * errors < 256, seq < 2^24; a record that does not fit makes the call return FMGPU_ERR_UNSUPPORTED (checked on the device; the call
