@@ -97,7 +97,8 @@ static int set_opt(int option, int64_t value) {
 // between handles on two devices re-uses both sets.  FMGPU_OPT_FAIL_SCRATCH = k (test hook) fails the k-th allocation of the next creation.
 void CallScratch::drop() {
     for (void* p : {(void*)ctr, (void*)sink, (void*)len2, frames, dfs_ctr, order, board, exact_state}) if (p) (void)hipFree(p);
-    if (exact_state_ev) (void)hipEventDestroy(exact_state_ev);
+    for (hipEvent_t ev : {exact_state_ev, exact_fork_ev, exact_join_ev}) if (ev) (void)hipEventDestroy(ev);
+    if (exact_side) (void)hipStreamDestroy(exact_side);
     if (pinned) (void)hipHostFree(pinned);
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);

@@ -234,8 +234,10 @@ struct CallScratch {
     hipStream_t dfs_streams[8] = {};                              // a ragged batch: the launches of its read lengths run side by side on these (made on first use)
     hipEvent_t dfs_events[9] = {};
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    void* exact_state = nullptr; size_t exact_state_bytes = 0;    // exact search along the sample chain: one word per read between its three kernels, grown on demand and kept between calls
+    void* exact_state = nullptr; size_t exact_state_bytes = 0;    // exact search along the sample chain: one word per read between its kernels, grown on demand and kept between calls
     hipEvent_t exact_state_ev = nullptr;                          // ... recorded behind the last kernel that used it: a call on another stream waits for it
+    hipStream_t exact_side = nullptr;                             // ... the continue launch and the jump over its list run on this stream beside the jump over all reads (made on first use)
+    hipEvent_t exact_fork_ev = nullptr, exact_join_ev = nullptr;  // ... forked from the caller's stream behind the park launch, joined in front of the resume launch
     void drop();
 };
 int call_scratch(CallScratch** out);          // the calling thread's scratch for its current device (created on first use; all-or-nothing)

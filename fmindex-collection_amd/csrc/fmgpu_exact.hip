@@ -147,10 +147,11 @@ __device__ __forceinline__ uint32_t pair_rank_lds(const lds_word* own, uint32_t 
 // MODE (the sample chain, 32-bit rows): 0 the whole search.  1 "park": a lane whose interval is one row while at least park_min symbols remain leaves the loop — its interval goes
 // to out_lb[q] (lb | len << 32), the symbols consumed | PARKED to state[q] — and a lane that ends writes its result as in mode 0 and FINISHED.  Once at most `hand` lanes of a wave
 // are left (the reads that take long to reach one row, or never do: 3 of 64 on the genome), the wave hands them over instead of riding on with 61 dummy lines per pass: interval and
-// symbols consumed | CONTINUE as above, the read's number appended to `list`.  3 "continue": one lane per entry of that list, dense again, from where the read stands; parks and ends as
-// in mode 1.  2 "resume": a lane whose state says RESUME (or still PARKED) starts from its interval and the symbols consumed, with the window filled there, and ends as any read
-// does; the others do and write nothing.  k_exact_chain runs between 3 and 2.
-constexpr uint32_t kStContinue = 0u, kStParked = 1u, kStResume = 2u, kStFinished = 3u, kStShift = 30u, kStDoneMask = (1u << kStShift) - 1u;
+// symbols consumed | CONTINUE as above, the read's number appended to `list`.  3 "continue": one lane per entry of that list, dense again, from where the read stands; ends as in mode 1 and
+// parks as PARKED_LATE (the jump over the list takes those; the jump over all reads takes PARKED).  2 "resume": a lane whose state says RESUME (or still PARKED / PARKED_LATE)
+// starts from its interval and the symbols consumed, with the window filled there, and ends as any read does; the others do and write nothing.  k_exact_chain runs between
+// 1 and 2 (all reads) and between 3 and 2 (the list).  state[q] = symbols consumed | code << kStShift.
+constexpr uint32_t kStContinue = 0u, kStParked = 1u, kStResume = 2u, kStFinished = 3u, kStParkedLate = 4u, kStShift = 29u, kStDoneMask = (1u << kStShift) - 1u;
 template <class Q, int MODE = 0>
 __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __restrict__ pairs, const idx_t* __restrict__ ex, uint32_t nex, const idx_t* __restrict__ psuper,
                                                  const void* __restrict__ slut, uint32_t lutL,
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
     bool parked = false, handed = false; uint32_t park_done = 0;    // (modes 1, 3; `done` itself goes on counting the wave's passes)
     if constexpr (MODE == 2) {
         const uint32_t st = q < nq ? state[q] : kStFinished << kStShift;
-        if ((st >> kStShift) == kStResume || (st >> kStShift) == kStParked) { const uint64_t w = out_lb[q]; lb = (idx_t)w; len = (idx_t)(w >> 32); from = st & kStDoneMask; }
+        if ((st >> kStShift) == kStResume || (st >> kStShift) == kStParked || (st >> kStShift) == kStParkedLate) { const uint64_t w = out_lb[q]; lb = (idx_t)w; len = (idx_t)(w >> 32); from = st & kStDoneMask; }
         else m = 0;                                                 // (finished before: nothing to do, nothing to write)
     }
     if constexpr (MODE == 3) if (q < nq) { const uint64_t w = out_lb[q]; lb = (idx_t)w; len = (idx_t)(w >> 32); from = state[q] & kStDoneMask; }
@@ -312,14 +313,14 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
     if constexpr (MODE == 0) { if (q < nq) store_interval(out_lb, out_len, q, lb, len); }
     else if constexpr (MODE == 1 || MODE == 3) {
         if (q < nq) {
-            if (parked || handed) { out_lb[q] = (uint64_t)lb | ((uint64_t)len << 32); state[q] = park_done | ((parked ? kStParked : kStContinue) << kStShift); }
+            if (parked || handed) { out_lb[q] = (uint64_t)lb | ((uint64_t)len << 32); state[q] = park_done | ((parked ? (MODE == 3 ? kStParkedLate : kStParked) : kStContinue) << kStShift); }
             else { store_interval(out_lb, out_len, q, lb, len); state[q] = kStFinished << kStShift; }
         }
     } else { if (m) store_interval(out_lb, out_len, q, lb, len); }
     add_counters(steps_total, steps, 12u * acc + 68u * acc2 + (uint32_t)kSlutEntryBytes * acc3, acc + acc2 + acc3, lut_steps);
 }
 
-// ---- one-row reads along the sample chain (Format C, fmgpu_common.h; 32-bit rows).  One lane per read; a lane whose read k_exact_p did not park leaves at once.
+// ---- one-row reads along the sample chain (Format C, fmgpu_common.h; 32-bit rows).  One lane per read; a lane whose read k_exact_p did not park does and writes nothing.
 //  seek   at most rate - 1 one-symbol steps on Format A until the row is a sampled one.  The 64-byte block of a step says whether the row is sampled (fused presence bits, else
 //         the presence bitvector), holds the entry of the read's next symbol and the rank of the sampled row; the four lanes of a quad fetch it together, straight into LDS, as
 //         k_locate_coop does (a lane that reads its own block with several loads runs at half the line rate).  A step that would empty the interval, a delimiter or a foreign
@@ -329,10 +330,26 @@ __global__ __launch_bounds__(256) void k_exact_p(OccA<5> occ, const uint8_t* __r
 //  window is found there, by the pair and single steps that give the reference's miss row and step count.  Jumped symbols count as steps and as table_steps.
 constexpr uint32_t kChainRegion = 1024u + 16u;       // bytes per region of a round (64 pieces + padding that spreads the owners' reads over the LDS banks)
 constexpr uint32_t kChainFilterBits = 32768;         // chain position mod this
-template <class Q>
+// The read comes from a QueryWindow filled once where the read was parked (no query byte is loaded inside the loops; a read with more than a window of symbols left refills at
+// `done`): the lane's next symbol is nibble d (0..7) of w[0], its next 16 are alignbit(w[1], w[0], 4 d) and alignbit(w[2], w[1], 4 d), and a lane whose d reaches 8 shifts the
+// window down — the words are indexed by constants only (QueryWindow::fill).  An entry's 2-bit codes, spread to nibbles + 1 each, are compared with the read's next `rate`
+// nibbles in one 64-bit compare: equal means every one of those symbols is in 1..4 (a delimiter is 0, a foreign byte 15, a nibble of the packed form above 4 itself).
+// LISTED: one lane per entry of the continue launch's list, acting on PARKED_LATE (the reads that launch parked); otherwise one lane per read, acting on PARKED (the park launch's).
+__device__ __forceinline__ uint64_t chain_code_nibbles(uint32_t syms) {     // 16 2-bit codes -> 16 nibbles, + 1 each: the symbols themselves
+    uint64_t x = syms;
+    x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+    x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+    x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    return x + 0x1111111111111111ull;
+}
+template <class Q, bool LISTED = false>
 __global__ __launch_bounds__(256) void k_exact_chain(OccA<5> occ, ViewSA sa, const uint2* __restrict__ chain, const uint32_t* __restrict__ chain_of, const uint32_t* __restrict__ ex, uint32_t nex,
                                                      uint32_t rate, const uint8_t* __restrict__ qbuf, const uint64_t* __restrict__ qoff, uint64_t nq,
-                                                     uint64_t* __restrict__ out_lb, uint32_t* __restrict__ state, unsigned long long* __restrict__ steps_total) {
+                                                     uint64_t* __restrict__ out_lb, uint32_t* __restrict__ state, unsigned long long* __restrict__ steps_total,
+                                                     const uint32_t* __restrict__ list_count = nullptr, const uint32_t* __restrict__ list = nullptr) {
+    uint32_t listed_reads = 0;
+    if constexpr (LISTED) { listed_reads = *list_count; if (blockIdx.x * 256u >= listed_reads) return; }        // (the launch is sized for the longest list there can be)
     extern __shared__ uint32_t s_blk[];                             // 4 waves x 4 regions
     __shared__ uint32_t s_filt[kChainFilterBits / 32u];
     __shared__ uint32_t s_ex[512];
@@ -353,19 +370,28 @@ __global__ __launch_bounds__(256) void k_exact_chain(OccA<5> occ, ViewSA sa, con
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     lds_word* const wave_lds = (lds_word*)(s_blk + wave * 4u * (kChainRegion / 4u));
     const lds_word* const own = wave_lds + (lane & 3u) * (kChainRegion / 4u) + (lane >> 2) * 16u;
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t row = 0, done = 0, m = 0, cur = 255u;                  // cur: the read's next symbol
+    uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (LISTED) q = q < listed_reads ? (uint64_t)list[q] : nq;
+    constexpr uint32_t mine_state = LISTED ? kStParkedLate : kStParked;
+    uint32_t row = 0, done = 0, m = 0;
+    uint64_t o = 0;
     bool seeking = false;
-    QueryReader<Q> qr;
     if (q < nq) {
         const uint32_t st = state[q];
-        if ((st >> kStShift) == kStParked) {
-            const uint64_t o = qoff[q];
+        if ((st >> kStShift) == mine_state) {
+            o = qoff[q];
             m = (uint32_t)(qoff[q + 1] - o); done = st & kStDoneMask; row = (uint32_t)out_lb[q];
-            if (done < m) { seeking = true; qr.init(qbuf, o, m - done); cur = qr.next(); }
+            seeking = done < m;
         }
     }
     const bool mine = seeking;
+    QueryWindow win;
+    uint32_t d = 0, wleft = 0;                                      // the lane's next symbol: nibble d of w[0]; symbols of the read the window still holds from there on
+    if (__ballot(mine)) { win.template fill<Q>(qbuf, o, m, done, 5u); wleft = 8u * kWindowWords; }      // (m = 0 in a lane that has no read here: it loads nothing)
+    else {
+#pragma unroll
+        for (uint32_t i = 0; i < kWindowWords; ++i) win.w[i] = 0u;
+    }
     bool found = false;
     uint32_t rank = 0, walked = 0, steps = 0, tsteps = 0, acc = 0, acc4 = 0, acc8 = 0;
     for (;;) {                                                      // wave-uniform: a lane that is not seeking rides along with block 0
@@ -382,6 +408,8 @@ __global__ __launch_bounds__(256) void k_exact_chain(OccA<5> occ, ViewSA sa, con
         if (seeking) {
             ++acc;
             const uint32_t bit = row & 63u;
+            // the read's next symbol (at most rate - 1 <= 15 steps from a fresh window: it never runs dry here); past the read's end: none
+            const uint32_t cur = done < m ? __builtin_amdgcn_alignbit(win.w[1], win.w[0], 4u * d) & 15u : 15u;
             bool present;
             if (occ.v.fused) present = ((((uint64_t)own[1] | ((uint64_t)own[2] << 32)) >> bit) & 1ull) != 0;
             else present = sa_present(sa, (idx_t)row);
@@ -396,7 +424,8 @@ __global__ __launch_bounds__(256) void k_exact_chain(OccA<5> occ, ViewSA sa, con
                 else {
                     row = own[3u * cur] + popc64(bits & lowmask(bit));
                     ++done; ++steps; ++walked;
-                    cur = done < m ? qr.next() : 255u;
+                    --wleft;
+                    if (++d == 8u) { win.shift(); d = 0u; }
                 }
             }
         }
@@ -407,23 +436,22 @@ __global__ __launch_bounds__(256) void k_exact_chain(OccA<5> occ, ViewSA sa, con
         uint32_t t = chain_of[rank];
         uint2 e = chain[t];
         ++acc4; ++acc8;
+        const uint64_t rate_mask = rate >= 16u ? ~0ull : (1ull << (4u * rate)) - 1ull;
         while (m - done >= rate && !listed(t)) {                    // (entry 0 has no predecessor: listed)
             const uint2 p = chain[t - 1u];
             ++acc8;
-            uint32_t code = 0; bool ok = true;
-            for (uint32_t j = 0; j < rate; ++j) {
-                const uint32_t c = j == 0u ? cur : qr.next();
-                ok = ok && c - 1u < 4u;
-                code |= ((c - 1u) & 3u) << (2u * j);
-            }
-            if (!ok || code != e.y) break;
+            if (wleft < rate) { win.template fill<Q>(qbuf, o, m, done, 5u); d = 0u; wleft = 8u * kWindowWords; }      // (a read with more than a window of symbols left: its next 128)
+            const uint64_t next16 = (uint64_t)__builtin_amdgcn_alignbit(win.w[1], win.w[0], 4u * d) | ((uint64_t)__builtin_amdgcn_alignbit(win.w[2], win.w[1], 4u * d) << 32);
+            if ((next16 & rate_mask) != (chain_code_nibbles(e.y) & rate_mask)) break;
             row = p.x; e = p; --t;
             done += rate; steps += rate; tsteps += rate;
-            cur = done < m ? qr.next() : 255u;
+            wleft -= rate; d += rate;
+            if (d >= 8u) { win.shift(); d -= 8u; }
+            if (d >= 8u) { win.shift(); d -= 8u; }
         }
     }
     if (mine) { out_lb[q] = (uint64_t)row | (1ull << 32); state[q] = done | (kStResume << kStShift); }
-    add_counters(steps_total, steps, 64u * acc + 4u * acc4 + 8u * acc8, acc + acc4 + acc8, tsteps);
+    add_counters(steps_total, steps, 64u * acc + 4u * acc4 + 8u * acc8, acc + acc4 + acc8, tsteps, true);
 }
 
 // ---- exact search on Format S (fmgpu_common.h): ONE 128-byte line per LF step and interval end where the multi-ary wavelet tree of sigma = 28 takes two —
@@ -881,7 +909,7 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
         // k_exact_a runs best with 5 resident blocks per CU, not the 8 its 28 registers allow (measured on the 3.09 Gbp index, 10 M x 101 bp: 8 / 6 / 5 / 4 / 3
         // blocks = 19.53 / 19.23 / 18.92 / 19.10 / 18.95 ms — more waves only queue up at the memory system): 28 KB of unused dynamic LDS set the residency
         const size_t lds_a = dev_env("FMGPU_DEV_EXACT_LDS") ? dev_extra_lds : (size_t)28 * 1024;
-        // the sample chain (no table in front, a batch long enough to park): park -> continue -> jump -> resume, four launches under one timer
+        // the sample chain (no table in front, a batch long enough to park): park -> continue, jump(list) | jump(all) -> resume, five launches under one timer
         uint32_t park_min = kParkMin;
         if (const char* ev = dev_env("FMGPU_DEV_EXACT_PARK_MIN")) park_min = std::max(16u, (uint32_t)atoi(ev));      // (dev knob; a parked read holds a whole window)
         bool along_chain = !kWide && x->chain && x->bwt.sigma == 5 && x->bwt.pairs && !x->bwt.slut && !x->bwt.kblk && !x->bwt.walkj &&
@@ -891,6 +919,7 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
         const uint64_t nwaves = (nq + 63) / 64;
         uint32_t* state = nullptr; uint32_t* list = nullptr;      // state: [nq] | the list's length (16 bytes) | the list: nwaves x 16 at most
         CallScratch* sc = nullptr;
+        bool overlap = false;
         if (along_chain) {
             if (!have_shape) { uint32_t mn = 0; if ((rc = query_len_range(qo, nq, stream, &shape_max, &mn))) return rc; timer.start(); }
             along_chain = shape_max >= park_min + 16u && shape_max <= kStDoneMask;
@@ -911,6 +940,15 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
             else FM_HIP(hipStreamWaitEvent(stream, sc->exact_state_ev, 0));      // (the thread's previous call may have run on another stream)
             state = (uint32_t*)sc->exact_state; list = state + state_words;
             FM_HIP(hipMemsetAsync(list, 0, 16, stream));
+            // the side leg: not without a list, not with the dev knob, and not while the caller's stream is capturing (a graph with parallel branches is the caller's to make)
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+            overlap = hand != 0 && !dev_env("FMGPU_DEV_EXACT_SERIAL") && cap == hipStreamCaptureStatusNone;
+            if (overlap) {
+                if (!sc->exact_side) FM_HIP(hipStreamCreateWithFlags(&sc->exact_side, hipStreamNonBlocking));
+                if (!sc->exact_fork_ev) FM_HIP(hipEventCreateWithFlags(&sc->exact_fork_ev, hipEventDisableTiming));
+                if (!sc->exact_join_ev) FM_HIP(hipEventCreateWithFlags(&sc->exact_join_ev, hipEventDisableTiming));
+            }
         }
         auto launch = [&](auto src) {                            // the kernel of the byte form or of the 4-bit packed form
             using Q = decltype(src);
@@ -918,10 +956,22 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
                 const size_t lds_p = 4 * 8 * kCoopRegion + dev_extra_lds;
                 k_exact_p<Q, 1><<<grid, block, lds_p, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super, nullptr, 0u, qb, qo, nq, n, ol, on, dsteps, state, park_min,
                                                                 list, list + 4, hand);
-                if (hand) k_exact_p<Q, 3><<<dim3((unsigned)((nwaves * hand + 255) / 256)), block, lds_p, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super, nullptr, 0u, qb, qo, nq, n,
-                                                                                                                ol, on, dsteps, state, park_min, list, list + 4, 0u);
-                if (!dev_env("FMGPU_DEV_EXACT_NO_JUMP"))            // (dev knob: park and resume alone — a parked read resumes where it stands)
-                k_exact_chain<Q><<<grid, block, 4 * 4 * kChainRegion, stream>>>(OccA<5>{x->bwt.va}, x->vsa, x->chain, x->chain_of, x->chain_ex, x->chain_nex, x->chain_rate, qb, qo, nq, ol, state, dsteps);
+                // park | continue, jump(list) beside jump(all) | resume.  The two legs touch disjoint reads: jump(all) writes only reads whose state is PARKED, set by the park
+                // launch, which is complete at the fork; continue and jump(list) write only listed reads, whose state moves CONTINUE -> PARKED_LATE / FINISHED -> RESUME, every one of
+                // them a value jump(all) skips (state words are aligned 4-byte stores: it sees the old or the new one).  The list and its count are complete at the fork, and the
+                // step counters are atomics.  Serial (no side stream): the same launches in the order park, continue, jump(list), jump(all), resume.
+                const bool jump = !dev_env("FMGPU_DEV_EXACT_NO_JUMP");     // (dev knob: park and resume alone — a parked read resumes where it stands)
+                hipStream_t side = overlap ? sc->exact_side : stream;
+                const dim3 lgrid((unsigned)((nwaves * hand + 255) / 256));
+                if (overlap) { (void)hipEventRecord(sc->exact_fork_ev, stream); (void)hipStreamWaitEvent(side, sc->exact_fork_ev, 0); }
+                if (hand) {
+                    k_exact_p<Q, 3><<<lgrid, block, lds_p, side>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super, nullptr, 0u, qb, qo, nq, n,
+                                                                   ol, on, dsteps, state, park_min, list, list + 4, 0u);
+                    if (jump) k_exact_chain<Q, true><<<lgrid, block, 4 * 4 * kChainRegion, side>>>(OccA<5>{x->bwt.va}, x->vsa, x->chain, x->chain_of, x->chain_ex, x->chain_nex, x->chain_rate, qb, qo, nq, ol, state, dsteps,
+                                                                                                   list, list + 4);
+                }
+                if (jump) k_exact_chain<Q><<<grid, block, 4 * 4 * kChainRegion, stream>>>(OccA<5>{x->bwt.va}, x->vsa, x->chain, x->chain_of, x->chain_ex, x->chain_nex, x->chain_rate, qb, qo, nq, ol, state, dsteps);
+                if (overlap) { (void)hipEventRecord(sc->exact_join_ev, side); (void)hipStreamWaitEvent(stream, sc->exact_join_ev, 0); }
                 k_exact_p<Q, 2><<<grid, block, lds_p, stream>>>(OccA<5>{x->bwt.va}, x->bwt.pairs, x->bwt.pairs_ex, x->bwt.pairs_nex, x->bwt.pairs_super, nullptr, 0u, qb, qo, nq, n, ol, on, dsteps, state, park_min);
                 (void)hipEventRecord(sc->exact_state_ev, stream);
                 return;

@@ -39,9 +39,11 @@ __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
 
 // counters of the one-thread-per-query kernels: [0] executed steps, [1] table bytes consumed, [2] table accesses, [3] steps that an interval-table entry stood for (fmgpu_stats), each striped
 // over kCounterStripes words (a single word would serialise one atomic per wave — 156 k of them for 10 M queries — behind each other)
-__device__ __forceinline__ void add_counters(unsigned long long* __restrict__ ctr, uint32_t steps, uint32_t bytes, uint32_t accesses, uint32_t table_steps = 0u) {
+// stepless: a wave that took no step still adds what it loaded (k_exact_chain's list form: which reads share a wave follows the order of the list, which differs from run to run,
+// and the sums must not)
+__device__ __forceinline__ void add_counters(unsigned long long* __restrict__ ctr, uint32_t steps, uint32_t bytes, uint32_t accesses, uint32_t table_steps = 0u, bool stepless = false) {
     const uint32_t ts = wave_sum(steps), tb = wave_sum(bytes), ta = wave_sum(accesses), tt = wave_sum(table_steps);
-    if ((threadIdx.x & 63u) == 0 && ts) {
+    if ((threadIdx.x & 63u) == 0 && (ts || (stepless && ta))) {
         const uint32_t stripe = blockIdx.x & (kCounterStripes - 1u);
         atomicAdd(&ctr[stripe], (unsigned long long)ts);
         atomicAdd(&ctr[kCounterStripes + stripe], (unsigned long long)tb);

@@ -1,6 +1,8 @@
 """exact search along the sample chain: one build of the headline index, then the headline batch (10 M x 101 bp) under the development build's knobs —
-the pair table alone, the hand-over threshold (FMGPU_DEV_EXACT_HAND), the park threshold (FMGPU_DEV_EXACT_PARK_MIN), park + resume without the jump (FMGPU_DEV_EXACT_NO_JUMP) —
-two rounds, every result compared with the first.  usage: python tools/exact_chain_sweep.py [launches per setting]   (needs make DEV=1)"""
+the pair table alone, the five launches on one stream (FMGPU_DEV_EXACT_SERIAL: the side leg behind instead of beside the jump over all reads), the hand-over threshold
+(FMGPU_DEV_EXACT_HAND), the park threshold (FMGPU_DEV_EXACT_PARK_MIN), park + resume without the jump (FMGPU_DEV_EXACT_NO_JUMP) — two rounds, every result compared with the first.
+usage: python tools/exact_chain_sweep.py [launches per setting] [legs]   (needs make DEV=1; legs: only off / shipped / serial; FMGPU_LIBRARY = another development build of
+the same ABI, e.g. the parent commit's, whose rows then stand beside this build's in one job)"""
 import ctypes as C
 import os
 import sys
@@ -8,7 +10,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ["FMGPU_LIBRARY"] = os.path.join(ROOT, "fmindex-collection_amd", "libfmgpu_dev.so")
+os.environ.setdefault("FMGPU_LIBRARY", os.path.join(ROOT, "fmindex-collection_amd", "libfmgpu_dev.so"))
 import numpy as np
 import torch
 import bench
@@ -16,6 +18,8 @@ import fmindex_collection_amd as fm
 from fmindex_collection_amd import capi, datasets
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+legs_only = len(sys.argv) > 2 and sys.argv[2] == "legs"
+print("library", os.environ["FMGPU_LIBRARY"], flush=True)
 c = bench.Ctx()
 c.args = type("Args", (), {"scale": 1.0})()
 c.rank, c.world, c.np, c.torch, c.fm, c.capi, c.datasets = 0, 1, np, torch, fm, capi, datasets
@@ -36,7 +40,7 @@ stats = capi.Stats()
 
 
 def run(label, env, sel):
-    for k in ("FMGPU_DEV_EXACT_PARK_MIN", "FMGPU_DEV_EXACT_NO_JUMP", "FMGPU_DEV_EXACT_HAND"):
+    for k in ("FMGPU_DEV_EXACT_PARK_MIN", "FMGPU_DEV_EXACT_NO_JUMP", "FMGPU_DEV_EXACT_HAND", "FMGPU_DEV_EXACT_SERIAL"):
         os.environ.pop(k, None)
     os.environ.update(env)
     fm.options["kernel_select"] = sel
@@ -67,7 +71,10 @@ def knobs(hand, park, nojump=False):
 
 base = None
 for rnd in range(2):
-    for label, env, sel in [("off", {}, capi.SEL_NO_SAMPLE_CHAIN), ("shipped", {}, 0)] + [knobs(h, p) for h, p in ((10, 32), (10, 48), (0, 48), (3, 48), (6, 48), (16, 48), (6, 32), (6, 64), (16, 32))] + [knobs(10, 32, True)]:
+    rows = [("off", {}, capi.SEL_NO_SAMPLE_CHAIN), ("shipped", {}, 0), ("serial", {"FMGPU_DEV_EXACT_SERIAL": "1"}, 0)]
+    if not legs_only:
+        rows += [knobs(h, p) for h, p in ((10, 32), (10, 48), (0, 48), (3, 48), (6, 48), (16, 48), (6, 32), (6, 64), (16, 32))] + [knobs(10, 32, True)]
+    for label, env, sel in rows:
         res, lf = run(label + "_%d" % rnd, env, sel)
         if base is None:
             base = (res, lf)

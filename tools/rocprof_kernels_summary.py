@@ -16,7 +16,7 @@ def files(root, suffix):
 
 
 def short(name):
-    m = re.search(r"(k_\w+)<[^,>]*(?:, (\d+))?>", name)
+    m = re.search(r"(k_\w+)<[^,>]*(?:, (\w+))?>", name)       # (k_exact_p<Q, 1> -> k_exact_p<1>, k_exact_chain<Q, true> -> k_exact_chain<true>: its list form)
     return (m.group(1) + ("<%s>" % m.group(2) if m.group(2) else "")) if m else name.split("(")[0]
 
 
