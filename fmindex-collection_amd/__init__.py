@@ -14,12 +14,12 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import FmgpuError, DeviceBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE
+from .capi import FmgpuError, DeviceBuffer, PinnedBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE
 from . import search_scheme  # noqa: F401
 
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
-           "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device"]
+           "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer"]
 
 
 class _Options:
@@ -647,6 +647,83 @@ class search_ng26:
         call = _q4(queries, capi.lib().fmgpu_search_scheme, capi.lib().fmgpu_search_scheme_q4)
         hits, st = _run_hits(lambda out, c, cnt, st: call(
             index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(sc), n, capi.ptr(out), c, C.byref(cnt), C.byref(st), None), cap)
+        return (hits, st) if want_stats else hits
+
+
+class Feed:
+    """a feed (fmgpu_feed_*, include/fmgpu.h): HOST batches searched chunk by chunk on one index, the upload of the next chunk and the download of the previous one
+    running beside the search of the current one.  0 / None in an argument = the library's default.  `queries` = a flat (qbuf, qoff) of numpy arrays (pinned memory,
+    e.g. PinnedBuffer.array(...), is copied from where it lies), a list of sequences (searched through the `_v` calls, without flattening) or a PackedQueries of
+    numpy arrays.  One feed serves one call at a time; a context manager."""
+
+    def __init__(self, index, chunk_reads=0, chunk_symbols=0, slots=0, host_threads=0, pack4=False):
+        cfg = capi.FeedConfig(int(chunk_reads or 0), int(chunk_symbols or 0), int(slots or 0), int(host_threads or 0), 1 if pack4 else 0, 0)
+        h = C.c_void_p()
+        capi.check(capi.lib().fmgpu_feed_create(index._h, C.byref(cfg), C.byref(h)))
+        self._f, self._index = h, index                      # (the handle outlives the feed)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._f:
+            capi.check(capi.lib().fmgpu_feed_destroy(self._f))
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """dict: pinned_bytes, device_bytes the feed holds; chunks, staged_bytes, uploaded_bytes of the last call"""
+        v = [C.c_uint64() for _ in range(5)]
+        capi.check(capi.lib().fmgpu_feed_info(self._f, *(C.byref(x) for x in v)))
+        return dict(zip(("pinned_bytes", "device_bytes", "chunks", "staged_bytes", "uploaded_bytes"), (int(x.value) for x in v)))
+
+    @staticmethod
+    def _batch(queries):
+        """(suffix of the entry point, first argument, second argument, nq, objects to keep alive)"""
+        if isinstance(queries, PackedQueries):
+            return "_q4", capi.ptr(queries.packed), capi.ptr(queries.qoff), queries.nq, None
+        if isinstance(queries, tuple):
+            qbuf, qoff, nq = _queries(queries)
+            return "", capi.ptr(qbuf), capi.ptr(qoff), nq, None
+        reads = [np.ascontiguousarray(q, dtype=np.uint8) for q in queries]
+        lens = np.fromiter((r.size for r in reads), dtype=np.uint64, count=len(reads))
+        ptrs = np.fromiter((r.ctypes.data for r in reads), dtype=np.uint64, count=len(reads))
+        return "_v", capi.ptr(ptrs), capi.ptr(lens), len(reads), (reads, lens, ptrs)
+
+    def search_exact(self, queries, out=None, want_stats=False):
+        """(lb, len) of every read, what search_no_errors.search returns; `out` = (lb, len) uint64 arrays to write into (pinned ones are written in place)"""
+        suffix, a, b, nq, keep = self._batch(queries)
+        lb, ln = (np.empty(nq, dtype=np.uint64), np.empty(nq, dtype=np.uint64)) if out is None else out
+        st = capi.Stats()
+        call = getattr(capi.lib(), "fmgpu_feed_search_exact" + suffix)
+        capi.check(call(self._f, a, b, nq, capi.ptr(lb), capi.ptr(ln), C.byref(st) if want_stats else None))
+        del keep
+        return (lb, ln, st) if want_stats else (lb, ln)
+
+    def search_scheme(self, queries, scheme, partition=None, n=UINT64_MAX, capacity=None, want_stats=False, edit=False):
+        """hit records in callback order, what search_ng26.search returns (a PackedQueries is not taken: the scheme kernels read bytes)"""
+        suffix, a, b, nq, keep = self._batch(queries)
+        if suffix == "_q4":
+            raise ValueError("a feed searches schemes over byte batches")
+        pi, l, u = (_u64(x) for x in scheme)
+        sc = capi.Scheme()
+        sc.n_searches, sc.n_parts = pi.shape
+        sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
+        part = _u64(partition) if partition is not None else None
+        sc.partition = part.ctypes.data_as(capi.u64p) if part is not None else None
+        sc.edit = 1 if edit else 0
+        cap = capacity if capacity is not None else max(1024, 4 * nq)
+        call = getattr(capi.lib(), "fmgpu_feed_search_scheme" + suffix)
+        hits, st = _run_hits(lambda out, c, cnt, st: call(self._f, a, b, nq, C.byref(sc), n, capi.ptr(out), c, C.byref(cnt), C.byref(st) if want_stats else None), cap)
+        del keep
         return (hits, st) if want_stats else hits
 
 

@@ -114,6 +114,12 @@ class Stats(C.Structure):
                 ("table_bytes", C.c_uint64), ("table_accesses", C.c_uint64), ("table_steps", C.c_uint64)]
 
 
+class FeedConfig(C.Structure):
+    """fmgpu_feed_config: 0 in a field = the library's default"""
+    _fields_ = [("chunk_reads", C.c_uint64), ("chunk_symbols", C.c_uint64), ("slots", C.c_int32), ("host_threads", C.c_int32),
+                ("pack4", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/fmgpu.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "fmgpu_abi_version", "fmgpu_last_error", "fmgpu_device_count", "fmgpu_set_device",
@@ -131,6 +137,8 @@ EXPORTS = [
     "fmgpu_queries_pack4", "fmgpu_queries_unpack4", "fmgpu_search_exact_q4", "fmgpu_search_scheme_q4", "fmgpu_search_ng21_q4",
     "fmgpu_search_best", "fmgpu_search_best_ng21", "fmgpu_search_best_q4", "fmgpu_search_best_ng21_q4",
     "fmgpu_search_smems", "fmgpu_search_smems_q4",
+    "fmgpu_feed_create", "fmgpu_feed_destroy", "fmgpu_feed_plan", "fmgpu_feed_search_exact", "fmgpu_feed_search_exact_q4", "fmgpu_feed_search_exact_v",
+    "fmgpu_feed_search_scheme", "fmgpu_feed_search_scheme_v", "fmgpu_feed_info", "fmgpu_malloc_host", "fmgpu_free_host",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -254,6 +262,18 @@ def lib():
     L.fmgpu_search_smems.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64,
                                      C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(Stats), C.c_void_p]
     L.fmgpu_search_smems_q4.argtypes = L.fmgpu_search_smems.argtypes
+    if hasattr(L, "fmgpu_feed_create"):                       # (FMGPU_LIBRARY may name an older build of the same ABI: tools/feed_probe.py times one)
+        L.fmgpu_feed_create.argtypes = [C.c_void_p, C.POINTER(FeedConfig), C.POINTER(C.c_void_p)]
+        L.fmgpu_feed_destroy.argtypes = [C.c_void_p]
+        L.fmgpu_feed_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
+        L.fmgpu_feed_search_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.fmgpu_feed_search_exact_q4.argtypes = L.fmgpu_feed_search_exact.argtypes
+        L.fmgpu_feed_search_exact_v.argtypes = L.fmgpu_feed_search_exact.argtypes
+        L.fmgpu_feed_search_scheme.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Scheme), C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.POINTER(Stats)]
+        L.fmgpu_feed_search_scheme_v.argtypes = L.fmgpu_feed_search_scheme.argtypes
+        L.fmgpu_feed_info.argtypes = [C.c_void_p, u64p, u64p, u64p, u64p, u64p]
+        L.fmgpu_malloc_host.argtypes = [C.POINTER(C.c_void_p), C.c_uint64]
+        L.fmgpu_free_host.argtypes = [C.c_void_p]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
@@ -321,6 +341,39 @@ class DeviceBuffer:
     def free(self):
         if self.ptr:
             lib().fmgpu_free(C.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PinnedBuffer:
+    """pinned host memory (fmgpu_malloc_host): what a feed copies from and writes to in place.  `.array(dtype, count)` is a numpy view of it (keep the buffer alive)."""
+
+    def __init__(self, nbytes):
+        p = C.c_void_p()
+        check(lib().fmgpu_malloc_host(C.byref(p), nbytes))
+        self.ptr, self.nbytes = p.value, nbytes
+
+    def array(self, dtype, count=None):
+        dtype = np.dtype(dtype)
+        count = self.nbytes // dtype.itemsize if count is None else count
+        assert count * dtype.itemsize <= self.nbytes
+        return np.frombuffer((C.c_uint8 * self.nbytes).from_address(self.ptr), dtype=dtype, count=count)
+
+    @classmethod
+    def from_array(cls, a):
+        a = np.ascontiguousarray(a)
+        b = cls(max(a.nbytes, 8))
+        b.array(np.uint8, a.nbytes)[:] = a.view(np.uint8).reshape(-1)
+        return b
+
+    def free(self):
+        if self.ptr:
+            lib().fmgpu_free_host(C.c_void_p(self.ptr))
             self.ptr = None
 
     def __del__(self):

@@ -164,6 +164,17 @@ static inline const IndexHeader* header_of(fmgpu_index_t h) {
 namespace fmgpu {
 int check_scheme(fmgpu_index_t h, const fmgpu_scheme* scheme, uint64_t max_hits_per_query) { ROUTE(h, check_scheme(h, scheme, max_hits_per_query)); }
 int check_expanded_scheme(fmgpu_index_t h, const fmgpu_expanded_scheme* scheme) { ROUTE(h, check_expanded_scheme(h, scheme)); }
+int search_exact_shaped(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats, void* stream,
+                        int32_t q4, uint64_t total, uint32_t longest, uint32_t shortest) {
+    ROUTE(h, search_exact_shaped(h, qbuf, qoff, nq, out_lb, out_len, stats, stream, q4, total, longest, shortest));
+}
+int exact_reads_nibbles_on(fmgpu_index_t h, int32_t* yes) { ROUTE(h, exact_reads_nibbles_on(h, yes)); }
+int handle_device(fmgpu_index_t h, int32_t* device) {
+    const IndexHeader* hd = header_of(h);
+    if (!hd) return fail(FMGPU_ERR_INVALID, "index handle is null or not a handle of this library");
+    *device = hd->device;
+    return 0;
+}
 }  // namespace fmgpu
 
 extern "C" {
@@ -327,6 +338,8 @@ int fmgpu_cursor_extend(fmgpu_index_t h, int32_t direction, uint64_t count, cons
 
 int fmgpu_malloc(void** ptr, uint64_t bytes) { if (!ptr) return fail(FMGPU_ERR_INVALID, "ptr is null"); FM_HIP(hipMalloc(ptr, bytes ? bytes : 8)); return 0; }
 int fmgpu_free(void* ptr) { if (ptr) FM_HIP(hipFree(ptr)); return 0; }
+int fmgpu_malloc_host(void** ptr, uint64_t bytes) { if (!ptr) return fail(FMGPU_ERR_INVALID, "ptr is null"); FM_HIP(hipHostMalloc(ptr, bytes ? bytes : 8, hipHostMallocDefault)); return 0; }
+int fmgpu_free_host(void* ptr) { if (ptr) FM_HIP(hipHostFree(ptr)); return 0; }
 int fmgpu_memcpy_h2d(void* dst, const void* src, uint64_t bytes) { if (bytes) FM_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return 0; }
 int fmgpu_memcpy_d2h(void* dst, const void* src, uint64_t bytes) { if (bytes) FM_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return 0; }
 int fmgpu_synchronize(void* stream) { FM_HIP(hipStreamSynchronize((hipStream_t)stream)); return 0; }

@@ -26,6 +26,9 @@ int fmgpu_search_scheme_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_
                            fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream);
 int fmgpu_search_ng21_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, const fmgpu_expanded_scheme* scheme, uint64_t max_hits_per_query,
                          fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream);
+int search_exact_shaped(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats, void* stream,
+                        int32_t q4, uint64_t total, uint32_t longest, uint32_t shortest);      // (not exported: exact search on device buffers whose shape the caller knows, for fmgpu_feed.hip)
+int exact_reads_nibbles_on(fmgpu_index_t h, int32_t* yes);                                     // (not exported: does exact search read the 4-bit packed form itself on this handle)
 int check_scheme(fmgpu_index_t h, const fmgpu_scheme* scheme, uint64_t max_hits_per_query);      // (not exported: the single-scheme calls' own argument checks, for fmgpu_best.hip)
 int check_expanded_scheme(fmgpu_index_t h, const fmgpu_expanded_scheme* scheme);
 int fmgpu_search_backtracking(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint64_t max_errors, fmgpu_hit* out, uint64_t capacity,

@@ -206,6 +206,13 @@ int unpack_queries(const uint8_t* packed, const uint64_t* qoff, uint64_t nq, hip
 int check_scheme(fmgpu_index_t h, const fmgpu_scheme* scheme, uint64_t max_hits_per_query);
 int check_expanded_scheme(fmgpu_index_t h, const fmgpu_expanded_scheme* scheme);
 
+// What a feed (fmgpu_feed.hip) asks of a handle, routed by its row width (fmgpu_abi.hip): exact search on device buffers whose shape the caller knows from host offsets
+// (fmgpu_exact.hip: no read-back, and no synchronisation without stats), whether exact search reads the 4-bit packed form itself there, and the handle's device.
+int search_exact_shaped(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats, void* stream,
+                        int32_t q4, uint64_t total, uint32_t longest, uint32_t shortest);
+int exact_reads_nibbles_on(fmgpu_index_t h, int32_t* yes);
+int handle_device(fmgpu_index_t h, int32_t* device);
+
 struct Built {   // host copies of construction by-products (fmgpu_build_index with keep_host)
     std::vector<std::vector<uint8_t>> part;
 };

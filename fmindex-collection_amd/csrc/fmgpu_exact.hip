@@ -850,9 +850,12 @@ static bool exact_reads_nibbles(const Index* x) {
     return x->bwt.search_family() == FAM_A && (!tables || exact_pair_lut(x)) && !(kernel_flags() & FMGPU_SEL_UNPACK_QUERIES);
 }
 
-// q4: qbuf is the 4-bit packed form (only where exact_reads_nibbles(x) holds)
+// what a caller that holds the offsets in host memory knows of a batch before it runs: symbols in all, the longest and the shortest read
+struct QueryShapeHint { uint64_t total; uint32_t longest, shortest; };
+
+// q4: qbuf is the 4-bit packed form (only where exact_reads_nibbles(x) holds); shape: the batch's shape from the caller instead of a read-back (search_exact_shaped)
 static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
-                        uint64_t* out_lb, uint64_t* out_len, bool packed, fmgpu_stats* stats, void* stream_, bool q4 = false) {
+                        uint64_t* out_lb, uint64_t* out_len, bool packed, fmgpu_stats* stats, void* stream_, bool q4 = false, const QueryShapeHint* shape = nullptr) {
     size_t dev_extra_lds = 0;                                      // dev knob: unused dynamic LDS per block, to limit the resident blocks per CU
     { const char* ev = dev_env("FMGPU_DEV_EXACT_LDS"); if (ev) dev_extra_lds = (size_t)atoi(ev); }
     Index* x = reinterpret_cast<Index*>(h);
@@ -869,7 +872,8 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
     uint64_t total = 0;
     uint32_t shape_max = 0, shape_min = 0;
     bool have_shape = false;                                     // offsets in HBM: total and length range come back in one copy
-    if (is_device_pointer(qoff)) { if ((rc = query_shape((const uint64_t*)soff.dev, nq, stream, &shape_max, &shape_min, &total))) return rc; have_shape = true; }
+    if (shape) { total = shape->total; shape_max = shape->longest; shape_min = shape->shortest; have_shape = true; }
+    else if (is_device_pointer(qoff)) { if ((rc = query_shape((const uint64_t*)soff.dev, nq, stream, &shape_max, &shape_min, &total))) return rc; have_shape = true; }
     else total = qoff[nq];
     if ((rc = sbuf.in(qbuf, q4 ? (total + 1) / 2 : total, stream))) return rc;
     if ((rc = slb.out(out_lb, nq * 8, stream))) return rc;
@@ -1065,6 +1069,30 @@ int fmgpu_search_exact_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t
     UnpackedQueries u;
     if (int rc = unpack_queries(packed, qoff, nq, (hipStream_t)stream, &u)) return rc;
     return search_exact(h, u.qbuf(), u.qoff(), nq, out_lb, out_len, false, stats, stream);
+}
+
+// fmgpu_search_exact / fmgpu_search_exact_q4 for a caller that knows the batch's shape from host offsets (a feed, fmgpu_feed.hip: one call per chunk): every buffer is
+// device memory, qoff[nq] = total, and the longest / shortest read are exactly those of the batch (the kernels size their LDS staging by the longest).  No read-back and,
+// with stats == NULL, no synchronisation — except a packed batch on a handle whose kernel does not read nibbles, which is unpacked as in fmgpu_search_exact_q4.
+int search_exact_shaped(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats, void* stream,
+                        int32_t q4, uint64_t total, uint32_t longest, uint32_t shortest) {
+    Index* x = reinterpret_cast<Index*>(h);
+    if (!x) return fail(FMGPU_ERR_INVALID, "index handle is null");
+    const QueryShapeHint hint{total, longest, shortest};
+    if (!q4) return search_exact(h, qbuf, qoff, nq, out_lb, out_len, false, stats, stream, false, &hint);
+    if (x->bwt.sigma > 15) return fail(FMGPU_ERR_UNSUPPORTED, "4-bit packed queries need sigma <= 15, this index has sigma = " + std::to_string(x->bwt.sigma));
+    if (exact_reads_nibbles(x)) return search_exact(h, qbuf, qoff, nq, out_lb, out_len, false, stats, stream, true, &hint);
+    if (!nq || !qbuf || !qoff || !out_lb || !out_len) return search_exact(h, qbuf, qoff, nq, out_lb, out_len, false, stats, stream);
+    if (int drc = on_handle_device(x)) return drc;
+    UnpackedQueries u;
+    if (int rc = unpack_queries(qbuf, qoff, nq, (hipStream_t)stream, &u)) return rc;
+    return search_exact(h, u.qbuf(), u.qoff(), nq, out_lb, out_len, false, stats, stream, false, &hint);
+}
+int exact_reads_nibbles_on(fmgpu_index_t h, int32_t* yes) {
+    Index* x = reinterpret_cast<Index*>(h);
+    if (!x || !yes) return fail(FMGPU_ERR_INVALID, "index handle is null");
+    *yes = x->bwt.sigma <= 15 && exact_reads_nibbles(x) ? 1 : 0;
+    return 0;
 }
 
 int fmgpu_search_exact_depth(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint32_t* out_depth, void* stream_) {

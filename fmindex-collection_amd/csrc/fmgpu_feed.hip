@@ -1,0 +1,505 @@
+// fmgpu_feed.hip — feeds (include/fmgpu.h: fmgpu_feed_*): a session object bound to one index handle that searches a HOST batch chunk by chunk, with the upload of
+// chunk i + 1 and the download of chunk i - 1 running beside the search of chunk i.  A feed owns pinned staging slots, device slots and three streams (upload, compute,
+// download); the searches themselves are the routed single-handle calls on device pointers (exact search in the form that takes the chunk's shape from the host
+// offsets: no read-back between chunks).  Everything that touches caller memory is host code in fmgpu_feed_host.h.  Nothing here depends on the row width.
+//
+// One chunk, on the calling thread:   wait for the slot (its previous chunk's download) -> scatter that chunk's results -> stage this chunk into the pinned slot (workers)
+//   -> upload stream: H2D offsets + symbols, event U -> compute stream: wait U, search, event C -> download stream: wait C, D2H results, event D.
+// Slot s serves chunks s, s + slots, ...: nothing is uploaded into it before event D of its previous chunk has been waited for on the host, which orders every reuse
+// of its device and pinned buffers; the only stream-to-stream waits are U -> compute and C -> download.
+#include "fmgpu_common.h"
+#include "fmgpu_feed_host.h"
+
+#include <memory>
+
+namespace fmgpu {
+namespace {
+
+namespace fh = fmgpu_feed_host;
+
+constexpr uint64_t kDefaultChunkReads = 1024 * 1024;         // defaults of fmgpu_feed_config (the sweep of tools/feed_probe.py)
+constexpr uint64_t kDefaultChunkSymbols = 128ull << 20;
+constexpr int kMaxSlots = 4;
+
+// 0: pageable (or unknown to the runtime), 1: pinned host memory, 2: device / managed memory
+int pointer_kind(const void* p) {
+    if (!p) return 0;
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof a);
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) return 2;
+    return a.type == hipMemoryTypeHost ? 1 : 0;
+}
+
+struct Grown {            // a buffer that only ever grows: device memory or pinned host memory
+    void* p = nullptr; size_t bytes = 0; bool pinned = false;
+    int need(size_t b, uint64_t* tally) {
+        if (b <= bytes) return 0;
+        release(tally);
+        b = (b + 255) & ~(size_t)255;
+        hipError_t e = pinned ? hipHostMalloc(&p, b, hipHostMallocDefault) : hipMalloc(&p, b);
+        if (e != hipSuccess) { p = nullptr; return hip_fail(e, pinned ? "hipHostMalloc(feed slot)" : "hipMalloc(feed slot)"); }
+        bytes = b; *tally += b;
+        return 0;
+    }
+    void release(uint64_t* tally) {
+        if (!p) return;
+        if (pinned) (void)hipHostFree(p); else (void)hipFree(p);
+        if (tally) *tally -= bytes;
+        p = nullptr; bytes = 0;
+    }
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+struct Slot {
+    Grown d_q, d_off, d_lb, d_len, d_hits;                   // device
+    Grown p_q, p_off, p_lb, p_len, p_hits;                   // pinned
+    hipEvent_t ev_up = nullptr, ev_comp = nullptr, ev_down = nullptr;
+    bool busy = false;                                       // a chunk is in flight: ev_down has been recorded
+    uint64_t first = 0, reads = 0;                           // ... its reads
+    uint64_t hits = 0, produced = 0;                         // ... scheme search: its records and the records of the chunks before it
+    bool hits_in_place = false, results_in_place = false;
+    Slot() { p_q.pinned = p_off.pinned = p_lb.pinned = p_len.pinned = p_hits.pinned = true; }
+};
+
+}  // namespace
+}  // namespace fmgpu
+
+struct fmgpu_feed {
+    uint32_t magic = 0x46454544u;                            // "FEED"
+    fmgpu_index_t h = nullptr;
+    int32_t device = 0, sigma = 0, nibbles = 0;              // nibbles: exact search reads the 4-bit packed form itself on this handle
+    uint64_t chunk_reads = 0, chunk_symbols = 0;
+    int32_t slots = 2, pack4 = 0;
+    std::unique_ptr<fmgpu_feed_host::Workers> workers;
+    hipStream_t up = nullptr, comp = nullptr, down = nullptr;
+    fmgpu::Slot slot[fmgpu::kMaxSlots];
+    std::vector<uint64_t> plan;                              // first read of every chunk of the current call, and nq behind them
+    uint64_t hit_hint = 0;                                   // records the largest chunk so far produced: what a slot's hit buffer is sized for before it runs
+    uint64_t pinned_bytes = 0, device_bytes = 0, last_chunks = 0, last_staged = 0, last_uploaded = 0;
+};
+
+namespace fmgpu {
+namespace {
+
+using Feed = ::fmgpu_feed;
+
+void drain(Feed* f) {
+    for (hipStream_t s : {f->up, f->comp, f->down}) if (s && hipStreamSynchronize(s) != hipSuccess) (void)hipGetLastError();
+    for (int s = 0; s < f->slots; ++s) f->slot[s].busy = false;
+}
+
+int check_feed(Feed* f) {
+    if (!f || f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return fail(FMGPU_ERR_NO_DEVICE, "no HIP device visible — the product path has no CPU fallback"); }
+    if (dev != f->device) return fail(FMGPU_ERR_INVALID, "the handle lives on device " + std::to_string(f->device) + ", the calling thread's current device is " + std::to_string(dev));
+    return 0;
+}
+
+// what one call searches: a flat byte batch, a flat packed batch or scattered reads
+struct Batch {
+    const uint8_t* qbuf = nullptr; const uint64_t* qoff = nullptr;       // flat
+    const uint8_t* const* reads = nullptr; const uint64_t* lens = nullptr; // scattered
+    uint64_t nq = 0;
+    bool q4 = false;                                                     // the caller's batch is packed
+    bool in_pinned = false;                                              // flat: qbuf is pinned memory (copied from where it lies)
+};
+
+// the plan of a call and the largest chunk: every offset is checked (non-decreasing) by the workers, the chunks are then cut by bisection
+int make_plan(Feed* f, const Batch& b, uint64_t* max_reads, uint64_t* max_symbols) {
+    f->plan.clear();
+    uint64_t mr = 0, ms = 0;
+    if (b.qoff) {
+        std::vector<fh::Shape> part(f->workers->parts());
+        f->workers->run([&](uint32_t t, uint32_t parts) { part[t] = fh::shape_of_offsets(b.qoff, fh::slice_cut(b.nq, parts, t), fh::slice_cut(b.nq, parts, t + 1)); });
+        for (const fh::Shape& s : part) if (!s.ok) return fail(FMGPU_ERR_INVALID, "qoff is not non-decreasing");
+        for (uint64_t first = 0; first < b.nq;) {
+            const uint64_t end = fh::chunk_end(b.qoff, b.nq, first, f->chunk_reads, f->chunk_symbols);
+            f->plan.push_back(first);
+            mr = std::max(mr, end - first); ms = std::max(ms, b.qoff[end] - b.qoff[first]);
+            first = end;
+        }
+    } else {                                                             // scattered reads: the same rule over the lengths
+        for (uint64_t first = 0; first < b.nq;) {
+            uint64_t end = first, sym = 0;
+            while (end < b.nq && end - first < f->chunk_reads) {
+                const uint64_t len = b.lens[end];
+                if (end > first && len > f->chunk_symbols - sym) break;  // (sym <= chunk_symbols here: only a chunk's first read may be longer)
+                if (len && !b.reads[end]) return fail(FMGPU_ERR_INVALID, "reads[" + std::to_string(end) + "] is null");
+                sym += len; ++end;
+                if (sym > f->chunk_symbols) break;                       // one over-long read: a chunk of its own
+            }
+            f->plan.push_back(first);
+            mr = std::max(mr, end - first); ms = std::max(ms, sym);
+            first = end;
+        }
+    }
+    f->plan.push_back(b.nq);
+    *max_reads = mr; *max_symbols = ms;
+    return 0;
+}
+
+// every slot sized for the largest chunk of this call (buffers only ever grow)
+int size_slots(Feed* f, uint64_t max_reads, uint64_t max_symbols, bool exact, bool out_pinned, bool in_pinned) {
+    const size_t qbytes = (size_t)max_symbols + 64, obytes = ((size_t)max_reads + 1) * 8, rbytes = (size_t)max_reads * 8;
+    const int used = (int)std::min<uint64_t>((uint64_t)f->slots, f->plan.size() - 1);
+    for (int s = 0; s < used; ++s) {
+        Slot& sl = f->slot[s];
+        int rc;
+        if ((rc = sl.d_q.need(qbytes, &f->device_bytes)) || (rc = sl.d_off.need(obytes, &f->device_bytes)) || (rc = sl.p_off.need(obytes, &f->pinned_bytes))) return rc;
+        if (!in_pinned && (rc = sl.p_q.need(qbytes, &f->pinned_bytes))) return rc;
+        if (exact) {
+            if ((rc = sl.d_lb.need(rbytes, &f->device_bytes)) || (rc = sl.d_len.need(rbytes, &f->device_bytes))) return rc;
+            if (!out_pinned && ((rc = sl.p_lb.need(rbytes, &f->pinned_bytes)) || (rc = sl.p_len.need(rbytes, &f->pinned_bytes)))) return rc;
+        }
+        for (hipEvent_t* ev : {&sl.ev_up, &sl.ev_comp, &sl.ev_down}) if (!*ev) FM_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    }
+    return 0;
+}
+
+// what staging a chunk leaves behind for its search
+struct Staged1 {
+    uint64_t reads = 0, total = 0;
+    uint32_t longest = 0, shortest = 0;
+    const uint8_t* dq = nullptr;          // what the search is handed as qbuf
+    bool nibbles = false;                 // the slot holds nibbles
+};
+
+// stage chunk c into slot sl and enqueue its upload; the slot is free
+int upload_chunk(Feed* f, const Batch& b, Slot& sl, uint64_t c, bool want_nibbles, Staged1* out) {
+    const uint64_t first = f->plan[c], end = f->plan[c + 1], n = end - first;
+    uint64_t* poff = sl.p_off.as<uint64_t>();
+    uint8_t* pq = sl.p_q.as<uint8_t>();
+    uint8_t* dq = sl.d_q.as<uint8_t>();
+    fh::Workers& w = *f->workers;
+    std::vector<fh::Shape> part(w.parts());
+    size_t qbytes = 0, qskip = 0;          // bytes of the slot that travel, from byte qskip on
+    const void* qsrc = nullptr;            // ... and where they lie
+    Staged1 st;
+    st.reads = n;
+    if (b.qoff) {
+        const uint64_t s0 = b.qoff[first], s1 = b.qoff[end], origin = fh::slot_origin(s0), sym = s1 - s0;
+        const bool pack = want_nibbles && !b.q4;
+        st.nibbles = b.q4 || pack;
+        if (b.q4) { qskip = (size_t)((s0 >> 1) - (origin >> 1)); qbytes = (size_t)fh::packed_bytes(s0, s1); }
+        else if (pack) { qskip = (size_t)((s0 - origin) >> 1); qbytes = (size_t)fh::packed_bytes(s0 - origin, s1 - origin); }
+        else { qskip = (size_t)(s0 - origin); qbytes = (size_t)sym; }
+        const bool in_place = b.in_pinned && !pack;
+        w.run([&](uint32_t t, uint32_t parts) {
+            const uint64_t r0 = fh::slice_cut(n, parts, t), r1 = fh::slice_cut(n, parts, t + 1);
+            part[t] = fh::shape_of_offsets(b.qoff, first + r0, first + r1);
+            fh::stage_offsets(b.qoff, first, origin, r0, t + 1 == parts ? n + 1 : r1, poff);
+            if (in_place) return;
+            if (b.q4) fh::stage_packed(b.qbuf, s0, origin, fh::slice_cut(qbytes, parts, t), fh::slice_cut(qbytes, parts, t + 1), pq);
+            else if (pack) fh::pack_nibbles(b.qbuf + s0, fh::slice_cut(sym, parts, t, s0 - origin, 2), fh::slice_cut(sym, parts, t + 1, s0 - origin, 2), (uint32_t)f->sigma, s0 - origin, pq);
+            else fh::stage_bytes(b.qbuf, s0, origin, fh::slice_cut(sym, parts, t), fh::slice_cut(sym, parts, t + 1), pq);
+        });
+        qsrc = in_place ? (const void*)(b.qbuf + (b.q4 ? (s0 >> 1) : s0)) : (const void*)(pq + qskip);
+        if (!in_place) f->last_staged += qbytes;
+    } else {
+        st.nibbles = want_nibbles;
+        fh::stage_lengths(b.lens, first, n, poff);
+        const uint64_t sym = poff[n];
+        const uint64_t align = want_nibbles ? 2 : 1;
+        w.run([&](uint32_t t, uint32_t parts) {
+            part[t] = fh::shape_of_lengths(b.lens, first + fh::slice_cut(n, parts, t), first + fh::slice_cut(n, parts, t + 1));
+            fh::gather_reads(b.reads, first, poff, n, fh::slice_cut(sym, parts, t, 0, align), fh::slice_cut(sym, parts, t + 1, 0, align), want_nibbles ? (uint32_t)f->sigma : 0u, pq);
+        });
+        qbytes = (size_t)(want_nibbles ? (sym + 1) / 2 : sym);
+        qsrc = pq;
+        f->last_staged += qbytes;
+    }
+    fh::Shape shape;
+    for (const fh::Shape& s : part) shape.merge(s);
+    if (shape.longest > 0xffffffffull) return fail(FMGPU_ERR_UNSUPPORTED, "a read of 2^32 symbols or more");
+    st.total = poff[n];                    // the slot's last offset: what the kernels' qoff[nq] is
+    st.longest = (uint32_t)shape.longest; st.shortest = n ? (uint32_t)shape.shortest : 0u;
+    st.dq = dq;
+    if (qskip + qbytes + 32 > sl.d_q.bytes) return fail(FMGPU_ERR_HIP, "feed: a chunk outgrew its slot");
+    FM_HIP(hipMemcpyAsync(sl.d_off.p, poff, (n + 1) * 8, hipMemcpyHostToDevice, f->up));
+    if (qbytes) FM_HIP(hipMemcpyAsync(dq + qskip, qsrc, qbytes, hipMemcpyHostToDevice, f->up));
+    FM_HIP(hipEventRecord(sl.ev_up, f->up));
+    f->last_uploaded += (n + 1) * 8 + qbytes;
+    *out = st;
+    return 0;
+}
+
+// wait for the chunk a slot holds and hand its results to the caller
+int retire_exact(Feed* f, Slot& sl, uint64_t* out_lb, uint64_t* out_len) {
+    if (!sl.busy) return 0;
+    FM_HIP(hipEventSynchronize(sl.ev_down));
+    sl.busy = false;
+    if (sl.results_in_place) return 0;
+    const uint64_t* plb = sl.p_lb.as<uint64_t>(); const uint64_t* pln = sl.p_len.as<uint64_t>();
+    const uint64_t first = sl.first, n = sl.reads;
+    f->workers->run([&](uint32_t t, uint32_t parts) { fh::scatter_intervals(plb, pln, first, fh::slice_cut(n, parts, t), fh::slice_cut(n, parts, t + 1), out_lb, out_len); });
+    f->last_staged += n * 16;
+    return 0;
+}
+int retire_hits(Feed* f, Slot& sl, fmgpu_hit* out, uint64_t capacity) {
+    if (!sl.busy) return 0;
+    FM_HIP(hipEventSynchronize(sl.ev_down));
+    sl.busy = false;
+    if (!sl.hits || sl.produced + sl.hits > capacity) return 0;          // (records beyond the caller's capacity are counted, not written)
+    const fmgpu_hit* src = sl.hits_in_place ? out + sl.produced : sl.p_hits.as<fmgpu_hit>();
+    const uint64_t first = sl.first, n = sl.hits, produced = sl.produced;
+    f->workers->run([&](uint32_t t, uint32_t parts) { fh::scatter_hits(src, fh::slice_cut(n, parts, t), fh::slice_cut(n, parts, t + 1), first, out, produced); });
+    if (!sl.hits_in_place) f->last_staged += n * sizeof(fmgpu_hit);
+    return 0;
+}
+
+void add_stats(fmgpu_stats* sum, const fmgpu_stats& st) {
+    sum->lf_steps += st.lf_steps; sum->hits += st.hits; sum->kernel_ms += st.kernel_ms; sum->prepass_ms += st.prepass_ms;
+    sum->table_bytes += st.table_bytes; sum->table_accesses += st.table_accesses; sum->table_steps += st.table_steps;
+}
+
+int begin_call(Feed* f) {
+    f->last_chunks = f->last_staged = f->last_uploaded = 0;
+    return 0;
+}
+
+int run_exact(Feed* f, const Batch& b, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats) {
+    if (stats) *stats = fmgpu_stats{};
+    begin_call(f);
+    const bool out_pinned = pointer_kind(out_lb) == 1 && pointer_kind(out_len) == 1;
+    const bool want_nibbles = !b.q4 && f->pack4 && f->sigma <= 15 && f->nibbles;
+    uint64_t max_reads = 0, max_symbols = 0;
+    int rc;
+    if ((rc = make_plan(f, b, &max_reads, &max_symbols))) return rc;
+    if ((rc = size_slots(f, max_reads, max_symbols, true, out_pinned, b.in_pinned && !want_nibbles))) return rc;
+    const uint64_t chunks = f->plan.size() - 1;
+    f->last_chunks = chunks;
+    auto body = [&]() -> int {
+        for (uint64_t c = 0; c < chunks; ++c) {
+            Slot& sl = f->slot[c % (uint64_t)f->slots];
+            int r;
+            if ((r = retire_exact(f, sl, out_lb, out_len))) return r;
+            Staged1 st;
+            if ((r = upload_chunk(f, b, sl, c, want_nibbles, &st))) return r;
+            FM_HIP(hipStreamWaitEvent(f->comp, sl.ev_up, 0));
+            fmgpu_stats cs{};
+            if ((r = search_exact_shaped(f->h, st.dq, sl.d_off.as<uint64_t>(), st.reads, sl.d_lb.as<uint64_t>(), sl.d_len.as<uint64_t>(), stats ? &cs : nullptr, f->comp,
+                                         st.nibbles ? 1 : 0, st.total, st.longest, st.shortest))) return r;
+            if (stats) add_stats(stats, cs);
+            FM_HIP(hipEventRecord(sl.ev_comp, f->comp));
+            FM_HIP(hipStreamWaitEvent(f->down, sl.ev_comp, 0));
+            sl.first = f->plan[c]; sl.reads = st.reads; sl.results_in_place = out_pinned;
+            uint64_t* tlb = out_pinned ? out_lb + sl.first : sl.p_lb.as<uint64_t>();
+            uint64_t* tln = out_pinned ? out_len + sl.first : sl.p_len.as<uint64_t>();
+            FM_HIP(hipMemcpyAsync(tlb, sl.d_lb.p, st.reads * 8, hipMemcpyDeviceToHost, f->down));
+            FM_HIP(hipMemcpyAsync(tln, sl.d_len.p, st.reads * 8, hipMemcpyDeviceToHost, f->down));
+            FM_HIP(hipEventRecord(sl.ev_down, f->down));
+            sl.busy = true;
+        }
+        for (uint64_t k = 0; k < (uint64_t)f->slots; ++k) {              // the chunks still in flight, oldest first
+            Slot& sl = f->slot[(chunks + k) % (uint64_t)f->slots];
+            if (int r = retire_exact(f, sl, out_lb, out_len)) return r;
+        }
+        return 0;
+    };
+    rc = body();
+    if (rc) drain(f);
+    return rc;
+}
+
+int run_scheme(Feed* f, const Batch& b, const fmgpu_scheme* scheme, uint64_t max_hits, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats) {
+    if (stats) *stats = fmgpu_stats{};
+    *out_count = 0;
+    begin_call(f);
+    const bool out_pinned = capacity && pointer_kind(out) == 1;
+    uint64_t max_reads = 0, max_symbols = 0;
+    int rc;
+    if ((rc = make_plan(f, b, &max_reads, &max_symbols))) return rc;
+    if ((rc = size_slots(f, max_reads, max_symbols, false, out_pinned, b.in_pinned))) return rc;
+    const uint64_t chunks = f->plan.size() - 1;
+    f->last_chunks = chunks;
+    uint64_t produced = 0;
+    auto body = [&]() -> int {
+        for (uint64_t c = 0; c < chunks; ++c) {
+            Slot& sl = f->slot[c % (uint64_t)f->slots];
+            int r;
+            if ((r = retire_hits(f, sl, out, capacity))) return r;
+            Staged1 st;
+            if ((r = upload_chunk(f, b, sl, c, false, &st))) return r;
+            FM_HIP(hipStreamWaitEvent(f->comp, sl.ev_up, 0));
+            // the slot's hit buffer: two records per read to begin with, what the largest chunk so far produced once one is known; too small for this chunk, it is
+            // grown to the count the search reported and the chunk runs again
+            uint64_t cnt = 0;
+            fmgpu_stats cs{};
+            for (int attempt = 0;; ++attempt) {
+                const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(16, 2 * st.reads), std::max(f->hit_hint, cnt));
+                if ((r = sl.d_hits.need((size_t)want * sizeof(fmgpu_hit), &f->device_bytes))) return r;
+                const uint64_t cap = sl.d_hits.bytes / sizeof(fmgpu_hit);
+                r = ::fmgpu_search_scheme(f->h, st.dq, sl.d_off.as<uint64_t>(), st.reads, scheme, max_hits, sl.d_hits.as<fmgpu_hit>(), cap, &cnt, stats ? &cs : nullptr, f->comp);
+                if (r == FMGPU_ERR_CAPACITY && attempt == 0 && cnt > cap) continue;
+                if (r) return r;
+                break;
+            }
+            f->hit_hint = std::max(f->hit_hint, cnt + cnt / 4);
+            if (stats) add_stats(stats, cs);
+            FM_HIP(hipEventRecord(sl.ev_comp, f->comp));
+            FM_HIP(hipStreamWaitEvent(f->down, sl.ev_comp, 0));
+            sl.first = f->plan[c]; sl.reads = st.reads; sl.hits = cnt; sl.produced = produced;
+            const bool fits = produced + cnt <= capacity;
+            sl.hits_in_place = out_pinned && fits;
+            if (cnt && fits) {
+                fmgpu_hit* target = out + produced;
+                if (!sl.hits_in_place) {
+                    if ((r = sl.p_hits.need((size_t)cnt * sizeof(fmgpu_hit), &f->pinned_bytes))) return r;
+                    target = sl.p_hits.as<fmgpu_hit>();
+                }
+                FM_HIP(hipMemcpyAsync(target, sl.d_hits.p, (size_t)cnt * sizeof(fmgpu_hit), hipMemcpyDeviceToHost, f->down));
+            }
+            FM_HIP(hipEventRecord(sl.ev_down, f->down));
+            sl.busy = true;
+            produced += cnt;
+        }
+        for (uint64_t k = 0; k < (uint64_t)f->slots; ++k) {
+            Slot& sl = f->slot[(chunks + k) % (uint64_t)f->slots];
+            if (int r = retire_hits(f, sl, out, capacity)) return r;
+        }
+        return 0;
+    };
+    rc = body();
+    if (rc) { drain(f); return rc; }
+    *out_count = produced;
+    if (produced > capacity) return fail(FMGPU_ERR_CAPACITY, "result buffer holds " + std::to_string(capacity) + " records, " + std::to_string(produced) + " produced");
+    return 0;
+}
+
+int no_device_memory(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs) if (pointer_kind(p) == 2) return fail(FMGPU_ERR_INVALID, "a feed takes host memory only: an argument is device memory");
+    return 0;
+}
+
+}  // namespace
+}  // namespace fmgpu
+
+using namespace fmgpu;
+
+extern "C" {
+
+int fmgpu_feed_plan(const uint64_t* qoff, uint64_t nq, uint64_t chunk_reads, uint64_t chunk_symbols, uint64_t* out_first, uint64_t capacity, uint64_t* out_chunks) {
+    const int rc = fmgpu_feed_host::plan(qoff, nq, chunk_reads, chunk_symbols, out_first, capacity, out_chunks);
+    if (rc == FMGPU_ERR_INVALID) return fail(rc, !out_chunks || (nq && !qoff) || (capacity && !out_first) ? "qoff / out_first / out_chunks is null"
+                                                 : (!chunk_reads || !chunk_symbols) ? "chunk_reads and chunk_symbols must be at least 1" : "qoff is not non-decreasing");
+    if (rc == FMGPU_ERR_CAPACITY) return fail(rc, "out_first holds " + std::to_string(capacity) + " chunks, the batch has " + std::to_string(*out_chunks));
+    return rc;
+}
+
+int fmgpu_feed_create(fmgpu_index_t h, const fmgpu_feed_config* cfg, fmgpu_feed_t* out) {
+    if (!out) return fail(FMGPU_ERR_INVALID, "out is null");
+    *out = nullptr;
+    int32_t device = 0;
+    if (int rc = handle_device(h, &device)) return rc;
+    fmgpu_feed_config c{};
+    if (cfg) c = *cfg;
+    if (c.slots == 0) c.slots = 2;
+    if (c.host_threads == 0) c.host_threads = 4;
+    if (c.slots < 2 || c.slots > kMaxSlots) return fail(FMGPU_ERR_INVALID, "fmgpu_feed_config: slots must be 0 or 2 .. 4");
+    if (c.host_threads < 1 || c.host_threads > 16) return fail(FMGPU_ERR_INVALID, "fmgpu_feed_config: host_threads must be 0 or 1 .. 16");
+    if (c.reserved != 0) return fail(FMGPU_ERR_INVALID, "fmgpu_feed_config: reserved must be 0");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return fail(FMGPU_ERR_NO_DEVICE, "no HIP device visible — the product path has no CPU fallback"); }
+    if (dev != device) return fail(FMGPU_ERR_INVALID, "the handle lives on device " + std::to_string(device) + ", the calling thread's current device is " + std::to_string(dev));
+    std::unique_ptr<fmgpu_feed> f(new (std::nothrow) fmgpu_feed);
+    if (!f) return fail(FMGPU_ERR_NOMEM, "out of host memory");
+    f->h = h; f->device = device;
+    f->chunk_reads = c.chunk_reads ? c.chunk_reads : kDefaultChunkReads;
+    f->chunk_symbols = c.chunk_symbols ? c.chunk_symbols : kDefaultChunkSymbols;
+    if (f->chunk_reads > 0x7fffffffull) f->chunk_reads = 0x7fffffffull;                  // (a launch covers fewer than 2^32 threads)
+    f->slots = c.slots; f->pack4 = c.pack4 != 0;
+    if (int rc = ::fmgpu_index_info(h, nullptr, &f->sigma, nullptr, nullptr, nullptr)) return rc;
+    if (int rc = exact_reads_nibbles_on(h, &f->nibbles)) return rc;
+    try { f->workers.reset(new fmgpu_feed_host::Workers((uint32_t)c.host_threads)); }
+    catch (const std::exception& e) { return fail(FMGPU_ERR_NOMEM, std::string("feed: cannot start the host threads: ") + e.what()); }
+    for (hipStream_t* s : {&f->up, &f->comp, &f->down}) {
+        hipError_t e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+        if (e != hipSuccess) { *s = nullptr; const int rc = hip_fail(e, "hipStreamCreateWithFlags(feed)"); fmgpu_feed_destroy(f.release()); return rc; }
+    }
+    *out = f.release();
+    return 0;
+}
+
+int fmgpu_feed_destroy(fmgpu_feed_t f) {
+    if (!f) return 0;
+    if (f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is not a feed of this library");
+    drain(f);
+    for (Slot& sl : f->slot) {
+        for (Grown* g : {&sl.d_q, &sl.d_off, &sl.d_lb, &sl.d_len, &sl.d_hits, &sl.p_q, &sl.p_off, &sl.p_lb, &sl.p_len, &sl.p_hits}) g->release(nullptr);
+        for (hipEvent_t ev : {sl.ev_up, sl.ev_comp, sl.ev_down}) if (ev) (void)hipEventDestroy(ev);
+    }
+    for (hipStream_t s : {f->up, f->comp, f->down}) if (s) (void)hipStreamDestroy(s);
+    f->magic = 0;
+    delete f;
+    return 0;
+}
+
+int fmgpu_feed_info(fmgpu_feed_t f, uint64_t* pinned_bytes, uint64_t* device_bytes, uint64_t* last_chunks, uint64_t* last_staged_bytes, uint64_t* last_uploaded_bytes) {
+    if (!f || f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    if (pinned_bytes) *pinned_bytes = f->pinned_bytes;
+    if (device_bytes) *device_bytes = f->device_bytes;
+    if (last_chunks) *last_chunks = f->last_chunks;
+    if (last_staged_bytes) *last_staged_bytes = f->last_staged;
+    if (last_uploaded_bytes) *last_uploaded_bytes = f->last_uploaded;
+    return 0;
+}
+
+static int feed_exact(fmgpu_feed_t f, Batch b, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats) {
+    if (stats) *stats = fmgpu_stats{};
+    if (b.nq == 0) return 0;                                                              // (before the feed is looked at)
+    if (!f || f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    if (b.q4 && f->sigma > 15) return fail(FMGPU_ERR_UNSUPPORTED, "4-bit packed queries need sigma <= 15, this index has sigma = " + std::to_string(f->sigma));
+    if (b.reads ? (!b.lens || !out_lb || !out_len) : (!b.qbuf || !b.qoff || !out_lb || !out_len))
+        return fail(FMGPU_ERR_INVALID, b.reads || b.lens ? "reads / lens / out_lb / out_len is null" : "qbuf / qoff / out_lb / out_len is null");
+    if (int rc = check_feed(f)) return rc;
+    if (int rc = no_device_memory({b.qbuf, b.qoff, b.reads, b.lens, out_lb, out_len})) return rc;
+    if (b.reads) if (int rc = no_device_memory({b.reads[0]})) return rc;                  // (looked at only once the array itself is known to be host memory)
+    b.in_pinned = b.qbuf && pointer_kind(b.qbuf) == 1;
+    return run_exact(f, b, out_lb, out_len, stats);
+}
+
+int fmgpu_feed_search_exact(fmgpu_feed_t f, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats) {
+    Batch b; b.qbuf = qbuf; b.qoff = qoff; b.nq = nq;
+    return feed_exact(f, b, out_lb, out_len, stats);
+}
+int fmgpu_feed_search_exact_q4(fmgpu_feed_t f, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats) {
+    Batch b; b.qbuf = packed; b.qoff = qoff; b.nq = nq; b.q4 = true;
+    return feed_exact(f, b, out_lb, out_len, stats);
+}
+int fmgpu_feed_search_exact_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t* lens, uint64_t nq, uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats) {
+    if (nq && !reads) return (f && f->magic == 0x46454544u) ? fail(FMGPU_ERR_INVALID, "reads / lens / out_lb / out_len is null") : fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    Batch b; b.reads = reads; b.lens = lens; b.nq = nq;
+    return feed_exact(f, b, out_lb, out_len, stats);
+}
+
+static int feed_scheme(fmgpu_feed_t f, Batch b, const fmgpu_scheme* scheme, uint64_t max_hits, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats) {
+    if (stats) *stats = fmgpu_stats{};
+    if (out_count) *out_count = 0;
+    if (b.nq == 0) return 0;
+    if (!f || f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    if ((b.reads ? !b.lens : (!b.qbuf || !b.qoff)) || (!out && capacity) || !out_count)
+        return fail(FMGPU_ERR_INVALID, b.reads || b.lens ? "reads / lens / out / out_count is null" : "qbuf / qoff / out / out_count is null");
+    if (int rc = check_feed(f)) return rc;
+    if (int rc = check_scheme(f->h, scheme, max_hits)) return rc;
+    if (max_hits == 0 || scheme->n_searches == 0) return 0;                               // (the one-shot call's own answer: nothing to search)
+    if (int rc = no_device_memory({b.qbuf, b.qoff, b.reads, b.lens, out, out_count})) return rc;
+    if (b.reads) if (int rc = no_device_memory({b.reads[0]})) return rc;
+    b.in_pinned = b.qbuf && pointer_kind(b.qbuf) == 1;
+    return run_scheme(f, b, scheme, max_hits, out, capacity, out_count, stats);
+}
+
+int fmgpu_feed_search_scheme(fmgpu_feed_t f, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* scheme, uint64_t max_hits_per_query,
+                             fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats) {
+    Batch b; b.qbuf = qbuf; b.qoff = qoff; b.nq = nq;
+    return feed_scheme(f, b, scheme, max_hits_per_query, out, capacity, out_count, stats);
+}
+int fmgpu_feed_search_scheme_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t* lens, uint64_t nq, const fmgpu_scheme* scheme, uint64_t max_hits_per_query,
+                               fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats) {
+    if (nq && !reads) return (f && f->magic == 0x46454544u) ? fail(FMGPU_ERR_INVALID, "reads / lens / out / out_count is null") : fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    Batch b; b.reads = reads; b.lens = lens; b.nq = nq;
+    return feed_scheme(f, b, scheme, max_hits_per_query, out, capacity, out_count, stats);
+}
+
+}  // extern "C"

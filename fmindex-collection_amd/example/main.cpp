@@ -12,6 +12,8 @@
 //   * locating is one batched call over all rows of all cursors (the rows and their order are the reference's);
 //   * --packed (not in the reference): the reads are packed once, 4 bits per symbol, and searched in that form (the `_q4` entry points); the reverse
 //     complements are made on the device while packing (fmgpu_queries_pack4) instead of on the host.  The output is the same, byte for byte.
+//   * --feed (not in the reference): `noerror` and `ng26` (mode all) search through an fmc::Feed — the reads go to the device chunk by chunk, upload, search and
+//     download overlapped, the Sequences object is not flattened; with --packed the packed batch goes through the feed.  The output is the same, byte for byte.
 #include "../../include/fmc_gpu.hpp"
 
 #include <algorithm>
@@ -42,7 +44,7 @@ struct Options {
     bool schemeDyn = false;
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false;
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -82,6 +84,7 @@ FlagRule const kFlags[] = {
     {"--convertUnknownChar", false, [](Options& o, char const*) { o.unknownToA = true; }},
     {"--help", false, [](Options& o, char const*) { o.wantHelp = true; }},
     {"--packed", false, [](Options& o, char const*) { o.packed = true; }},
+    {"--feed", false, [](Options& o, char const*) { o.feed = true; }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
     {"--ext", true, [](Options&, char const*) {}},
     {"--threads", true, [](Options&, char const*) {}},
@@ -248,10 +251,12 @@ struct Run {
         };
         switch (kind) {
         case Algorithm::noerror:
-            fmc::search_no_errors::search(index, reads, [&](size_t read, auto const& cursor) { collect(read, cursor, 0); });
+            if (config.feed) fmc::Feed{index}.search_no_errors(reads, [&](size_t read, auto const& cursor) { collect(read, cursor, 0); });
+            else fmc::search_no_errors::search(index, reads, [&](size_t read, auto const& cursor) { collect(read, cursor, 0); });
             break;
         case Algorithm::ng26: {
-            if (config.hitMode == HitMode::all) fmc::search_ng26::search<true>(index, reads, schemeByName(config.schemeName, 0, k), {}, collect, perRead);
+            if (config.hitMode == HitMode::all && config.feed) fmc::Feed{index}.search_ng26<true>(reads, schemeByName(config.schemeName, 0, k), {}, collect, perRead);
+            else if (config.hitMode == HitMode::all) fmc::search_ng26::search<true>(index, reads, schemeByName(config.schemeName, 0, k), {}, collect, perRead);
             else fmc::search_ng26::search_best<true>(index, reads, schemesUpTo([&](size_t j) {
                      return std::tuple<fmc::search_scheme::Scheme, std::vector<size_t>>{schemeByName(config.schemeName, j, j), {}}; }), collect, perRead);
             break;
@@ -331,6 +336,7 @@ int main(int argc, char const* const* argv) try {
                     "          --no-reverse (don't use reverse compliment)\\\n"
                     "          --mode [all, besthits] (all: all hits with k errors (default), besthits: all hits with the lowest hit)\\\n"
                     "          --packed (search the reads in the 4-bit packed form; reverse complements are made on the device)\\\n"
+                    "          --feed (noerror, ng26: search through a feed, chunk by chunk with upload, search and download overlapped)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }

@@ -986,6 +986,94 @@ struct Search {
 };
 template <typename I, typename Q, typename D> Search(I const&, Q const&, bool, size_t, std::optional<size_t>, D const&) -> Search<I, Q, D>;
 
+// A feed (include/fmgpu.h: fmgpu_feed_*): host batches searched chunk by chunk on one index, upload, search and download overlapped.  What a caller that holds its
+// queries in host memory — the reference's Sequences — should search through: `fmc::Feed feed{index}; feed.search_no_errors(queries, delegate);`.  A Sequences object
+// (reads of one-byte symbols, each contiguous) goes down through the `_v` calls without being flattened, a PackedQueries through `_q4`.  The delegates are called as by
+// the free functions of the same names, which stay as they are.  One feed serves one call at a time; the index must outlive it.
+template <typename Index>
+struct Feed {
+    fmgpu_feed_t handle{nullptr};
+    Index const* index{nullptr};
+    explicit Feed(Index const& idx, fmgpu_feed_config const& config = {}) : index{&idx} { detail::check(fmgpu_feed_create(idx.handle, &config, &handle)); }
+    Feed(Feed const&) = delete;
+    Feed& operator=(Feed const&) = delete;
+    Feed(Feed&& o) noexcept : handle{o.handle}, index{o.index} { o.handle = nullptr; }
+    ~Feed() { if (handle) fmgpu_feed_destroy(handle); }
+
+    struct Info { uint64_t pinnedBytes, deviceBytes, lastChunks, lastStagedBytes, lastUploadedBytes; };
+    auto info() const -> Info {
+        Info i{};
+        detail::check(fmgpu_feed_info(handle, &i.pinnedBytes, &i.deviceBytes, &i.lastChunks, &i.lastStagedBytes, &i.lastUploadedBytes));
+        return i;
+    }
+
+    // search_no_errors::search(index, queries, delegate(qidx, cursor)): only non-empty cursors are reported
+    template <typename Queries, typename Delegate>
+    void search_no_errors(Queries const& queries, Delegate&& delegate) const {
+        std::vector<uint8_t const*> reads; std::vector<uint64_t> lens;
+        scattered(queries, reads, lens);
+        size_t nq = reads.size();
+        std::vector<uint64_t> lb(nq), len(nq);
+        detail::check(fmgpu_feed_search_exact_v(handle, reads.data(), lens.data(), nq, lb.data(), len.data(), nullptr));
+        reportExact(lb, len, delegate);
+    }
+    template <typename Delegate>
+    void search_no_errors(PackedQueries const& queries, Delegate&& delegate) const {
+        size_t nq = queries.size();
+        std::vector<uint64_t> lb(nq), len(nq);
+        detail::check(fmgpu_feed_search_exact_q4(handle, queries.packed.data(), queries.qoff.data(), nq, lb.data(), len.data(), nullptr));
+        reportExact(lb, len, delegate);
+    }
+    // search_ng26::search<Edit>(index, queries, scheme, partition, delegate(qidx, cursor, errors), n)
+    template <bool Edit = true, typename Queries, typename Delegate>
+    void search_ng26(Queries const& queries, search_scheme::Scheme const& scheme, std::vector<size_t> const& partition, Delegate&& delegate,
+                     size_t n = std::numeric_limits<size_t>::max()) const {
+        std::vector<uint8_t const*> reads; std::vector<uint64_t> lens;
+        scattered(queries, reads, lens);
+        size_t nq = reads.size();
+        if (scheme.empty() || nq == 0 || n == 0) return;
+        size_t P = scheme[0].pi.size();
+        std::vector<uint64_t> pi, l, u, part(partition.begin(), partition.end());
+        for (auto const& s : scheme) {
+            if (s.pi.size() != P) throw std::runtime_error("fmindex-collection (gpu): searches of a scheme must have the same number of parts");
+            pi.insert(pi.end(), s.pi.begin(), s.pi.end()); l.insert(l.end(), s.l.begin(), s.l.end()); u.insert(u.end(), s.u.begin(), s.u.end());
+        }
+        fmgpu_scheme sc{static_cast<int32_t>(scheme.size()), static_cast<int32_t>(P), pi.data(), l.data(), u.data(), part.empty() ? nullptr : part.data(), Edit ? 1 : 0, 0};
+        auto hits = detail::run_hits(nq, [&](fmgpu_hit* out, uint64_t cap, uint64_t* count) {
+            return fmgpu_feed_search_scheme_v(handle, reads.data(), lens.data(), nq, &sc, n, out, cap, count, nullptr);
+        });
+        detail::report(*index, hits, delegate);
+    }
+    // (the scheme kernels read bytes: a packed batch is unpacked on the host first)
+    template <bool Edit = true, typename Delegate>
+    void search_ng26(PackedQueries const& queries, search_scheme::Scheme const& scheme, std::vector<size_t> const& partition, Delegate&& delegate,
+                     size_t n = std::numeric_limits<size_t>::max()) const {
+        search_ng26<Edit>(queries.unpack(), scheme, partition, std::forward<Delegate>(delegate), n);
+    }
+
+  private:
+    template <typename Queries>
+    static void scattered(Queries const& queries, std::vector<uint8_t const*>& reads, std::vector<uint64_t>& lens) {
+        for (auto const& q : queries) {
+            static_assert(sizeof(*q.data()) == 1, "a feed takes reads of one-byte symbols, each contiguous in memory");
+            reads.push_back(reinterpret_cast<uint8_t const*>(q.data()));
+            lens.push_back(q.size());
+        }
+    }
+    template <typename Delegate>
+    void reportExact(std::vector<uint64_t> const& lb, std::vector<uint64_t> const& len, Delegate&& delegate) const {
+        using cursor_t = select_cursor_t<Index>;
+        for (size_t q = 0; q < lb.size(); ++q) {
+            if (len[q] == 0) continue;
+            cursor_t cur{};
+            cur.index = index; cur.lb = lb[q]; cur.len = len[q];
+            delegate(q, cur);
+        }
+    }
+};
+template <typename Index> Feed(Index const&) -> Feed<Index>;
+template <typename Index> Feed(Index const&, fmgpu_feed_config const&) -> Feed<Index>;
+
 // Library options (include/fmgpu.h: fmgpu_option) — what a new handle is given, which of several result-identical kernels serves a call; the library reads no
 // environment variable.  setOption(FMGPU_OPT_LF_TABLE, 0) before an index is made keeps it the plain configuration (occurrence tables + sampled suffix array).
 inline void setOption(fmgpu_option option, int64_t value) { detail::check(fmgpu_set_option(static_cast<int32_t>(option), value)); }

@@ -565,9 +565,84 @@ int fmgpu_replicas_search_ng21(fmgpu_replicas_t r, const uint8_t* qbuf, const ui
                                fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats);
 int fmgpu_replicas_locate(fmgpu_replicas_t r, const uint64_t* rows, uint64_t count, uint64_t* out_seq, uint64_t* out_pos, uint64_t* out_steps, fmgpu_stats* stats);
 
-/* device memory helpers for callers that keep queries / results resident in HBM */
+/* ---- feeds: chunked, overlapped search of HOST query batches ----------------------------------------------------------------------------
+ * The one-shot calls above stage a host batch whole: one allocation, one copy from pageable memory, the kernel, one copy back, nothing overlapped.  A feed is a session
+ * object bound to one index handle that owns pinned staging slots, device slots and three streams (upload, compute, download) and searches a host batch chunk by
+ * chunk: chunk i + 1 is staged and uploaded and chunk i - 1 is downloaded while chunk i is being searched.  What search_no_errors::search and search_ng26::search are
+ * handed in the reference is host memory (a Sequences object): this is the path such a caller takes.
+ *   - Results: out_lb / out_len of fmgpu_feed_search_exact / _q4 equal, element for element, what fmgpu_search_exact / _q4 returns for the same batch on the same
+ *     handle.  The hit records of fmgpu_feed_search_scheme equal, after fmgpu_hits_sort, those of fmgpu_search_scheme after fmgpu_hits_sort, field for field; qidx is the
+ *     read's number in the caller's batch.  The `_v` forms (scattered reads: reads[q] points at lens[q] symbols) give the results of the flat forms on the flattened batch.
+ *   - Scheme order and count: before sorting, the records of chunk c come before those of chunk c + 1.  *out_count is the batch's total, on success and on
+ *     FMGPU_ERR_CAPACITY alike; every chunk still runs, as the one-shot call runs its whole kernel; on FMGPU_ERR_CAPACITY the contents of `out` are unspecified.
+ *     A slot's device hit buffer that is too small for its chunk is grown and that chunk is run again: the caller never sees this.
+ *   - Chunks: fmgpu_feed_plan defines them and the search calls use exactly its rule.  A chunk is the longest run of consecutive reads with at most chunk_reads reads
+ *     and at most chunk_symbols symbols; it always holds at least one read, so a read longer than chunk_symbols is a chunk of its own.  out_first gets chunks + 1
+ *     entries (room for capacity + 1; it may be NULL with capacity == 0), the last one is nq; *out_chunks is always set; more chunks than `capacity` return
+ *     FMGPU_ERR_CAPACITY; a limit of 0 or a decreasing qoff returns FMGPU_ERR_INVALID.  fmgpu_feed_plan is pure host code and needs no device.
+ *   - Defaults of the limits: chunk_reads = 1 048 576, chunk_symbols = 128 Mi (134 217 728): 101 bp reads make chunks of 114 MB in and 16 MB out, ten of them in a
+ *     batch of 10 M reads — the best of the sweep in DESIGN 4.11 (64 Ki, 256 Ki and 1 Mi reads with 1, 4 and 16 host threads).  slots = 2, host_threads = 4;
+ *     host_threads is never derived from the machine's CPU count.
+ *   - Buffer sizes: the slots are sized for the call's largest chunk when the call starts and only ever grow (fmgpu_feed_info: pinned_bytes, device_bytes).
+ *   - Host memory only: a device pointer in any argument returns FMGPU_ERR_INVALID (the rule of fmgpu_replicas_*; of a `_v` batch the two arrays and reads[0] are looked at).
+ *   - Pinned host memory (fmgpu_malloc_host, hipHostMalloc, a pinned torch tensor; recognised with hipPointerGetAttributes): pinned symbols are copied from where they
+ *     lie and pinned outputs are written in place (hit records are renumbered there).  last_staged_bytes counts the bytes of symbols, intervals and hit records that
+ *     crossed a pinned slot, so nothing for those; the chunk's offsets (8 bytes per read) are always rewritten chunk-relative into the slot and are not counted.
+ *     last_uploaded_bytes counts every byte copied to the device (offsets and symbols), last_chunks the chunks of the last call.
+ *   - Offsets: qoff[0] need not be 0.  For `_q4` it may be odd and a chunk may start on an odd symbol: the chunk copies bytes qoff[first] >> 1 .. (qoff[end] + 1) >> 1
+ *     and its device offsets keep the parity.  Device query buffers are 16-byte aligned and padded by 16 bytes; a chunk sits in its slot from symbol qoff[first] & ~31
+ *     on, so every symbol keeps its place inside the aligned words and 16-byte pieces the readers load.
+ *   - pack4: a byte batch is written into the pinned slot as nibbles (a byte >= sigma becomes 15) and searched with the `_q4` kernel, whose results the section above
+ *     guarantees identical, when pack4 != 0, the handle has sigma <= 15 and exact search reads nibbles itself on the handle (the pair table with or without the interval
+ *     table in front, the one-symbol blocks).  In every other case the bytes travel as they are.  Packing is host work: pinned symbols are then packed through the
+ *     slot like pageable ones.  fmgpu_feed_search_scheme never packs.
+ *   - stats: lf_steps, hits, table_*, kernel_ms and prepass_ms are the sums over the chunks.  A non-NULL stats of an exact call costs overlap: each chunk reads its
+ *     counters back and so waits for its kernel before the next chunk is staged.
+ *   - Threading: only the calling thread makes HIP calls; the host_threads workers (the calling thread is one of them) only copy or pack between caller memory and
+ *     pinned slots, each on its own slice.  All chunk searches of a call run on ONE compute stream owned by the feed (the library's per-thread call scratch serves one
+ *     call at a time: kernels of two chunks are never in flight on two streams); upload and download have a stream each, tied to it with events: three streams and no
+ *     more, four queues with the side stream of exact search.  One feed serves one call at a time; two feeds on two host threads may use one handle concurrently.  A
+ *     feed lives on the device of its handle: calls on it must be made with that device current.
+ *   - An exact call with stats == NULL does not synchronise with the host between its chunks other than to wait for a slot: the shape of each chunk (symbols, longest
+ *     and shortest read) is taken from the host offsets instead of a read-back.  (A `_q4` batch on a handle whose exact kernel does not read nibbles is unpacked per
+ *     chunk as in fmgpu_search_exact_q4, which synchronises; scheme chunks read their record count back, as the one-shot call does.)
+ *   - Errors: codes and messages for a null handle (fmgpu_feed_create), null pointers, a bad scheme, a unidirectional handle and sigma > 15 for `_q4` are those of the
+ *     one-shot calls.  nq == 0 returns 0 and touches nothing.  A failing HIP call stops the enqueuing, drains the three streams and returns its code; the feed can
+ *     still be destroyed afterwards.
+ * Not served through a feed: search_ng21, best-stratum search, backtracking, smems, locate; feeds over replicas. */
+typedef struct fmgpu_feed* fmgpu_feed_t;
+typedef struct fmgpu_feed_config {
+    uint64_t chunk_reads;    /* 0 = default */
+    uint64_t chunk_symbols;  /* 0 = default */
+    int32_t  slots;          /* 0 = 2; 2 .. 4 */
+    int32_t  host_threads;   /* 0 = 4; 1 .. 16; never derived from the machine's CPU count */
+    int32_t  pack4;          /* != 0: byte batches travel as nibbles where that is exact (above) */
+    int32_t  reserved;       /* 0 */
+} fmgpu_feed_config;
+int fmgpu_feed_create(fmgpu_index_t h, const fmgpu_feed_config* cfg /* NULL = defaults */, fmgpu_feed_t* out);
+int fmgpu_feed_destroy(fmgpu_feed_t f);
+int fmgpu_feed_plan(const uint64_t* qoff, uint64_t nq, uint64_t chunk_reads, uint64_t chunk_symbols,
+                    uint64_t* out_first, uint64_t capacity, uint64_t* out_chunks);
+int fmgpu_feed_search_exact   (fmgpu_feed_t f, const uint8_t* qbuf,   const uint64_t* qoff, uint64_t nq,
+                               uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats);
+int fmgpu_feed_search_exact_q4(fmgpu_feed_t f, const uint8_t* packed, const uint64_t* qoff, uint64_t nq,
+                               uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats);
+int fmgpu_feed_search_exact_v (fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t* lens, uint64_t nq,
+                               uint64_t* out_lb, uint64_t* out_len, fmgpu_stats* stats);
+int fmgpu_feed_search_scheme  (fmgpu_feed_t f, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                               const fmgpu_scheme* scheme, uint64_t max_hits_per_query,
+                               fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats);
+int fmgpu_feed_search_scheme_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t* lens, uint64_t nq,
+                               const fmgpu_scheme* scheme, uint64_t max_hits_per_query,
+                               fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats);
+int fmgpu_feed_info(fmgpu_feed_t f, uint64_t* pinned_bytes, uint64_t* device_bytes,
+                    uint64_t* last_chunks, uint64_t* last_staged_bytes, uint64_t* last_uploaded_bytes);
+
+/* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
 int fmgpu_free(void* ptr);
+int fmgpu_malloc_host(void** ptr, uint64_t bytes);
+int fmgpu_free_host(void* ptr);
 int fmgpu_memcpy_h2d(void* dst, const void* src, uint64_t bytes);
 int fmgpu_memcpy_d2h(void* dst, const void* src, uint64_t bytes);
 int fmgpu_synchronize(void* stream);
