@@ -17,7 +17,7 @@ from . import capi
 from .capi import FmgpuError, DeviceBuffer, PinnedBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE
 from . import search_scheme  # noqa: F401
 
-__all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "LocateLinear", "search_locate", "reconstruct_text",
+__all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer"]
 
@@ -647,6 +647,84 @@ class search_ng26:
         call = _q4(queries, capi.lib().fmgpu_search_scheme, capi.lib().fmgpu_search_scheme_q4)
         hits, st = _run_hits(lambda out, c, cnt, st: call(
             index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(sc), n, capi.ptr(out), c, C.byref(cnt), C.byref(st), None), cap)
+        return (hits, st) if want_stats else hits
+
+
+class ScoringMatrix:
+    """search_hamming_sm::ScoringMatrix<QuerySigma, RefSigma> (search/SearchHammingSM.h:16-45) as the two mask arrays of fmgpu_scoring_matrix: bit r of free_mask[c] = text
+    rank r matches query rank c at no cost, bit r of cost_mask[c] = the pairing costs one error; neither = not pairable.  Default-constructed like the reference's: identity
+    free, every other pair of ranks 1.. at cost 1 (rank 0, the delimiter, pairs with nothing).  The search walks the members of a mask in ascending rank."""
+
+    def __init__(self, query_sigma, ref_sigma=None):
+        ref_sigma = query_sigma if ref_sigma is None else ref_sigma
+        if not (1 <= query_sigma <= 256 and 1 <= ref_sigma <= 32):
+            raise ValueError("ScoringMatrix: query_sigma in 1..256, ref_sigma in 1..32")
+        self.query_sigma, self.ref_sigma = int(query_sigma), int(ref_sigma)
+        self.free_mask = np.zeros(self.query_sigma, dtype=np.uint32)
+        self.cost_mask = np.zeros(self.query_sigma, dtype=np.uint32)
+        for y in range(1, self.ref_sigma):
+            for x in range(1, self.query_sigma):
+                self.set_cost(x, y, 0 if x == y else 1)
+
+    def set_cost(self, query_rank, ref_rank, cost):
+        """setCost: cost 0 = a free match, 1 = a mismatch that costs one error"""
+        if cost not in (0, 1):
+            raise ValueError("ScoringMatrix.set_cost: cost is 0 or 1")
+        self.set_unpairable(query_rank, ref_rank)
+        (self.cost_mask if cost else self.free_mask)[query_rank] |= np.uint32(1 << ref_rank)
+        return self
+
+    def set_unpairable(self, query_rank, ref_rank=None):
+        """query_rank pairs with ref_rank (or, None, with any rank) neither for free nor at a cost"""
+        if not 0 <= query_rank < self.query_sigma or (ref_rank is not None and not 0 <= ref_rank < self.ref_sigma):
+            raise ValueError("ScoringMatrix: rank out of range")
+        keep = np.uint32(0) if ref_rank is None else np.uint32(~(1 << ref_rank) & 0xffffffff)
+        self.free_mask[query_rank] &= keep
+        self.cost_mask[query_rank] &= keep
+        return self
+
+    # ranks 5..15 of iupac_dna() and the bases (ranks 1..4 = A C G T) each stands for
+    IUPAC = {"R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC", "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}
+
+    @classmethod
+    def iupac_dna(cls):
+        """query ranks 1..4 = A C G T, 5..15 = R Y S W K M B D H V N on a sigma = 5 index: every code is free for its bases and costs one error for the others"""
+        sm = cls(16, 5)
+        for k, bases in enumerate(cls.IUPAC.values()):
+            for r, base in enumerate("ACGT", start=1):
+                sm.set_cost(5 + k, r, 0 if base in bases else 1)
+        return sm
+
+    def _struct(self):
+        m = capi.ScoringMatrix()
+        m.query_sigma, m.reserved = self.query_sigma, 0
+        m.free_mask = self.free_mask.ctypes.data_as(C.POINTER(C.c_uint32))
+        m.cost_mask = self.cost_mask.ctypes.data_as(C.POINTER(C.c_uint32))
+        m._masks = (self.free_mask, self.cost_mask)                  # (the struct keeps the arrays it points into alive)
+        return m
+
+
+class search_hamming_sm:
+    """search/SearchHammingSM.h: the search-scheme Hamming walk with a scoring matrix (fmgpu_search_hamming_sm)"""
+
+    @staticmethod
+    def search(index, queries, scheme, matrix, partition=None, n=UINT64_MAX, capacity=None, want_stats=False):
+        """scheme = (pi, l, u) arrays [searches][parts]; matrix = a ScoringMatrix; `queries` in the byte form (a list of sequences or (qbuf, qoff)): query symbols may be
+        any byte below matrix.query_sigma.  Returns the hit records in the reference's callback order."""
+        if isinstance(queries, PackedQueries):
+            raise TypeError("search_hamming_sm takes the byte form of a batch (4-bit packed batches are not served)")
+        qbuf, qoff, nq = _queries(queries)
+        pi, l, u = (_u64(x) for x in scheme)
+        sc = capi.Scheme()
+        sc.n_searches, sc.n_parts = pi.shape
+        sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
+        part = _u64(partition) if partition is not None else None
+        sc.partition = part.ctypes.data_as(capi.u64p) if part is not None else None
+        sc.edit = 0
+        sm = matrix._struct()
+        cap = capacity if capacity is not None else max(1024, 4 * nq)
+        hits, st = _run_hits(lambda out, c, cnt, st: capi.lib().fmgpu_search_hamming_sm(
+            index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(sc), C.byref(sm), n, capi.ptr(out), c, C.byref(cnt), C.byref(st), None), cap)
         return (hits, st) if want_stats else hits
 
 

@@ -109,6 +109,11 @@ class ExpandedScheme(C.Structure):
     _fields_ = [("n_searches", C.c_int32), ("reserved", C.c_int32), ("length", C.c_uint64), ("pi", u64p), ("l", u64p), ("u", u64p)]
 
 
+class ScoringMatrix(C.Structure):
+    """fmgpu_scoring_matrix: per query symbol, the text symbols it matches for free and at the cost of one error (fmgpu_search_hamming_sm); host memory"""
+    _fields_ = [("query_sigma", C.c_int32), ("reserved", C.c_int32), ("free_mask", C.POINTER(C.c_uint32)), ("cost_mask", C.POINTER(C.c_uint32))]
+
+
 class Stats(C.Structure):
     _fields_ = [("lf_steps", C.c_uint64), ("hits", C.c_uint64), ("kernel_ms", C.c_float), ("prepass_ms", C.c_float),
                 ("table_bytes", C.c_uint64), ("table_accesses", C.c_uint64), ("table_steps", C.c_uint64)]
@@ -136,7 +141,7 @@ EXPORTS = [
     "fmgpu_index_accelerate_extract", "fmgpu_sequence_lengths", "fmgpu_extract",
     "fmgpu_queries_pack4", "fmgpu_queries_unpack4", "fmgpu_search_exact_q4", "fmgpu_search_scheme_q4", "fmgpu_search_ng21_q4",
     "fmgpu_search_best", "fmgpu_search_best_ng21", "fmgpu_search_best_q4", "fmgpu_search_best_ng21_q4",
-    "fmgpu_search_smems", "fmgpu_search_smems_q4",
+    "fmgpu_search_smems", "fmgpu_search_smems_q4", "fmgpu_search_hamming_sm",
     "fmgpu_feed_create", "fmgpu_feed_destroy", "fmgpu_feed_plan", "fmgpu_feed_search_exact", "fmgpu_feed_search_exact_q4", "fmgpu_feed_search_exact_v",
     "fmgpu_feed_search_scheme", "fmgpu_feed_search_scheme_v", "fmgpu_feed_info", "fmgpu_malloc_host", "fmgpu_free_host",
 ]
@@ -262,6 +267,8 @@ def lib():
     L.fmgpu_search_smems.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64,
                                      C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(Stats), C.c_void_p]
     L.fmgpu_search_smems_q4.argtypes = L.fmgpu_search_smems.argtypes
+    L.fmgpu_search_hamming_sm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Scheme), C.POINTER(ScoringMatrix), C.c_uint64,
+                                          C.c_void_p, C.c_uint64, u64p, C.POINTER(Stats), C.c_void_p]
     if hasattr(L, "fmgpu_feed_create"):                       # (FMGPU_LIBRARY may name an older build of the same ABI: tools/feed_probe.py times one)
         L.fmgpu_feed_create.argtypes = [C.c_void_p, C.POINTER(FeedConfig), C.POINTER(C.c_void_p)]
         L.fmgpu_feed_destroy.argtypes = [C.c_void_p]

@@ -285,6 +285,11 @@ int fmgpu_search_scheme(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
                         fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
     ROUTE(h, fmgpu_search_scheme(h, qbuf, qoff, nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream));
 }
+int fmgpu_search_hamming_sm(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* scheme, const fmgpu_scoring_matrix* matrix,
+                            uint64_t max_hits_per_query, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
+    if (nq == 0) { if (out_count) *out_count = 0; if (stats) *stats = fmgpu_stats{}; return 0; }      // (before the handle is looked at)
+    ROUTE(h, fmgpu_search_hamming_sm(h, qbuf, qoff, nq, scheme, matrix, max_hits_per_query, out, capacity, out_count, stats, stream));
+}
 int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_expanded_scheme* scheme, uint64_t max_hits_per_query,
                       fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream) {
     ROUTE(h, fmgpu_search_ng21(h, qbuf, qoff, nq, scheme, max_hits_per_query, out, capacity, out_count, stats, stream));

@@ -5,7 +5,7 @@
 //  k_scheme_fast_edit  search_ng26::search<Edit=true>, the same frame with the insertion / deletion branches (:146-218, :286-362); top frame in LDS (write-back)
 //  k_scheme, k_scheme_edit, k_ng21   the general forms (ragged small batches, explicit partitions, every layout, search_ng21): flat state machines
 //  k_backtracking      search_backtracking::search         (search/Backtracking.h:42-102)
-//  (exact search: fmgpu_exact.hip; locate: fmgpu_locate.hip; what they share: fmgpu_search_shared.h)
+//  (exact search: fmgpu_exact.hip; locate: fmgpu_locate.hip; Hamming search with a scoring matrix: fmgpu_search_sm.hip; what they share: fmgpu_search_shared.h)
 //
 // The general DFS kernels are flat state machines: every loop iteration performs exactly one memory phase per lane (the occurrence-table
 // blocks at both interval ends, Occ::all2, or one LF-table load for a one-row cursor) followed by register-only control logic.  Pending
@@ -2468,193 +2468,12 @@ __global__ __launch_bounds__(256) void k_heavy_flags(const uint4* __restrict__ l
     const uint64_t m = __ballot(heavy);
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(count, (uint32_t)__popcll(m));
 }
-// the same question without tables: the interval of the read's last 16 symbols by backward search on the blocks (16 of the ~500 nodes a read visits)
-template <class Occ>
-__global__ __launch_bounds__(256) void k_heavy_flags_plain(Occ occ, idx_t n, const uint8_t* __restrict__ qbuf, const uint64_t* __restrict__ qoff, uint64_t nq, uint32_t m,
-                                                           uint32_t threshold, uint8_t* __restrict__ flags, uint32_t* __restrict__ count) {   // m = 0: every read has its own length
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool heavy = false;
-    if (q < nq) {
-        const uint64_t o = qoff[q];
-        const uint32_t len_q = m ? m : (uint32_t)(qoff[q + 1] - o);
-        const uint8_t* s = qbuf + o;
-        idx_t lb = 0, len = len_q >= 16u ? n : (idx_t)0;
-        const uint32_t sigma = occ.sigma();
-        for (uint32_t t = 0; t < 16u && len != 0; ++t) {
-            const uint32_t c = s[len_q - 1u - t];
-            if (c < 1 || c >= sigma) { len = 0; break; }
-            idx_t ra, rb;
-            occ.lf2(lb, lb + len, c, ra, rb);
-            lb = ra; len = rb - ra;
-        }
-        heavy = len > threshold;
-        flags[q] = heavy ? 1 : 0;
-    }
-    const uint64_t mk = __ballot(heavy);
-    if ((threadIdx.x & 63u) == 0 && mk) atomicAdd(count, (uint32_t)__popcll(mk));
-}
-// rows of the 16-symbol interval above which a read counts as one of a high-copy repeat (genome-like text, plain index / with tables:
-// > 2 rows 157.8 / 115.7 ms, > 8: 155.8 / 111.5, > 64: 151.3 / 111.1, > 1000: 157.1 / 114.6)
-constexpr uint32_t kHeavyInterval = 64;
-static uint32_t heavy_rows() { const char* e = dev_env("FMGPU_DEV_HEAVY_ROWS"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : kHeavyInterval; }   // (dev knob)
 
 __global__ __launch_bounds__(256) void k_len_pairs(const uint64_t* __restrict__ qoff, uint64_t nq, uint32_t* __restrict__ len, uint32_t* __restrict__ idx) {
     uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q < nq) { len[q] = (uint32_t)(qoff[q + 1] - qoff[q]); idx[q] = (uint32_t)q; }
 }
 
-constexpr size_t kFrameCache = (size_t)2 << 30;
-constexpr uint32_t kDfsSlots = 8;            // launches of a ragged batch that run side by side at most (CallScratch holds that many streams)
-struct DfsWorkspace {
-    uint64_t* planes = nullptr; Counters* ctr = nullptr; StackView view{};
-    unsigned grid = 0;
-    bool own_planes = false;
-    // blocks_per_cu: resident 256-lane blocks of the kernel that will run (the lanes walk the batch with a static stride, so
-    // every block must be resident from the start or the late ones form a tail).
-    // The frame stacks (~1 GB for a full-chip launch over 101-symbol reads) stay with the calling host thread between calls: allocating and
-    // freeing them per call costs ~0.2 ms (hipFree synchronises the device), 2-3 % of a 10 M-read k = 2 call.
-    WorkBoard* board = nullptr;                                    // (with_board) sharing between the waves of a launch
-    // slots > 1 (a ragged batch: one launch per read length): that many launches run side by side, each on a stream, a share of the grid, a stretch of the frame stacks, a hand-out counter
-    // and a board of its own — `grid` is then ONE launch's grid, `view` the first launch's stretch
-    uint32_t slots = 1;
-    CallScratch* scratch = nullptr;
-    size_t slot_bytes = 0;                                         // bytes of the frame stacks per concurrent launch
-    // with_board: every resident block is launched however small the batch — a block without reads of its own waits at the board for subtrees of the heavy reads
-    int init(uint32_t depth, uint64_t nq, int blocks_per_cu, hipStream_t stream, int nplanes = 3, bool with_board = false, uint32_t want_slots = 1) {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        uint64_t want = (uint64_t)cus * (uint64_t)std::max(1, std::min(8, blocks_per_cu));
-        slots = std::max(1u, std::min(kDfsSlots, want_slots));
-        if (slots > 1) want = std::max<uint64_t>(1, want / slots);
-        grid = (unsigned)std::max<uint64_t>(1, with_board ? want : std::min<uint64_t>(want, (nq + 255) / 256));
-        view.nlanes = (uint64_t)grid * 256; view.depth = depth;
-        uint64_t words = view.nlanes * ((uint64_t)depth + 1) * slots;
-        const size_t need = words * 8 * (size_t)nplanes;
-        CallScratch* sc = nullptr;
-        int rc = call_scratch(&sc); if (rc) return rc;
-        if (need <= kFrameCache) {
-            if (sc->frames_bytes < need) {
-                if (sc->frames) { (void)hipFree(sc->frames); sc->frames = nullptr; sc->frames_bytes = 0; }
-                FM_HIP(hipMalloc(&sc->frames, need));
-                sc->frames_bytes = need;
-            }
-            planes = (uint64_t*)sc->frames;
-        } else {
-            FM_HIP(hipMalloc((void**)&planes, need));
-            own_planes = true;
-        }
-        view.p0 = planes; view.p1 = planes + words; view.p2 = planes + 2 * words; view.p3 = nplanes > 3 ? planes + 3 * words : nullptr;
-        slot_bytes = (need / slots) & ~(size_t)15;
-        scratch = sc;
-        ctr = (Counters*)sc->dfs_ctr;
-        FM_HIP(hipMemsetAsync(ctr, 0, 256, stream));                         // next: the query hand-out counter of the scheme kernels (+ a debug area)
-        if (with_board) {
-            if (sc->board_slots < slots) {
-                if (sc->board) { (void)hipFree(sc->board); sc->board = nullptr; sc->board_slots = 0; }
-                FM_HIP(hipMalloc(&sc->board, sizeof(WorkBoard) * slots));
-                sc->board_slots = slots;
-            }
-            board = (WorkBoard*)sc->board;
-        }
-        if (slots > 1) {
-            for (uint32_t k = 0; k < slots; ++k) if (!sc->dfs_streams[k]) FM_HIP(hipStreamCreateWithFlags(&sc->dfs_streams[k], hipStreamNonBlocking));
-            for (uint32_t k = 0; k <= slots; ++k) if (!sc->dfs_events[k]) FM_HIP(hipEventCreateWithFlags(&sc->dfs_events[k], hipEventDisableTiming));
-        }
-        return 0;
-    }
-    // what the k-th concurrent launch works with
-    hipStream_t stream_of(uint32_t k, hipStream_t caller) const { return slots > 1 ? scratch->dfs_streams[k] : caller; }
-    unsigned long long* next_of(uint32_t k) const { return slots > 1 ? reinterpret_cast<unsigned long long*>(ctr) + 24 + k : &ctr->next; }      // (the hand-out counters of side-by-side launches: words 24..31 of the counter area)
-    WorkBoard* board_of(uint32_t k) const { return board ? board + (slots > 1 ? k : 0) : nullptr; }
-    StackView view_of(uint32_t k) const {                          // (the fast kernels address their frames from p0 alone: a stretch of the whole area per launch)
-        StackView v = view;
-        v.p0 = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(planes) + (size_t)k * slot_bytes);
-        return v;
-    }
-    // side-by-side launches start after everything the caller's stream holds, and the caller's stream goes on after all of them
-    int fork(hipStream_t caller) {
-        if (slots <= 1) return 0;
-        FM_HIP(hipEventRecord(scratch->dfs_events[slots], caller));
-        for (uint32_t k = 0; k < slots; ++k) FM_HIP(hipStreamWaitEvent(scratch->dfs_streams[k], scratch->dfs_events[slots], 0));
-        forked = true;
-        return 0;
-    }
-    int join(hipStream_t caller) {
-        if (slots <= 1) return 0;
-        for (uint32_t k = 0; k < slots; ++k) { FM_HIP(hipEventRecord(scratch->dfs_events[k], scratch->dfs_streams[k])); FM_HIP(hipStreamWaitEvent(caller, scratch->dfs_events[k], 0)); }
-        forked = false;
-        return 0;
-    }
-    int reset_board(hipStream_t stream, uint32_t k = 0) {          // before every launch that uses it (k: which of the side-by-side launches)
-        if (!board) return 0;
-        WorkBoard* const board = board_of(k);
-        FM_HIP(hipMemsetAsync(board, 0, kBoardResetBytes, stream));
-        uint32_t cfg[3] = {kBoardHeavy, kBoardPeriod, kBoardWaiters};
-        if (const char* e = dev_env("FMGPU_DEV_BOARD_HEAVY")) cfg[0] = (uint32_t)atoi(e);
-        if (const char* e = dev_env("FMGPU_DEV_BOARD_PERIOD")) { cfg[1] = 1; while (cfg[1] * 2 <= (uint32_t)std::max(1, atoi(e))) cfg[1] *= 2; }      // (a power of two: the kernels test pass & (period - 1))
-        if (const char* e = dev_env("FMGPU_DEV_BOARD_WAITERS")) cfg[2] = (uint32_t)std::max(1, atoi(e));
-        FM_HIP(hipMemsetD32Async((hipDeviceptr_t)&board->heavy, (int)cfg[0], 1, stream));      // (fills, not copies: no host buffer has to outlive the call)
-        FM_HIP(hipMemsetD32Async((hipDeviceptr_t)&board->period, (int)cfg[1], 1, stream));
-        FM_HIP(hipMemsetD32Async((hipDeviceptr_t)&board->waiters, (int)cfg[2], 1, stream));
-        return 0;
-    }
-    // after the launch has been synchronised: a waiting wave that gave up means results may be missing
-    int check_board() {
-        if (!board) return 0;
-        unsigned long long f = 0;
-        for (uint32_t k = 0; k < slots; ++k) { unsigned long long fk = 0; FM_HIP(hipMemcpy(&fk, &board_of(k)->failed, 8, hipMemcpyDeviceToHost)); f += fk; }
-        if (dev_env("FMGPU_DEV_BOARD_LOG")) {                        // (development build: what went over the board in the last launch)
-            unsigned long long v[2] = {0, 0}, t = 0;
-            (void)hipMemcpy(&v[0], &board->ht, 8, hipMemcpyDeviceToHost); (void)hipMemcpy(&t, &board->tasks, 8, hipMemcpyDeviceToHost);
-            unsigned long long d[7] = {0}; uint32_t tries = 0;
-            (void)hipMemcpy(d, &board->dev[0], sizeof d, hipMemcpyDeviceToHost); (void)hipMemcpy(&tries, &board->cas_tries, 4, hipMemcpyDeviceToHost);
-            const double clk = 2.4e3;                              // (s_memtime counts the shader clock here: ~2.4 GHz — cycles per microsecond)
-            fprintf(stderr, "board: %llu batches asked for, %llu published, %llu subtrees, %u compare-and-swaps; wave-time: waiting %.1f %% (%llu waits), giving %.2f %% (%llu, %.1f us each), looking %.2f %% (%llu, %.1f us each)\n",
-                    v[0] >> 32, v[0] & 0xffffffffull, t, tries, d[6] ? 100.0 * d[0] / d[6] : 0.0, d[3], d[6] ? 100.0 * d[1] / d[6] : 0.0, d[4], d[4] ? d[1] / (double)d[4] / clk : 0.0,
-                    d[6] ? 100.0 * d[2] / d[6] : 0.0, d[5], d[5] ? d[2] / (double)d[5] / clk : 0.0);
-        }
-        return f ? fail(FMGPU_ERR_HIP, "work sharing between waves: " + std::to_string(f) + " waiting wave(s) gave up") : 0;
-    }
-    bool forked = false;                                           // side-by-side launches are out and have not been joined
-    ~DfsWorkspace() {
-        if (forked) for (uint32_t k = 0; k < slots; ++k) (void)hipStreamSynchronize(scratch->dfs_streams[k]);      // (an error path left between fork and join: nothing of this call may outlive it)
-        if (planes && own_planes) (void)hipFree(planes);
-    }
-};
-
-// the hand-out order of a batch with the reads of high-copy repeats in front (see k_heavy_flags): flag_pass(count, flags, counter) launches the
-// flag kernel over the first `count` reads.  A 64 k sample decides whether the pass over the whole batch is worth it; *out_order stays null if not.
-// The buffers live in the calling thread's scratch (the order is valid until the thread's next search call).
-template <class FlagPass>
-static int heavy_first_order(uint64_t nq, hipStream_t stream, FlagPass&& flag_pass, uint32_t** out_order) {
-    *out_order = nullptr;
-    CallScratch* sc = nullptr;
-    int rc = call_scratch(&sc); if (rc) return rc;
-    size_t tb = 0;
-    (void)hipcub::DevicePartition::Flagged(nullptr, tb, hipcub::CountingInputIterator<uint32_t>(0u), (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nq, stream);
-    const size_t off_flags = (nq * 4 + 255) / 256 * 256, off_cnt = off_flags + (nq + 255) / 256 * 256, off_tmp = off_cnt + 256;
-    const size_t need = off_tmp + std::max<size_t>(tb, 16);
-    if (sc->order_bytes < need) {
-        if (sc->order) { (void)hipFree(sc->order); sc->order = nullptr; sc->order_bytes = 0; }
-        FM_HIP(hipMalloc(&sc->order, need));
-        sc->order_bytes = need;
-    }
-    uint8_t* base = (uint8_t*)sc->order;
-    uint32_t* order = (uint32_t*)base; uint8_t* flags = base + off_flags; uint32_t* cnt = (uint32_t*)(base + off_cnt);
-    const uint64_t ns = std::min<uint64_t>(nq, 1u << 16);
-    FM_HIP(hipMemsetAsync(cnt, 0, 8, stream));
-    flag_pass(ns, flags, cnt);
-    FM_LAUNCHED("k_heavy_flags");
-    uint32_t heavy = 0;
-    FM_HIP(hipMemcpyAsync(&heavy, cnt, 4, hipMemcpyDeviceToHost, stream));
-    FM_HIP(hipStreamSynchronize(stream));
-    if ((uint64_t)heavy * 2000u < ns) return 0;                     // < 0.05 % of the sample: nothing worth moving
-    if (nq > ns) { flag_pass(nq, flags, cnt); FM_LAUNCHED("k_heavy_flags"); }
-    FM_HIP(hipcub::DevicePartition::Flagged(base + off_tmp, tb, hipcub::CountingInputIterator<uint32_t>(0u), flags, order, cnt + 1, (int)nq, stream));
-    *out_order = order;
-    return 0;
-}
 
 namespace api {
 #include "fmgpu_api_decl.h"
@@ -2691,40 +2510,6 @@ static void launch_lean(const Index* x, const uint32_t* d_steps, uint32_t S, uin
     if (board) launch(k_scheme_lean<kLeanWaves, kLeanSteps, false, false, true>); else launch(k_scheme_lean<kLeanWaves, kLeanSteps, false>);
 }
 
-// a caller's search_ng26 scheme checked and flattened into the kernels' form; `nothing`: the search reports nothing whatever the batch (SearchNg26.h:408-409)
-static int parse_scheme(const Index* x, const fmgpu_scheme* scheme, uint64_t max_hits, SchemeDev& sd, uint32_t& max_u, bool& nothing) {
-    nothing = false;
-    if (!x->bidirectional) return fail(FMGPU_ERR_INVALID, "search_ng26 needs a BiFMIndex (bwt_rev)");
-    if (!scheme || !scheme->pi || !scheme->l || !scheme->u) return fail(FMGPU_ERR_INVALID, "scheme is null");
-    if (scheme->n_searches < 0 || scheme->n_searches > kMaxSearches || scheme->n_parts < 1 || scheme->n_parts > kMaxParts)
-        return fail(FMGPU_ERR_UNSUPPORTED, "scheme larger than 16 searches x 16 parts");
-    if (max_hits == 0 || scheme->n_searches == 0) { nothing = true; return 0; }
-    sd.S = scheme->n_searches; sd.P = scheme->n_parts; sd.uniform = scheme->partition ? 0 : 1;
-    sd.dev_flags = kernel_flags();
-    sd.use_key = 0; sd.sharing = 0;                              // set by the launcher for the general Hamming kernel
-    for (int s = 0; s < sd.S; ++s) {
-        uint32_t seen = 0;
-        for (int p = 0; p < sd.P; ++p) {
-            uint64_t pi = scheme->pi[s * sd.P + p], l = scheme->l[s * sd.P + p], u = scheme->u[s * sd.P + p];
-            if (pi >= (uint64_t)sd.P || l > 255 || u > 254) return fail(FMGPU_ERR_INVALID, "scheme entry out of range");
-            seen |= 1u << pi; max_u = std::max<uint32_t>(max_u, (uint32_t)u);
-            sd.pi[s * kMaxParts + p] = (uint8_t)pi; sd.l[s * kMaxParts + p] = (uint8_t)l; sd.u[s * kMaxParts + p] = (uint8_t)u;
-        }
-        if (seen != (1u << sd.P) - 1u) return fail(FMGPU_ERR_INVALID, "scheme pi is not a permutation of the parts");
-        // connectivity (search_scheme/isValid.h:18-33): the kernel's cursor only grows at its two ends
-        uint32_t lo = sd.pi[s * kMaxParts], hi = lo;
-        for (int p = 1; p < sd.P; ++p) {
-            uint32_t v = sd.pi[s * kMaxParts + p];
-            if (v == hi + 1) hi = v; else if (v + 1 == lo) lo = v; else return fail(FMGPU_ERR_INVALID, "scheme pi is not contiguous");
-        }
-    }
-    if (scheme->partition) for (int p = 0; p < sd.P; ++p) {
-        if (scheme->partition[p] == 0 || scheme->partition[p] > 0xffffu) return fail(FMGPU_ERR_INVALID, "partition entries must be in [1, 65535]");
-        sd.partition[p] = (uint32_t)scheme->partition[p];
-        sd.psum += sd.partition[p];
-    }
-    return 0;
-}
 
 static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* scheme,
                    uint64_t max_hits, uint32_t K, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, hipStream_t stream) {

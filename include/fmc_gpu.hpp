@@ -4,7 +4,7 @@
 // (fmindex/FMIndexCursor.h, fmindex/BiFMIndexCursor.h: lb, lbRev, len, steps, count(), empty(), begin/end, extendLeft / extendRight with and
 // without a symbol, symbolLeft / symbolRight), single_locate_step, fmc::Search{...}(),
 // search_no_errors::search (search/SearchNoErrors.h), search_backtracking::search (search/Backtracking.h),
-// search_ng26::search (search/SearchNg26.h:426-444), fmc::search<Edit> (search/search.h:26-35), LocateLinear (locate.h:14-57),
+// search_ng26::search (search/SearchNg26.h:426-444), search_hamming_sm::{ScoringMatrix, search} (search/SearchHammingSM.h), fmc::search<Edit> (search/search.h:26-35), LocateLinear (locate.h:14-57),
 // search_scheme::{Search, Scheme, generator::{h2, pigeon_opt, pigeon_trivial, backtracking}, createUniformPartition, expand,
 // limitToHamming, isValid, isComplete} (search_scheme/).
 //
@@ -785,6 +785,65 @@ void search_best(Index const& index, Queries const& queries, size_t maxErrors, D
         search<Edit>(index, queries, i, [&](size_t qidx, auto cursor, size_t e) { if (cursor.count() == 0) return; found = true; delegate(qidx, cursor, e); }, n);
 }
 }  // namespace search_ng26
+
+// search/SearchHammingSM.h: the search-scheme Hamming walk with a scoring matrix (fmgpu_search_hamming_sm).  Every (query rank, text rank) pair is a free match,
+// a mismatch that costs one error, or not pairable; the query alphabet may be larger than the index's.
+namespace search_hamming_sm {
+// ScoringMatrix<QuerySigma, RefSigma> (:16-45) as the two mask arrays of fmgpu_scoring_matrix.  Default-constructed like the reference's: identity free, every other
+// pair of ranks 1.. at cost 1.  The search walks the members of a mask in ascending rank, which is the reference's list order when setCost is called in ascending
+// refRank per query rank (its default constructor and its test do so).
+template <size_t QuerySigma, size_t RefSigma = QuerySigma>
+struct ScoringMatrix {
+    static_assert(QuerySigma >= 1 && QuerySigma <= 256 && RefSigma >= 1 && RefSigma <= 32, "query ranks 0 .. 255 have a row; the masks are one word");
+    std::array<uint32_t, QuerySigma> freeMask{}, costMask{};
+
+    ScoringMatrix() {
+        for (size_t y{1}; y < RefSigma; ++y)
+            for (size_t x{1}; x < QuerySigma; ++x) setCost(x, y, x == y ? 0 : 1);
+    }
+    void setCost(size_t queryRank, size_t refRank, size_t cost) {   // cost 0 or 1
+        if (queryRank >= QuerySigma || refRank >= RefSigma || cost > 1) throw std::runtime_error("fmindex-collection (gpu): ScoringMatrix::setCost out of range");
+        setUnpairable(queryRank, refRank);
+        (cost ? costMask : freeMask)[queryRank] |= uint32_t{1} << refRank;
+    }
+    void setUnpairable(size_t queryRank, size_t refRank) {
+        freeMask.at(queryRank) &= ~(uint32_t{1} << refRank);
+        costMask.at(queryRank) &= ~(uint32_t{1} << refRank);
+    }
+    auto raw() const -> fmgpu_scoring_matrix { return {static_cast<int32_t>(QuerySigma), 0, freeMask.data(), costMask.data()}; }
+};
+// query ranks 1..4 = A C G T, 5..15 = R Y S W K M B D H V N on a sigma = 5 index: every code is free for its bases and costs one error for the others
+inline auto iupacDna() -> ScoringMatrix<16, 5> {
+    ScoringMatrix<16, 5> sm;
+    char const* bases[11] = {"AG", "CT", "CG", "AT", "GT", "AC", "CGT", "AGT", "ACT", "ACG", "ACGT"};
+    for (size_t k = 0; k < 11; ++k)
+        for (size_t r = 1; r <= 4; ++r) sm.setCost(5 + k, r, std::string(bases[k]).find("ACGT"[r - 1]) != std::string::npos ? 0 : 1);
+    return sm;
+}
+
+// search(index, queries, scheme, sm, delegate(qidx, cursor, errors)[, n]) — :199-212, with the `n` of search_ng26 (n results per query at most).  The parts are
+// createUniformPartition(scheme parts, query length); a query shorter than the scheme has parts reports nothing.
+template <typename Index, typename Queries, typename SM, typename Delegate>
+void search(Index const& index, Queries const& queries, search_scheme::Scheme const& scheme, SM const& sm, Delegate&& delegate,
+            size_t n = std::numeric_limits<size_t>::max()) {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    size_t nq = off.size() - 1;
+    if (scheme.empty() || nq == 0 || n == 0) return;
+    size_t P = scheme[0].pi.size();
+    std::vector<uint64_t> pi, l, u;
+    for (auto const& s : scheme) {
+        if (s.pi.size() != P) throw std::runtime_error("fmindex-collection (gpu): searches of a scheme must have the same number of parts");
+        pi.insert(pi.end(), s.pi.begin(), s.pi.end()); l.insert(l.end(), s.l.begin(), s.l.end()); u.insert(u.end(), s.u.begin(), s.u.end());
+    }
+    fmgpu_scheme sc{static_cast<int32_t>(scheme.size()), static_cast<int32_t>(P), pi.data(), l.data(), u.data(), nullptr, 0, 0};
+    fmgpu_scoring_matrix m = sm.raw();
+    auto hits = detail::run_hits(nq, [&](fmgpu_hit* out, uint64_t cap, uint64_t* count) {
+        return fmgpu_search_hamming_sm(index.handle, buf.data(), off.data(), nq, &sc, &m, n, out, cap, count, nullptr, nullptr);
+    });
+    detail::report(index, hits, delegate);
+}
+}  // namespace search_hamming_sm
 
 // search/SearchNg21.h: edit-distance search over an EXPANDED scheme (search_scheme::expand(scheme, query length): one {pi, l, u} entry per
 // query symbol), so the queries of a call have that length; shorter ones — which the reference would read out of bounds — report nothing.

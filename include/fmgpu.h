@@ -403,6 +403,43 @@ int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff
                       const fmgpu_expanded_scheme* scheme, uint64_t max_hits_per_query,
                       fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream);
 
+/* ---- Hamming search with a scoring matrix ---------------------------------------------------------------------------------------------------
+ * search_hamming_sm::search(index, queries, scheme, ScoringMatrix<QuerySigma, RefSigma>, delegate) (search/SearchHammingSM.h:188-212): the search-scheme Hamming
+ * walk in which every (query symbol, text symbol) pair is a free match, a mismatch that costs one error, or not pairable.  The query alphabet may be larger than
+ * the index's: a DNA read with N, an IUPAC primer on a sigma = 5 index, a 28-letter protein query alphabet on 21 ranks.  BiFMIndex only, sigma <= 32.
+ *   - Matrix (host memory): query bytes 0 .. query_sigma - 1 have a row; bit r of free_mask[c] = text symbol r matches query symbol c at no cost, bit r of
+ *     cost_mask[c] = the pairing costs one error.  A query byte >= query_sigma, or one whose two masks are empty, pairs with nothing.  The library treats no symbol
+ *     specially: the delimiter 0 is pairable exactly where a mask says so.
+ *   - The walk: one pass per search s of the scheme, in order.  Part lengths are createUniformPartition(P, m), or scheme->partition if given; a read of another
+ *     total length is skipped, as in fmgpu_search_scheme.  A state is (cursor, e, part p, symbols left in the part); the part is consumed rightwards if p == 0 or
+ *     pi[p-1] < pi[p], else leftwards.  At a state with symbols left, c = the next query symbol, F = the members of free_mask[c], K = those of cost_mask[c], both in
+ *     ascending symbol order.  If e + 1 <= u[p] the children are the cursor extended by every r in F with e unchanged, then by every r in K with e + 1; if
+ *     e + 1 > u[p], only the children of F.  Empty children are dropped.  A part that is used up continues into part p + 1 iff l[p] <= e; a new part is entered only
+ *     if e <= u[p]; after the last part the cursor is reported iff l[P-1] <= e <= u[P-1].
+ *   - A read with m < P produces nothing (the rule of fmgpu_search_scheme; the reference would walk empty parts).  Reads of up to 65534 symbols.
+ *   - Deviation: the reference keeps noCostList / costList in the order of the setCost calls; this call walks ascending symbols, which is the reference's order when
+ *     setCost is called in ascending refRank per query rank (its default constructor and its test do so).
+ *   - Records: {qidx, lb, lb_rev, len, errors = e, seq = position of the report within its read in the depth-first order above}: fmgpu_hits_sort returns the
+ *     reference's callback order, and the records go into fmgpu_locate_hits as they are.
+ *   - max_hits_per_query = n as for fmgpu_search_scheme: the last cursor of a read is clipped to what is left of n, the read's remaining searches are skipped once n
+ *     is reached, 0 produces nothing.  *out_count = the records produced, on success and on FMGPU_ERR_CAPACITY alike.
+ *   - stats: lf_steps = the extensions the reference executes — one per state expanded over all symbols (e + 1 <= u[p]), |F| per state expanded in matches-only
+ *     mode, empty results included; hits = records; kernel_ms = the search kernel alone; table_bytes / table_accesses as fmgpu_search_scheme's general kernel counts.
+ *   - FMGPU_ERR_INVALID: a unidirectional handle (the message of fmgpu_search_scheme); scheme->edit != 0; a null matrix or mask array; query_sigma outside 1 .. 256; a
+ *     mask bit >= sigma; a query symbol whose two masks overlap.  FMGPU_ERR_UNSUPPORTED: sigma > 32 (the masks are one word).  A bad scheme: the codes of
+ *     fmgpu_search_scheme.  nq == 0 returns 0 before the handle is looked at.
+ *   - qbuf / qoff / out may each be host or device memory; qoff[0] need not be 0.  The call returns after completion.
+ *   - Not served: `_q4` batches, feeds, replicas, the best-stratum ladder, and work sharing between lanes or waves (a lane walks its read alone). */
+typedef struct fmgpu_scoring_matrix {
+    int32_t query_sigma;        /* 1 .. 256: query bytes 0 .. query_sigma-1 have a row */
+    int32_t reserved;           /* 0 */
+    const uint32_t* free_mask;  /* query_sigma words: bit r set = text symbol r matches this query symbol at no cost */
+    const uint32_t* cost_mask;  /* query_sigma words: bit r set = pairing with text symbol r costs one error */
+} fmgpu_scoring_matrix;         /* host memory */
+int fmgpu_search_hamming_sm(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                            const fmgpu_scheme* scheme, const fmgpu_scoring_matrix* matrix, uint64_t max_hits_per_query,
+                            fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream);
+
 /* Best-stratum search: a ladder of schemes walked over one batch in one call — what search_ng26::search_best with an explicit scheme list
  * (search/SearchNg26.h:447-469) and search_ng21::search_best / search_best_n (search/SearchNg21.h:242-293) cut per read, cut per batch on the device.
  * Marking the found reads, selecting and compacting the others and renaming qidx are device passes; neither the queries nor the found set come back to the host
