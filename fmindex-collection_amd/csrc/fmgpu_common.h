@@ -147,7 +147,9 @@ inline const char* dev_env(const char* name) {
     (void)name; return nullptr;
 #endif
 }
-// bits of FMGPU_OPT_KERNEL_SELECT (FMGPU_SEL_* in include/fmgpu.h); a DEV build ORs the non-selection bits of FMGPU_DEV_FLAGS in (1 = count hits only, ...)
+// bits of FMGPU_OPT_KERNEL_SELECT (FMGPU_SEL_* in include/fmgpu.h); a DEV build ORs the non-selection bits of FMGPU_DEV_FLAGS in (kDevCountOnly, ...).
+// A search call reads them once, at its entry point, and passes the value down: a concurrent fmgpu_set_option cannot hand one call two configurations.
+constexpr int kDevCountOnly = 1 << 0;         // the one bit outside FMGPU_SEL_ALL that the launchers' word carries by name: the kernels count hits and write no records
 inline int kernel_flags() {
     int f = (int)opt(FMGPU_OPT_KERNEL_SELECT) & FMGPU_SEL_ALL;
 #ifdef FMGPU_DEV

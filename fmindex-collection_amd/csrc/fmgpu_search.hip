@@ -2484,21 +2484,21 @@ int fmgpu_hits_sort(fmgpu_hit* hits, uint64_t count, void* stream);
 static size_t lean_lds_bytes(uint32_t m, size_t step_words) {
     return (size_t)((m + 15) / 16) * 1024 + 8192 + step_words * 4 + 16 + (size_t)4 * kRingWords * kRingCap * 4;      // staged reads | top and bottom frame slots | steps | ring fill | rings
 }
-static void launch_lean(const Index* x, const uint32_t* d_steps, uint32_t S, uint32_t m, size_t step_words, dim3 g, const uint8_t* dq, const uint64_t* doff, uint64_t count,
-                        fmgpu_hit* dout, uint64_t capacity, const DfsWorkspace& ws, const uint32_t* qm, hipStream_t stream, uint32_t lut_ok = 0, uint32_t slot = 0) {
+static void launch_lean(const Index* x, int flags, const uint32_t* d_steps, uint32_t S, uint32_t m, size_t step_words, dim3 g, const StagedBatch& batch, uint64_t count,
+                        uint64_t capacity, const DfsWorkspace& ws, const uint32_t* qm, hipStream_t stream, uint32_t lut_ok = 0, uint32_t slot = 0) {
     const idx_t n = (idx_t)x->bwt.n;
-    const bool dense = x->bwt.dense && x->rev.dense && !(kernel_flags() & (1 << 29));      // (bit 29 of FMGPU_DEV_FLAGS: read Format A although Format D exists)
+    const bool dense = x->bwt.dense && x->rev.dense && !(flags & FMGPU_SEL_LEAN_FORMAT_A);      // (read Format A although Format D exists)
     LeanArgs la{x->bwt.va.blk, x->rev.va.blk, d_steps, S, m, (idx_t)(x->hC[1] + x->hC[2] + x->hC[3] + x->hC[4]), x->bwt.va.super, x->rev.va.super,
                 kWide ? (uint32_t)((x->bwt.n >> kSuperShift) + 1) : 0u,
                 (const uint4*)x->bwt.dense, (const uint4*)x->rev.dense, x->bwt.dense_ex, x->rev.dense_ex, x->bwt.dense_nex, x->rev.dense_nex, nullptr, 0u, 0u};
-    if (!kWide && x->lut && x->lut_len >= 1 && x->lut_len <= 16 && lut_ok && !(kernel_flags() & FMGPU_SEL_NO_PREFIX_TABLE)) { la.lut = x->lut; la.lutL = x->lut_len; la.lut_ok = lut_ok; }
+    if (!kWide && x->lut && x->lut_len >= 1 && x->lut_len <= 16 && lut_ok && !(flags & FMGPU_SEL_NO_PREFIX_TABLE)) { la.lut = x->lut; la.lutL = x->lut_len; la.lut_ok = lut_ok; }
     const size_t lds = lean_lds_bytes(m, step_words);
     uint32_t waste = kLeanRefillWaste, heavy = kLeanShareHeavy; [[maybe_unused]] int steps = kLeanSteps;
     if (const char* ev = dev_env("FMGPU_DEV_LEAN_WASTE")) waste = (uint32_t)std::max(1, atoi(ev));
     if (const char* ev = dev_env("FMGPU_DEV_LEAN_HEAVY")) heavy = (uint32_t)std::max(0, atoi(ev));
     if (const char* ev = dev_env("FMGPU_DEV_LEAN_STEPS")) steps = atoi(ev);
     WorkBoard* const board = ws.board_of(slot);
-    auto launch = [&](auto kern) { kern<<<g, dim3(256), lds, stream>>>(la, dq, doff, count, n, dout, capacity, ws.ctr, reinterpret_cast<ulonglong2*>(ws.view_of(slot).p0), ws.view.nlanes,
+    auto launch = [&](auto kern) { kern<<<g, dim3(256), lds, stream>>>(la, batch.q(), batch.off(), count, n, batch.hits(), capacity, ws.ctr, reinterpret_cast<ulonglong2*>(ws.view_of(slot).p0), ws.view.nlanes,
                                                                     (m + 15) / 16, qm, waste, heavy, board, ws.next_of(slot)); };
 #ifdef FMGPU_DEV
     if (steps == 1) launch(k_scheme_lean<kLeanWaves, 1, false>); else if (steps == 2) launch(k_scheme_lean<kLeanWaves, 2, false>); else if (steps == 8) launch(k_scheme_lean<kLeanWaves, 8, false>); else
@@ -2517,48 +2517,38 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
     if (out_count) *out_count = 0;
     if (nq == 0) return 0;
     if (!qbuf || !qoff || (!out && capacity) || !out_count) return fail(FMGPU_ERR_INVALID, "qbuf / qoff / out / out_count is null");
+    const int flags = kernel_flags();                              // the call's options, read once
+    const bool heavy_first = opt_on(FMGPU_OPT_HEAVY_FIRST);
     SchemeDev sd{};
     bool edit = false;
     uint32_t max_u = 0;
     if (scheme_mode) {
         bool nothing = false;
-        if (int prc = parse_scheme(x, scheme, max_hits, sd, max_u, nothing)) return prc;
+        if (int prc = parse_scheme(x, scheme, max_hits, flags, sd, max_u, nothing)) return prc;
         if (nothing) return 0;
         edit = scheme->edit != 0;
     }
-    Staged soff, sbuf, sout;
+    StagedBatch batch;
     int rc;
-    if ((rc = soff.in(qoff, (nq + 1) * 8, stream))) return rc;
-    uint64_t total = 0;
-    uint32_t maxlen = 0, minlen = 0;
-    const bool have_shape = is_device_pointer(qoff);             // offsets in HBM: total and length range come back in one copy
-    if (have_shape) { if ((rc = query_shape((const uint64_t*)soff.dev, nq, stream, &maxlen, &minlen, &total))) return rc; }
-    else total = qoff[nq];
-    if ((rc = sbuf.in(qbuf, total, stream))) return rc;
-    if ((rc = sout.out(out, capacity * sizeof(fmgpu_hit), stream))) return rc;
-    if (!have_shape && (rc = query_len_range((const uint64_t*)soff.dev, nq, stream, &maxlen, &minlen))) return rc;
-    if (maxlen > 0xfffeu) return fail(FMGPU_ERR_UNSUPPORTED, "queries longer than 65534 symbols");
-    static std::mutex occ_mu; static std::map<std::tuple<int, int, int, size_t>, int> occ_cache;
-    int bpc = 8;
+    if ((rc = batch.stage(qbuf, qoff, nq, out, capacity, stream))) return rc;
+    const uint32_t maxlen = batch.maxlen, minlen = batch.minlen;
     // LDS budget of a 256-lane block of the DFS kernels: 64 KB in all — the staged queries (1 KB per word and block) beside the kernels' own
     // tables and hit buffers (<= 17 KB static in the general kernels; per-step tables + hit buffers in the table-driven ones, reserved below)
     const size_t stage_words = x->bwt.sigma <= 15 ? (maxlen + 7) / 8 : (maxlen + 3) / 4;
     const size_t tables_lds = scheme_mode ? (size_t)3 * (size_t)std::max(sd.S, 1) * ((size_t)maxlen + 1) * 4 + (size_t)kWaveHitWords * 4 : 0;
     const size_t stage_budget = (size_t)64 * 1024 - std::max<size_t>((kWide ? 24 : 17) * 1024, std::min<size_t>(tables_lds, 47 * 1024));
     const size_t occ_lds = stage_words * 1024 > stage_budget ? 0 : stage_words * 1024;
-    const auto occ_key = std::make_tuple(x->bwt.search_family(), x->bwt.sigma, (int)scheme_mode + (edit ? 2 : 0), occ_lds);
-    bool occ_known = false;
-    { std::lock_guard<std::mutex> g(occ_mu); auto it = occ_cache.find(occ_key); if (it != occ_cache.end()) { bpc = it->second; occ_known = true; } }
-    if (!occ_known) {   // residency of the kernel instantiation that will run (queried once: the call is slow)
-        auto occ_of = [&](auto kernel) { int nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, occ_lds) == hipSuccess && nb > 0) bpc = nb; else (void)hipGetLastError(); };
+    const DfsKernel general = !scheme_mode ? DfsKernel::backtracking : edit ? DfsKernel::scheme_edit : DfsKernel::scheme;
+    int bpc = resident_blocks({general, x->bwt.search_family(), x->bwt.sigma, occ_lds}, 8, [&] {   // residency of the general kernel instantiation that would run
+        int nb = 0;
         dispatch_occ(x->bwt, [&](auto occ, auto ms) {
             using O = decltype(occ);
-            if (scheme_mode && edit) occ_of(k_scheme_edit<O, decltype(ms)::value>); else
-            if (scheme_mode) occ_of(k_scheme<O, decltype(ms)::value>); else occ_of(k_backtracking<O, decltype(ms)::value>);
+            if (scheme_mode && edit) nb = max_resident_blocks(k_scheme_edit<O, decltype(ms)::value>, occ_lds); else
+            if (scheme_mode) nb = max_resident_blocks(k_scheme<O, decltype(ms)::value>, occ_lds); else nb = max_resident_blocks(k_backtracking<O, decltype(ms)::value>, occ_lds);
             return 0;
         });
-        std::lock_guard<std::mutex> g(occ_mu); occ_cache[occ_key] = bpc;
-    }
+        return nb;
+    });
     // query staging: 8 (nibbles) or 4 (bytes) symbols per LDS word, 256 lanes per block; above 48 KB the kernels read global memory
     const uint32_t qnib = x->bwt.sigma <= 15 ? 1u : 0u;
     uint32_t qwords = qnib ? (maxlen + 7) / 8 : (maxlen + 3) / 4;
@@ -2579,19 +2569,13 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
     std::vector<uint32_t> wide_tab;
     bool lean_wide = false;
     if (scheme_mode && !edit && x->bwt.family == FAM_A && !x->bwt.shadow && x->bwt.sigma == 5 && x->bwt.va.bstride == 64u && minlen == maxlen && maxlen <= 255 && max_hits == ~0ull &&
-        sd.S <= 16 && max_u <= 2 && nq <= 0xffffffffull && n >= 2 && n < ((idx_t)1 << 38) && !(sd.dev_flags & (2 | (1 << 24) | (1 << 30)))) {
+        sd.S <= 16 && max_u <= 2 && nq <= 0xffffffffull && n >= 2 && n < ((idx_t)1 << 38) && !(flags & (FMGPU_SEL_GENERAL_DFS | FMGPU_SEL_NO_SHARING | FMGPU_SEL_NO_LEAN))) {
         uint32_t lut_ok = 0;
         lean_wide = build_step_table(sd, maxlen, 0, 0, wide_tab, lut_ok);
         if (lean_wide) {
             wide_tab.resize(wide_tab.size() / 3);                  // (the stretch words serve the walk tables)
-            if (maxlen >= 16 && nq >= (1u << 16) && nq < 0x7fffffffull && opt_on(FMGPU_OPT_HEAVY_FIRST)) {
-                uint32_t* order = nullptr;
-                const auto pre_t0 = std::chrono::steady_clock::now();
-                if ((rc = heavy_first_order(nq, stream, [&](uint64_t count_reads, uint8_t* flags, uint32_t* cnt) {
-                        k_heavy_flags_plain<OccA<5>><<<dim3((unsigned)((count_reads + 255) / 256)), 256, 0, stream>>>(OccA<5>{x->bwt.va}, n, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                                                                   count_reads, maxlen, heavy_rows(), flags, cnt);
-                    }, &order))) return rc;
-                if (order) { d_qmap = order; prepass_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - pre_t0).count(); }
+            if (maxlen >= 16 && nq >= (1u << 16) && nq < 0x7fffffffull && heavy_first) {
+                if ((rc = heavy_first_on_blocks(OccA<5>{x->bwt.va}, n, maxlen, batch, nq, stream, &d_qmap, &prepass_ms))) return rc;
             }
             bpc = 3;
         }
@@ -2601,9 +2585,9 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
     // fast path: equal-length batch on a Format-A BiFMIndex — with LF tables, or (Hamming, sigma <= 5) on the blocks alone
     // 16-symbol walk: 2-bit symbols, queries staged in LDS as nibbles
     const bool have_lf = x->bwt.lf_table && x->rev.lf_table;
-    const bool use_wj = !edit && !(sd.dev_flags & 32) && have_lf && x->bwt.walkj && x->rev.walkj && x->bwt.walk_bits == 2 && x->rev.walk_bits == 2 && qnib && qwords;
-    const bool fast_ok = scheme_mode && x->bwt.search_family() == FAM_A && (have_lf || x->bwt.sigma == 5) && x->bwt.sigma <= 32 && !(sd.dev_flags & 2);   // (sigma = 5: the fast kernels also run on the plain index)
-    const uint32_t lutL = (sd.dev_flags & 4) ? 0 : x->lut_len;
+    const bool use_wj = !edit && !(flags & FMGPU_SEL_NO_WALK_TABLE) && have_lf && x->bwt.walkj && x->rev.walkj && x->bwt.walk_bits == 2 && x->rev.walk_bits == 2 && qnib && qwords;
+    const bool fast_ok = scheme_mode && x->bwt.search_family() == FAM_A && (have_lf || x->bwt.sigma == 5) && x->bwt.sigma <= 32 && !(flags & FMGPU_SEL_GENERAL_DFS);   // (sigma = 5: the fast kernels also run on the plain index)
+    const uint32_t lutL = (flags & FMGPU_SEL_NO_PREFIX_TABLE) ? 0 : x->lut_len;
     // one launch of the table-driven kernel per query length: an equal-length batch is one bucket; a ragged batch is sorted by length on the
     // device (the kernel reads its queries through the sorted index) as long as the buckets stay large enough to be worth a launch each
     struct Bucket { uint32_t m; uint64_t first, count; std::vector<uint32_t> tab; uint32_t lut_ok; };
@@ -2612,25 +2596,23 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
         Bucket b{maxlen, 0, nq, {}, 0};
         fast = build_step_table(sd, maxlen, lutL, use_wj ? 16u : 0u, b.tab, b.lut_ok);
         if (fast) buckets.push_back(std::move(b));
-        const bool hf_on = opt_on(FMGPU_OPT_HEAVY_FIRST);
         const bool by_lut = fast && x->lut && lutL >= 15 && lutL <= 16 && (buckets[0].lut_ok & 1u);     // (no step table — m < P, a scheme too large for it: the general kernel below)
         const bool by_blocks = !have_lf && x->bwt.sigma == 5 && maxlen >= 16;     // (the plain-index instantiation)
-        if (fast && (by_lut || by_blocks) && nq >= (1u << 16) && nq < 0x7fffffffull && hf_on) {
-            // hand the reads of high-copy repeats out first (k_heavy_flags; decided on a sample of the batch — a text without repeats has nothing to
-            // reorder, and the pass would cost 5 % of a 7 ms batch)
-            LutPositions lp{};
-            if (by_lut) for (uint32_t t = 0; t < lutL; ++t) lp.pos[t] = buckets[0].tab[t] & 0xffffu;
-            uint32_t* order = nullptr;
-            const auto pre_t0 = std::chrono::steady_clock::now();
-            if ((rc = heavy_first_order(nq, stream, [&](uint64_t count_reads, uint8_t* flags, uint32_t* cnt) {
-                    const dim3 g((unsigned)((count_reads + 255) / 256));
-                    if (by_lut) k_heavy_flags<<<g, 256, 0, stream>>>(x->lut, lutL, (uint32_t)x->bwt.sigma - 1u, lp, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev, count_reads,
-                                                                     (uint32_t)x->bwt.sigma, heavy_rows(), flags, cnt);
-                    else k_heavy_flags_plain<OccA<5>><<<g, 256, 0, stream>>>(OccA<5>{x->bwt.va}, n, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev, count_reads, maxlen, heavy_rows(), flags, cnt);
-                }, &order))) return rc;
-            if (order) { d_qmap = order; prepass_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - pre_t0).count(); }
+        if (fast && (by_lut || by_blocks) && nq >= (1u << 16) && nq < 0x7fffffffull && heavy_first) {
+            // hand the reads of high-copy repeats out first (decided on a sample of the batch — a text without repeats has nothing to
+            // reorder, and the pass would cost 5 % of a 7 ms batch): by the prefix table where it answers (k_heavy_flags), else from the blocks
+            if (by_lut) {
+                LutPositions lp{};
+                for (uint32_t t = 0; t < lutL; ++t) lp.pos[t] = buckets[0].tab[t] & 0xffffu;
+                const auto pre_t0 = std::chrono::steady_clock::now();
+                if ((rc = heavy_first_order(nq, stream, [&](uint64_t count_reads, uint8_t* hflags, uint32_t* cnt) {
+                        k_heavy_flags<<<dim3((unsigned)((count_reads + 255) / 256)), 256, 0, stream>>>(x->lut, lutL, (uint32_t)x->bwt.sigma - 1u, lp, batch.q(), batch.off(), count_reads,
+                                                                                                    (uint32_t)x->bwt.sigma, heavy_rows(), hflags, cnt);
+                    }, &d_qmap))) return rc;
+                if (d_qmap) prepass_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - pre_t0).count();
+            } else if ((rc = heavy_first_on_blocks(OccA<5>{x->bwt.va}, n, maxlen, batch, nq, stream, &d_qmap, &prepass_ms))) return rc;
         }
-    } else if (fast_ok && nq >= (1u << 16) && nq < 0x7fffffffull && !(sd.dev_flags & 64)) {
+    } else if (fast_ok && nq >= (1u << 16) && nq < 0x7fffffffull && !(flags & FMGPU_SEL_NO_LENGTH_BUCKETS)) {
         uint32_t *klen = nullptr, *kidx = nullptr, *slen = nullptr, *runs = nullptr;
         void* tmp = nullptr; size_t tmp_bytes = 0, tmp2 = 0;
         const uint32_t max_runs = maxlen - minlen + 1;
@@ -2646,7 +2628,7 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
             he = hipMalloc(&tmp, std::max(tmp_bytes, tmp2));
         }
         if (he != hipSuccess) { drop(); return hip_fail(he, "hipMalloc(length buckets)"); }
-        k_len_pairs<<<dim3((unsigned)((nq + 255) / 256)), 256, 0, stream>>>((const uint64_t*)soff.dev, nq, klen, kidx);
+        k_len_pairs<<<dim3((unsigned)((nq + 255) / 256)), 256, 0, stream>>>(batch.off(), nq, klen, kidx);
         size_t tb = std::max(tmp_bytes, tmp2);
         he = hipcub::DeviceRadixSort::SortPairs(tmp, tb, klen, slen, kidx, d_qmap, (int)nq, 0, 16, stream);
         tb = std::max(tmp_bytes, tmp2);
@@ -2677,16 +2659,9 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
         size_t max_tab = 0;
         for (const Bucket& b : buckets) max_tab = std::max(max_tab, b.tab.size());
         const size_t lds_fast = lds_bytes + max_tab * 4 + (size_t)kWaveHitWords * 4 + 2 * 256 * 16 + 16;      // (+ the top frames of the edit kernel's stacks)
-        const auto key = std::make_tuple(-1, x->bwt.sigma, 3, lds_fast);
-        bool known = false;
-        { std::lock_guard<std::mutex> g(occ_mu); auto it = occ_cache.find(key); if (it != occ_cache.end()) { bpc = it->second; known = true; } }
-        if (!known) {
-            int nb = 0;
-            hipError_t oe = x->bwt.sigma == 5 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_scheme_fast_edit<5, 5>, 256, lds_fast)
-                                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_scheme_fast_edit<0, 32>, 256, lds_fast);
-            if (oe == hipSuccess && nb > 0) bpc = nb; else (void)hipGetLastError();
-            std::lock_guard<std::mutex> g(occ_mu); occ_cache[key] = bpc;
-        }
+        bpc = resident_blocks({DfsKernel::scheme_fast_edit, FAM_A, x->bwt.sigma, lds_fast}, bpc, [&] {      // (no answer: the general kernel's figure stays)
+            return x->bwt.sigma == 5 ? max_resident_blocks(k_scheme_fast_edit<5, 5>, lds_fast) : max_resident_blocks(k_scheme_fast_edit<0, 32>, lds_fast);
+        });
     }
 #endif  // !FMGPU_WIDE
 #if !FMGPU_WIDE
@@ -2694,24 +2669,17 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
     // lanes of a wave share the work of large reads
     // (edit distance: <= 3 error edges of 16 bits each, the tree depth — query length + deletions — in 8 bits, the child index in 6)
     const int use_key = !fast || sd.S > 16 ? 0 : (!edit ? (max_u <= 2 ? 1 : 0) : (max_u <= 3 && maxlen + max_u <= 250 && x->bwt.sigma <= 32 ? 1 : 0));
-    const int sharing = use_key && max_hits == ~0ull && !(sd.dev_flags & (1 << 24)) ? 1 : 0;
-    // the plain index (sigma = 5, no table) with path keys and unlimited hits per read: the lean kernel (k_scheme_lean); bit 30 of FMGPU_DEV_FLAGS keeps
+    const int sharing = use_key && max_hits == ~0ull && !(flags & FMGPU_SEL_NO_SHARING) ? 1 : 0;
+    // the plain index (sigma = 5, no table) with path keys and unlimited hits per read: the lean kernel (k_scheme_lean); FMGPU_SEL_NO_LEAN keeps
     // k_scheme_fast<PLAIN> (the parity tests run both)
-    const bool lean = fast && !edit && !have_lf && x->bwt.sigma == 5 && sharing && nq <= 0xffffffffull && n >= 2 && !(sd.dev_flags & (1 << 30));
+    const bool lean = fast && !edit && !have_lf && x->bwt.sigma == 5 && sharing && nq <= 0xffffffffull && n >= 2 && !(flags & FMGPU_SEL_NO_LEAN);
     [[maybe_unused]] const uint32_t lean_qwords = (maxlen + 15) / 16;
     size_t lean_lds = 0;
     if (lean) {
         size_t max_tab = 0;
         for (const Bucket& b : buckets) max_tab = std::max(max_tab, b.tab.size() / 3);
         lean_lds = lean_lds_bytes(maxlen, max_tab);
-        const auto key = std::make_tuple(-2, x->bwt.sigma, 4, lean_lds);
-        bool known = false;
-        { std::lock_guard<std::mutex> g(occ_mu); auto it = occ_cache.find(key); if (it != occ_cache.end()) { bpc = it->second; known = true; } }
-        if (!known) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_scheme_lean<kLeanWaves, kLeanSteps, false>, 256, lean_lds) == hipSuccess && nb > 0) bpc = nb; else { (void)hipGetLastError(); bpc = 4; }
-            std::lock_guard<std::mutex> g(occ_mu); occ_cache[key] = bpc;
-        }
+        bpc = resident_blocks({DfsKernel::scheme_lean, FAM_A, x->bwt.sigma, lean_lds}, 4, [&] { return max_resident_blocks(k_scheme_lean<kLeanWaves, kLeanSteps, false>, lean_lds); });
         // measured on the genome-like text, 10 M x 101 bp (kernel ms): 7 / 6 / 5 / 4 resident blocks per CU = 141 / 126 / 120 / 118 (151 bp: 212 / 211 / 210 / 204); with
         // 4 node steps per pass 4 / 3 / 2 blocks = 111 / 106-108 / 134 (151 bp: 189 / 180-182 / 221) — the loop is bound by instruction issue (rocprofv3: ~550
         // wave instructions per iteration, the waves of a SIMD active 100 % of its time at 4 per SIMD; at 7 they spend 48 % of their cycles waiting to
@@ -2727,7 +2695,7 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
     // sharing between the waves of a launch (the board, fmgpu_search_shared.h): the table-driven edit-distance kernel, wherever its lanes share inside a wave
     bool with_board = false;
 #if !FMGPU_WIDE
-    with_board = fast && edit && sharing && !(kernel_flags() & FMGPU_SEL_NO_BOARD);
+    with_board = fast && edit && sharing && !(flags & FMGPU_SEL_NO_BOARD);
     const bool lean_any = lean;
 #else
     const bool lean_any = lean_wide;
@@ -2735,13 +2703,13 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
     {   // the lean kernel: its BOARD instantiation for the batches whose end it shortens (kLeanBoardReads)
         uint64_t lim = kLeanBoardReads;
         if (const char* ev = dev_env("FMGPU_DEV_LEAN_BOARD_READS")) lim = (uint64_t)atoll(ev);
-        if (lean_any && nq <= lim && !(kernel_flags() & FMGPU_SEL_NO_BOARD)) with_board = true;
+        if (lean_any && nq <= lim && !(flags & FMGPU_SEL_NO_BOARD)) with_board = true;
     }
     // a ragged batch through the equal-length kernels is one launch per read length: up to four of them run side by side (each on a quarter of the grid), so that the end of one
     // launch — the waves that hold its heaviest reads — overlaps the bulk of the next ones
     uint32_t dfs_slots = 1;
 #if !FMGPU_WIDE
-    if (fast && buckets.size() > 1 && !(kernel_flags() & FMGPU_SEL_NO_BOARD)) {
+    if (fast && buckets.size() > 1 && !(flags & FMGPU_SEL_NO_BOARD)) {
         dfs_slots = (uint32_t)std::min<size_t>(kDfsSlots, buckets.size());
         if (const char* ev = dev_env("FMGPU_DEV_DFS_SLOTS")) dfs_slots = (uint32_t)std::max(1, std::min((int)kDfsSlots, atoi(ev)));
     }
@@ -2770,7 +2738,7 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
     if (lean_wide) {
         FM_HIP(hipMemsetAsync(&ws.ctr->next, 0, 8, stream));
         if ((rc = ws.reset_board(stream))) return rc;
-        launch_lean(x, d_steps, (uint32_t)sd.S, maxlen, wide_tab.size(), grid, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev, nq, (fmgpu_hit*)sout.dev, capacity, ws, d_qmap, stream);
+        launch_lean(x, flags, d_steps, (uint32_t)sd.S, maxlen, wide_tab.size(), grid, batch, nq, capacity, ws, d_qmap, stream);
     } else
 #endif
 #if !FMGPU_WIDE
@@ -2787,7 +2755,7 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
             if (have_lf) { fa.lf_fw = x->bwt.lf_table; fa.lf_rv = x->rev.lf_table; }
             fa.steps = d_steps + at; fa.S = (uint32_t)sd.S; fa.m = b.m;
             at += b.tab.size();
-            if (have_lf && !(sd.dev_flags & 8)) { fa.w3_fw = x->bwt.walk3; fa.w3_rv = x->rev.walk3; }
+            if (have_lf && !(flags & FMGPU_SEL_NO_LF3)) { fa.w3_fw = x->bwt.walk3; fa.w3_rv = x->rev.walk3; }
             if (use_wj) { fa.wj_fw = x->bwt.walkj; fa.wj_rv = x->rev.walkj; }
             fa.lut = b.lut_ok ? x->lut : nullptr; fa.lutL = x->lut_len; fa.lut_ok = b.lut_ok;
             for (int k = 1; k < x->bwt.sigma && k <= 8; ++k) fa.C1[k - 1] = (idx_t)x->hC[k];
@@ -2796,26 +2764,22 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
             FM_HIP(hipMemsetAsync(lnext, 0, 8, lstream));          // reads are handed out from 0
             if ((rc = ws.reset_board(lstream, slot))) return rc;
             const uint32_t* qm = d_qmap ? d_qmap + b.first : nullptr;
+            // one launch statement for the table-driven kernels: `tail` is what follows use_key (the edit kernel's board, the hand-out counter)
+            auto launch_fast = [&](auto kern, auto occ_tag, auto... tail) {
+                using O = decltype(occ_tag);
+                kern<<<g, block, lds_fast, lstream>>>(O{x->bwt.va}, O{x->rev.va}, fa, batch.q(), batch.off(), b.count, n, max_hits, batch.hits(), capacity, ws.ctr, lview, qwords, qnib,
+                                                      sd.dev_flags, qm, sharing, use_key, tail...);
+            };
             if (edit) {
-                if (x->bwt.sigma == 5) {
-                    if (!have_lf) k_scheme_fast_edit<5, 5, true><<<g, block, lds_fast, lstream>>>(OccA<5>{x->bwt.va}, OccA<5>{x->rev.va}, fa, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                             b.count, n, max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, lview, qwords, qnib, sd.dev_flags, qm, sharing, use_key, ws.board_of(slot), lnext);
-                    else k_scheme_fast_edit<5, 5><<<g, block, lds_fast, lstream>>>(OccA<5>{x->bwt.va}, OccA<5>{x->rev.va}, fa, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                             b.count, n, max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, lview, qwords, qnib, sd.dev_flags, qm, sharing, use_key, ws.board_of(slot), lnext);
-                } else
-                    k_scheme_fast_edit<0, 32><<<g, block, lds_fast, lstream>>>(OccA<0>{x->bwt.va}, OccA<0>{x->rev.va}, fa, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                              b.count, n, max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, lview, qwords, qnib, sd.dev_flags, qm, sharing, use_key, ws.board_of(slot), lnext);
+                WorkBoard* const board = ws.board_of(slot);
+                if (x->bwt.sigma != 5) launch_fast(k_scheme_fast_edit<0, 32>, OccA<0>{}, board, lnext);
+                else if (!have_lf) launch_fast(k_scheme_fast_edit<5, 5, true>, OccA<5>{}, board, lnext);
+                else launch_fast(k_scheme_fast_edit<5, 5>, OccA<5>{}, board, lnext);
             } else if (lean) {
-                launch_lean(x, fa.steps, (uint32_t)sd.S, b.m, b.tab.size() / 3, g, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev, b.count, (fmgpu_hit*)sout.dev, capacity, ws, qm, lstream, b.lut_ok, slot);
-            } else if (x->bwt.sigma == 5 && !have_lf)
-                k_scheme_fast<5, 5, true><<<g, block, lds_fast, lstream>>>(OccA<5>{x->bwt.va}, OccA<5>{x->rev.va}, fa, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                          b.count, n, max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, lview, qwords, qnib, sd.dev_flags, qm, sharing, use_key, lnext);
-            else if (x->bwt.sigma == 5)
-                k_scheme_fast<5, 5, false><<<g, block, lds_fast, lstream>>>(OccA<5>{x->bwt.va}, OccA<5>{x->rev.va}, fa, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                    b.count, n, max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, lview, qwords, qnib, sd.dev_flags, qm, sharing, use_key, lnext);
-            else
-                k_scheme_fast<0, 32, false><<<g, block, lds_fast, lstream>>>(OccA<0>{x->bwt.va}, OccA<0>{x->rev.va}, fa, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                     b.count, n, max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, lview, qwords, qnib, sd.dev_flags, qm, sharing, use_key, lnext);
+                launch_lean(x, flags, fa.steps, (uint32_t)sd.S, b.m, b.tab.size() / 3, g, batch, b.count, capacity, ws, qm, lstream, b.lut_ok, slot);
+            } else if (x->bwt.sigma != 5) launch_fast(k_scheme_fast<0, 32, false>, OccA<0>{}, lnext);
+            else if (!have_lf) launch_fast(k_scheme_fast<5, 5, true>, OccA<5>{}, lnext);
+            else launch_fast(k_scheme_fast<5, 5, false>, OccA<5>{}, lnext);
         }
         if ((rc = ws.join(stream))) return rc;
     } else
@@ -2824,77 +2788,38 @@ static int run_dfs(Index* x, bool scheme_mode, const uint8_t* qbuf, const uint64
         // the general kernels: path keys order the hits of a read (Hamming: <= 2 substitutions; edit distance: <= 3 errors), and with them and no limit on the hits per read the
         // lanes that run out of queries at the end of the batch take subtrees from the busy lanes of their wave
         sd.use_key = sd.S > 16 ? 0 : (!edit ? (max_u <= 2 ? 1 : 0) : (max_u <= 3 && maxlen + max_u <= 250 && x->bwt.sigma <= 32 ? 1 : 0));
-        sd.sharing = sd.use_key && max_hits == ~0ull && !(sd.dev_flags & (1 << 24)) ? 1 : 0;
+        sd.sharing = sd.use_key && max_hits == ~0ull && !(flags & FMGPU_SEL_NO_SHARING) ? 1 : 0;
         // ... and the reads of high-copy repeats are handed out first here too (16 LF steps per read on whatever layout the index has)
         uint32_t* gen_order = nullptr;
-        {
-            if (nq >= (1u << 16) && nq < 0x7fffffffull && minlen >= 1 && opt_on(FMGPU_OPT_HEAVY_FIRST)) {
-                int orc = 0;
-                const auto pre_t0 = std::chrono::steady_clock::now();
-                rc = dispatch_occ(x->bwt, [&](auto occ, auto) {
-                    orc = heavy_first_order(nq, stream, [&](uint64_t count_reads, uint8_t* flags, uint32_t* cnt) {
-                        k_heavy_flags_plain<decltype(occ)><<<dim3((unsigned)((count_reads + 255) / 256)), 256, 0, stream>>>(occ, n, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                                                                         count_reads, 0u, heavy_rows(), flags, cnt);
-                    }, &gen_order);
-                    return 0;
-                });
-                if (rc || orc) return rc ? rc : orc;
-                if (gen_order) prepass_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - pre_t0).count();
-                timer.start();                                      // kernel_ms = the search kernel alone, as in the table-driven path
-            }
+        if (nq >= (1u << 16) && nq < 0x7fffffffull && minlen >= 1 && heavy_first) {
+            rc = dispatch_occ(x->bwt, [&](auto occ, auto) { return heavy_first_on_blocks(occ, n, 0u, batch, nq, stream, &gen_order, &prepass_ms); });
+            if (rc) return rc;
+            timer.start();                                          // kernel_ms = the search kernel alone, as in the table-driven path
         }
-        const DevString& rv = x->rev;
         LfView lfv{nullptr, nullptr, nullptr};
-        if (x->bwt.lf_table && rv.lf_table && !(sd.dev_flags & 16)) lfv = LfView{x->bwt.lf_table, rv.lf_table, x->dC};
+        if (x->bwt.lf_table && x->rev.lf_table && !(flags & FMGPU_SEL_NO_LF_GENERAL)) lfv = LfView{x->bwt.lf_table, x->rev.lf_table, x->dC};
         rc = dispatch_occ(x->bwt, [&](auto occ, auto ms) {
             using O = decltype(occ);
-            O r{};
-            if constexpr (std::is_same_v<O, OccA<5>> || std::is_same_v<O, OccA<0>>) r = O{rv.va};
-            else if constexpr (std::is_same_v<O, OccM>) r = O{rv.vm};
-            else r = O{rv.vr};
             (void)hipMemsetAsync(&ws.ctr->next, 0, 8, stream);         // queries are handed out from 0, one reservation per wave
             if (edit) {
-                k_scheme_edit<O, decltype(ms)::value><<<grid, block, lds_bytes, stream>>>(occ, r, sd, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev, nq, n,
-                                                                                  max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, ws.view, qwords, qnib, lfv, maxlen,
-                                                                                  (sd.dev_flags & 4) ? nullptr : x->lut, x->lut_len, gen_order);
+                k_scheme_edit<O, decltype(ms)::value><<<grid, block, lds_bytes, stream>>>(occ, rev_occ<O>(x->rev), sd, batch.q(), batch.off(), nq, n,
+                                                                                  max_hits, batch.hits(), capacity, ws.ctr, ws.view, qwords, qnib, lfv, maxlen,
+                                                                                  (flags & FMGPU_SEL_NO_PREFIX_TABLE) ? nullptr : x->lut, x->lut_len, gen_order);
                 return 0;
             }
-            k_scheme<O, decltype(ms)::value><<<grid, block, lds_bytes, stream>>>(occ, r, sd, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev, nq, n,
-                                                                         max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, ws.view, qwords, qnib, lfv, gen_order);
+            k_scheme<O, decltype(ms)::value><<<grid, block, lds_bytes, stream>>>(occ, rev_occ<O>(x->rev), sd, batch.q(), batch.off(), nq, n,
+                                                                         max_hits, batch.hits(), capacity, ws.ctr, ws.view, qwords, qnib, lfv, gen_order);
             return 0;
         });
     } else {
         rc = dispatch_occ(x->bwt, [&](auto occ, auto ms) {
-            k_backtracking<decltype(occ), decltype(ms)::value><<<grid, block, lds_bytes, stream>>>(occ, x->bidirectional, (const uint8_t*)sbuf.dev,
-                                                                                           (const uint64_t*)soff.dev, nq, n, K, (fmgpu_hit*)sout.dev,
+            k_backtracking<decltype(occ), decltype(ms)::value><<<grid, block, lds_bytes, stream>>>(occ, x->bidirectional, batch.q(), batch.off(), nq, n, K, batch.hits(),
                                                                                            capacity, ws.ctr, ws.view, qwords, qnib);
             return 0;
         });
     }
     timer.stop();
-    hipError_t le = hipGetLastError();
-    Counters hc{};
-    if (le == hipSuccess) le = hipMemcpyAsync(&hc, ws.ctr, sizeof hc, hipMemcpyDeviceToHost, stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(stream);
-    if (le != hipSuccess) return hip_fail(le, "search kernel");
-    if ((rc = ws.check_board())) return rc;
-#ifdef FMGPU_DEV_STAMPS
-    { unsigned long long dbg[12]; (void)hipMemcpy(dbg, reinterpret_cast<unsigned long long*>(ws.ctr) + 8, sizeof dbg, hipMemcpyDeviceToHost);
-      if (dbg[6]) fprintf(stderr, "stamps: waves %llu, wave node-steps %llu; cycles per node-step: top %.0f share %.0f refill %.0f flush+rest %.0f issue %.0f wait %.0f node %.0f tail %.0f\n", dbg[6], dbg[5],
-                          (double)dbg[9] / dbg[5], (double)dbg[7] / dbg[5], (double)dbg[8] / dbg[5], (double)dbg[0] / dbg[5], (double)dbg[1] / dbg[5], (double)dbg[2] / dbg[5], (double)dbg[3] / dbg[5], (double)dbg[4] / dbg[5]); }
-#endif
-    *out_count = hc.hits;
-    if (stats) { stats->lf_steps = hc.nodes; stats->hits = hc.hits; stats->kernel_ms = timer.ms(); stats->prepass_ms = prepass_ms; stats->table_bytes = hc.table_bytes; stats->table_accesses = hc.table_accesses; }
-    if (stats) { unsigned long long served = 0; (void)hipMemcpy(&served, reinterpret_cast<unsigned long long*>(ws.ctr) + 21, 8, hipMemcpyDeviceToHost); stats->table_steps = served; }   // (k_scheme_lean: nodes that prefix-table entries stood for)
-#ifdef FMGPU_DEV
-    if (stats) { unsigned long long bad = 0; (void)hipMemcpy(&bad, reinterpret_cast<unsigned long long*>(ws.ctr) + 20, 8, hipMemcpyDeviceToHost); stats->hits |= bad << 48; }     // (dev build: LDS frame slots that disagreed with the stack in HBM, in the top bits of `hits`)
-#endif
-    if (hc.hits > capacity) {
-        if (sout.writeback) { sout.bytes = capacity * sizeof(fmgpu_hit); (void)sout.finish(); }
-        return fail(FMGPU_ERR_CAPACITY, "result buffer holds " + std::to_string(capacity) + " records, " + std::to_string(hc.hits) + " produced");
-    }
-    if (sout.writeback) sout.bytes = hc.hits * sizeof(fmgpu_hit);
-    return sout.finish();
+    return finish_dfs("search kernel", rc, ws, timer, prepass_ms, batch, capacity, out_count, stats, stream);
 }
 
 int fmgpu_search_scheme(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* scheme,
@@ -2988,7 +2913,7 @@ int check_scheme(fmgpu_index_t h, const fmgpu_scheme* scheme, uint64_t max_hits_
     SchemeDev sd{};
     uint32_t max_u = 0;
     bool nothing = false;
-    return parse_scheme(x, scheme, max_hits_per_query, sd, max_u, nothing);
+    return parse_scheme(x, scheme, max_hits_per_query, kernel_flags(), sd, max_u, nothing);
 }
 int check_expanded_scheme(fmgpu_index_t h, const fmgpu_expanded_scheme* scheme) {
     Index* x = reinterpret_cast<Index*>(h);
@@ -3012,19 +2937,16 @@ int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff
     if (int hrc = check_expanded_head(x, scheme)) return hrc;
     if (nq == 0 || scheme->n_searches == 0) return 0;                                  // SearchNg21.h:205
     if (!qbuf || !qoff || (!out && capacity) || !out_count) return fail(FMGPU_ERR_INVALID, "qbuf / qoff / out / out_count is null");
+    const int flags = kernel_flags();                              // the call's options, read once
+    const bool heavy_first = opt_on(FMGPU_OPT_HEAVY_FIRST);
     std::vector<uint32_t> tab;
     uint32_t max_u = 0;
     if (int prc = parse_expanded(x, scheme, tab, max_u)) return prc;
     const uint64_t M = scheme->length;
     const uint32_t S = (uint32_t)scheme->n_searches;
-    Staged soff, sbuf, sout;
+    StagedBatch batch;
     int rc;
-    if ((rc = soff.in(qoff, (nq + 1) * 8, stream))) return rc;
-    uint64_t total = 0;
-    if (is_device_pointer(qoff)) { FM_HIP(hipMemcpyAsync(&total, qoff + nq, 8, hipMemcpyDeviceToHost, stream)); FM_HIP(hipStreamSynchronize(stream)); }
-    else total = qoff[nq];
-    if ((rc = sbuf.in(qbuf, total, stream))) return rc;
-    if ((rc = sout.out(out, capacity * sizeof(fmgpu_hit), stream))) return rc;
+    if ((rc = batch.stage(qbuf, qoff, nq, out, capacity, stream, false))) return rc;    // (no length range: k_ng21 skips the reads whose length is not M)
     const uint32_t qnib = x->bwt.sigma <= 15 ? 1u : 0u;
     uint32_t qwords = qnib ? ((uint32_t)M + 7) / 8 : ((uint32_t)M + 3) / 4;
     if ((size_t)qwords * 1024 > 48 * 1024) qwords = 0;             // 64 KB of LDS per block, 14 KB of hit buffers: very long queries stay in global memory
@@ -3032,73 +2954,38 @@ int fmgpu_search_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff
     const size_t lds_bytes = (size_t)qwords * 1024 + (tab_lds ? tab.size() * 4 : 0);
     LfView lfv{nullptr, nullptr, nullptr};
     if (x->bwt.lf_table && x->rev.lf_table) lfv = LfView{x->bwt.lf_table, x->rev.lf_table, x->dC};
-    static std::mutex occ_mu; static std::map<std::tuple<int, int, size_t>, int> occ_cache;
-    int bpc = 4;
-    const auto occ_key = std::make_tuple(x->bwt.search_family(), x->bwt.sigma, lds_bytes);
-    bool occ_known = false;
-    { std::lock_guard<std::mutex> g(occ_mu); auto it = occ_cache.find(occ_key); if (it != occ_cache.end()) { bpc = it->second; occ_known = true; } }
-    if (!occ_known) {
-        dispatch_occ(x->bwt, [&](auto occ, auto ms) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ng21<decltype(occ), decltype(ms)::value>, 256, lds_bytes) == hipSuccess && nb > 0) bpc = nb;
-            else (void)hipGetLastError();
-            return 0;
-        });
-        std::lock_guard<std::mutex> g(occ_mu); occ_cache[occ_key] = bpc;
-    }
+    const int bpc = resident_blocks({DfsKernel::ng21, x->bwt.search_family(), x->bwt.sigma, lds_bytes}, 4, [&] {
+        int nb = 0;
+        dispatch_occ(x->bwt, [&](auto occ, auto ms) { nb = max_resident_blocks(k_ng21<decltype(occ), decltype(ms)::value>, lds_bytes); return 0; });
+        return nb;
+    });
     // path keys (<= 3 errors, depth and child index within their bit fields) order the hits of a read; with them and no limit on the hits per read the
     // lanes that find the query queue empty take subtrees from the busy lanes of their wave
     const int use_key = S <= 16 && max_u <= 3 && M + max_u <= 250 && x->bwt.sigma <= 32 ? 1 : 0;
-    const int sharing = use_key && max_hits_per_query == ~0ull && !(kernel_flags() & (1 << 24)) ? 1 : 0;
+    const int sharing = use_key && max_hits_per_query == ~0ull && !(flags & FMGPU_SEL_NO_SHARING) ? 1 : 0;
     DfsWorkspace ws;
     if ((rc = ws.init((uint32_t)M + max_u + 2, nq, bpc, stream, kEditFramePlanes))) return rc;       // deletions lengthen the path beyond the query by at most the largest upper bound
     DBuf tab_buf;
     if ((rc = tab_buf.alloc(tab.size() * 4))) return rc;
     uint32_t* d_tab = tab_buf.as<uint32_t>();
-    hipError_t le = hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream);
+    FM_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream));
     EventTimer timer(stream, stats != nullptr);
     const idx_t n = (idx_t)x->bwt.n;
-    const auto pre_t0 = std::chrono::steady_clock::now();
     uint32_t* order = nullptr;                                     // heavy reads first, as in search_ng26
-    if (le == hipSuccess && nq >= (1u << 16) && nq < 0x7fffffffull && opt_on(FMGPU_OPT_HEAVY_FIRST)) {
-        int orc = 0;
-        rc = dispatch_occ(x->bwt, [&](auto occ, auto) {
-            orc = heavy_first_order(nq, stream, [&](uint64_t count_reads, uint8_t* flags, uint32_t* cnt) {
-                k_heavy_flags_plain<decltype(occ)><<<dim3((unsigned)((count_reads + 255) / 256)), 256, 0, stream>>>(occ, n, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                                                                 count_reads, 0u, heavy_rows(), flags, cnt);
-            }, &order);
-            return 0;
-        });
-        if (rc || orc) return rc ? rc : orc;
+    float prepass_ms = 0.f;
+    if (nq >= (1u << 16) && nq < 0x7fffffffull && heavy_first) {
+        rc = dispatch_occ(x->bwt, [&](auto occ, auto) { return heavy_first_on_blocks(occ, n, 0u, batch, nq, stream, &order, &prepass_ms); });
+        if (rc) return rc;
     }
-    const float prepass_ms = order ? std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - pre_t0).count() : 0.f;
     timer.start();                                                  // kernel_ms = the search kernel alone, in every path (the hand-out order is prepass_ms)
-    if (le == hipSuccess) rc = dispatch_occ(x->bwt, [&](auto occ, auto ms) {
+    rc = dispatch_occ(x->bwt, [&](auto occ, auto ms) {
         using O = decltype(occ);
-        const DevString& rv = x->rev;
-        O r{};
-        if constexpr (std::is_same_v<O, OccA<5>> || std::is_same_v<O, OccA<0>>) r = O{rv.va};
-        else if constexpr (std::is_same_v<O, OccM>) r = O{rv.vm};
-        else r = O{rv.vr};
-        k_ng21<O, decltype(ms)::value><<<dim3(ws.grid), dim3(256), lds_bytes, stream>>>(occ, r, d_tab, S, (uint32_t)M, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                                   nq, n, max_hits_per_query, (fmgpu_hit*)sout.dev, capacity, ws.ctr, ws.view, qwords, qnib, lfv, tab_lds, x->lut, x->lut_len, use_key, sharing, order);
+        k_ng21<O, decltype(ms)::value><<<dim3(ws.grid), dim3(256), lds_bytes, stream>>>(occ, rev_occ<O>(x->rev), d_tab, S, (uint32_t)M, batch.q(), batch.off(),
+                                                                                   nq, n, max_hits_per_query, batch.hits(), capacity, ws.ctr, ws.view, qwords, qnib, lfv, tab_lds, x->lut, x->lut_len, use_key, sharing, order);
         return 0;
     });
     timer.stop();
-    if (le == hipSuccess) le = hipGetLastError();
-    Counters hc{};
-    if (le == hipSuccess) le = hipMemcpyAsync(&hc, ws.ctr, sizeof hc, hipMemcpyDeviceToHost, stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(stream);
-    if (le != hipSuccess) return hip_fail(le, "search_ng21 kernel");
-    if (rc) return rc;
-    *out_count = hc.hits;
-    if (stats) { stats->lf_steps = hc.nodes; stats->hits = hc.hits; stats->kernel_ms = timer.ms(); stats->prepass_ms = prepass_ms; }
-    if (hc.hits > capacity) {
-        if (sout.writeback) { sout.bytes = capacity * sizeof(fmgpu_hit); (void)sout.finish(); }
-        return fail(FMGPU_ERR_CAPACITY, "result buffer holds " + std::to_string(capacity) + " records, " + std::to_string(hc.hits) + " produced");
-    }
-    if (sout.writeback) sout.bytes = hc.hits * sizeof(fmgpu_hit);
-    return sout.finish();
+    return finish_dfs("search_ng21 kernel", rc, ws, timer, prepass_ms, batch, capacity, out_count, stats, stream);
 }
 
 #if !FMGPU_WIDE   // (fmgpu_hit holds 64-bit fields: the record helpers are width-independent and live in the 32-bit-row build)

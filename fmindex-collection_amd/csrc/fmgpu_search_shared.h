@@ -750,8 +750,9 @@ static int query_len_range(const uint64_t* dqoff, uint64_t nq, hipStream_t strea
     return query_shape(dqoff, nq, stream, out_max, out_min, nullptr);
 }
 
-// ---- what the launchers of the general depth-first kernels share (fmgpu_search.hip: run_dfs; fmgpu_search_sm.hip: run_sm): the hand-out order with the reads of
-// high-copy repeats in front, the workspace (frame stacks, counters, board), and the scheme check
+// ---- what the launchers of the depth-first kernels share (fmgpu_search.hip: run_dfs, fmgpu_search_ng21; fmgpu_search_sm.hip: run_sm): the hand-out order with the reads of
+// high-copy repeats in front, the workspace (frame stacks, counters, board), the scheme check, and at the end of this file everything around the launch itself
+// (StagedBatch, resident_blocks, heavy_first_on_blocks, rev_occ, finish_dfs)
 // the same question without tables: the interval of the read's last 16 symbols by backward search on the blocks (16 of the ~500 nodes a read visits)
 template <class Occ>
 __global__ __launch_bounds__(256) void k_heavy_flags_plain(Occ occ, idx_t n, const uint8_t* __restrict__ qbuf, const uint64_t* __restrict__ qoff, uint64_t nq, uint32_t m,
@@ -936,7 +937,7 @@ static int heavy_first_order(uint64_t nq, hipStream_t stream, FlagPass&& flag_pa
 }
 
 // a caller's search_ng26 scheme checked and flattened into the kernels' form; `nothing`: the search reports nothing whatever the batch (SearchNg26.h:408-409)
-static int parse_scheme(const Index* x, const fmgpu_scheme* scheme, uint64_t max_hits, SchemeDev& sd, uint32_t& max_u, bool& nothing) {
+static int parse_scheme(const Index* x, const fmgpu_scheme* scheme, uint64_t max_hits, int flags, SchemeDev& sd, uint32_t& max_u, bool& nothing) {   // flags: the call's kernel_flags()
     nothing = false;
     if (!x->bidirectional) return fail(FMGPU_ERR_INVALID, "search_ng26 needs a BiFMIndex (bwt_rev)");
     if (!scheme || !scheme->pi || !scheme->l || !scheme->u) return fail(FMGPU_ERR_INVALID, "scheme is null");
@@ -944,7 +945,7 @@ static int parse_scheme(const Index* x, const fmgpu_scheme* scheme, uint64_t max
         return fail(FMGPU_ERR_UNSUPPORTED, "scheme larger than 16 searches x 16 parts");
     if (max_hits == 0 || scheme->n_searches == 0) { nothing = true; return 0; }
     sd.S = scheme->n_searches; sd.P = scheme->n_parts; sd.uniform = scheme->partition ? 0 : 1;
-    sd.dev_flags = kernel_flags();
+    sd.dev_flags = flags;
     sd.use_key = 0; sd.sharing = 0;                              // set by the launcher for the general Hamming kernel
     for (int s = 0; s < sd.S; ++s) {
         uint32_t seen = 0;
@@ -971,5 +972,113 @@ static int parse_scheme(const Index* x, const fmgpu_scheme* scheme, uint64_t max
 }
 
 // expands a scheme for queries of length m into the fast kernel's per-step table (see k_scheme_fast); false if it does not fit.
+
+// ---- what run_dfs, fmgpu_search_ng21 and run_sm do around their launches: the batch on the device, the residency of the kernel that will run, the heavy-first order
+// from the blocks, the counters and records back to the caller.  Which kernel runs, and on what grid, stays with each launcher.
+
+// The caller's batch and result buffer as the kernels see them (host buffers staged, device buffers in place), with the batch's shape.
+struct StagedBatch {
+    Staged soff, sbuf, sout;
+    uint64_t total = 0;
+    uint32_t maxlen = 0, minlen = 0;
+    const uint8_t* q() const { return (const uint8_t*)sbuf.dev; }
+    const uint64_t* off() const { return (const uint64_t*)soff.dev; }
+    fmgpu_hit* hits() const { return (fmgpu_hit*)sout.dev; }
+    // want_range = false (fmgpu_search_ng21: its kernel checks every read's length itself): host offsets cost no launch and no synchronisation — their length range is
+    // not computed — and no length is refused here
+    int stage(const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, fmgpu_hit* out, uint64_t capacity, hipStream_t stream, bool want_range = true) {
+        int rc;
+        if ((rc = soff.in(qoff, (nq + 1) * 8, stream))) return rc;
+        const bool have_shape = is_device_pointer(qoff);             // offsets in HBM: total and length range come back in one copy
+        if (have_shape) { if ((rc = query_shape(off(), nq, stream, &maxlen, &minlen, &total))) return rc; }
+        else total = qoff[nq];
+        if ((rc = sbuf.in(qbuf, total, stream))) return rc;
+        if ((rc = sout.out(out, capacity * sizeof(fmgpu_hit), stream))) return rc;
+        if (!want_range) return 0;
+        if (!have_shape && (rc = query_len_range(off(), nq, stream, &maxlen, &minlen))) return rc;
+        if (maxlen > 0xfffeu) return fail(FMGPU_ERR_UNSUPPORTED, "queries longer than 65534 symbols");
+        return 0;
+    }
+};
+
+// Resident 256-lane blocks per CU of a kernel instantiation at an LDS size: query() asks the runtime (0 = no answer, `fallback` stands in) the first time a key comes
+// up — the call is slow — and the answer is kept for the process.
+enum class DfsKernel { scheme, scheme_edit, backtracking, scheme_fast_edit, scheme_lean, ng21, scheme_sm };
+struct ResidencyKey {
+    DfsKernel kernel; int family, sigma; size_t lds;
+    bool operator<(const ResidencyKey& o) const { return std::tie(kernel, family, sigma, lds) < std::tie(o.kernel, o.family, o.sigma, o.lds); }
+};
+template <class K>
+static int max_resident_blocks(K kernel, size_t lds) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, lds) == hipSuccess && nb > 0) return nb;
+    (void)hipGetLastError();
+    return 0;
+}
+static std::mutex residency_mu;
+static std::map<ResidencyKey, int> residency;                  // (at namespace scope: one cache, not one per query type)
+template <class Query>
+static int resident_blocks(const ResidencyKey& key, int fallback, Query&& query) {
+    { std::lock_guard<std::mutex> g(residency_mu); auto it = residency.find(key); if (it != residency.end()) return it->second; }
+    const int nb = query();
+    const int bpc = nb > 0 ? nb : fallback;
+    std::lock_guard<std::mutex> g(residency_mu); residency[key] = bpc;
+    return bpc;
+}
+
+// The heavy-first order (heavy_first_order) decided by backward search on the blocks (k_heavy_flags_plain); m = 0: every read has its own length.  *order stays null
+// where nothing is worth moving; *prepass_ms is written only with an order.
+template <class Occ>
+static int heavy_first_on_blocks(Occ occ, idx_t n, uint32_t m, const StagedBatch& b, uint64_t nq, hipStream_t stream, uint32_t** order, float* prepass_ms) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = heavy_first_order(nq, stream, [&](uint64_t count_reads, uint8_t* flags, uint32_t* cnt) {
+        k_heavy_flags_plain<Occ><<<dim3((unsigned)((count_reads + 255) / 256)), 256, 0, stream>>>(occ, n, b.q(), b.off(), count_reads, m, heavy_rows(), flags, cnt);
+    }, order);
+    if (rc) return rc;
+    if (*order) *prepass_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
+// the reverse string through the accessor type that dispatch_occ chose for the forward one
+template <class O>
+static O rev_occ(const DevString& rv) {
+    if constexpr (std::is_same_v<O, OccA<5>> || std::is_same_v<O, OccA<0>>) return O{rv.va};
+    else if constexpr (std::is_same_v<O, OccM>) return O{rv.vm};
+    else return O{rv.vr};
+}
+
+// After timer.stop(): the launch's status, the counter area (one copy of its 256 bytes) and the records back to the caller.  `what` names the kernel in a HIP error,
+// launch_rc is what the launch's dispatch_occ returned.
+static int finish_dfs(const char* what, int launch_rc, DfsWorkspace& ws, EventTimer& timer, float prepass_ms, StagedBatch& b, uint64_t capacity, uint64_t* out_count,
+                      fmgpu_stats* stats, hipStream_t stream) {
+    unsigned long long area[32] = {};                              // Counters | debug stamps (words 8..19) | 20: bad frame slots (dev build) | 21: table steps | hand-out counters
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess) le = hipMemcpyAsync(area, ws.ctr, sizeof area, hipMemcpyDeviceToHost, stream);
+    if (le == hipSuccess) le = hipStreamSynchronize(stream);
+    if (le != hipSuccess) return hip_fail(le, what);
+    if (launch_rc) return launch_rc;
+    if (int rc = ws.check_board()) return rc;
+    Counters hc; memcpy(&hc, area, sizeof hc);
+#ifdef FMGPU_DEV_STAMPS
+    { const unsigned long long* dbg = area + 8;
+      if (dbg[6]) fprintf(stderr, "stamps: waves %llu, wave node-steps %llu; cycles per node-step: top %.0f share %.0f refill %.0f flush+rest %.0f issue %.0f wait %.0f node %.0f tail %.0f\n", dbg[6], dbg[5],
+                          (double)dbg[9] / dbg[5], (double)dbg[7] / dbg[5], (double)dbg[8] / dbg[5], (double)dbg[0] / dbg[5], (double)dbg[1] / dbg[5], (double)dbg[2] / dbg[5], (double)dbg[3] / dbg[5], (double)dbg[4] / dbg[5]); }
+#endif
+    *out_count = hc.hits;
+    if (stats) {
+        stats->lf_steps = hc.nodes; stats->hits = hc.hits; stats->kernel_ms = timer.ms(); stats->prepass_ms = prepass_ms;
+        stats->table_bytes = hc.table_bytes; stats->table_accesses = hc.table_accesses;
+        stats->table_steps = area[21];                              // (k_scheme_lean: nodes that prefix-table entries stood for)
+#ifdef FMGPU_DEV
+        stats->hits |= area[20] << 48;                              // (dev build: LDS frame slots that disagreed with the stack in HBM, in the top bits of `hits`)
+#endif
+    }
+    if (hc.hits > capacity) {
+        if (b.sout.writeback) { b.sout.bytes = capacity * sizeof(fmgpu_hit); (void)b.sout.finish(); }
+        return fail(FMGPU_ERR_CAPACITY, "result buffer holds " + std::to_string(capacity) + " records, " + std::to_string(hc.hits) + " produced");
+    }
+    if (b.sout.writeback) b.sout.bytes = hc.hits * sizeof(fmgpu_hit);
+    return b.sout.finish();
+}
 
 }  // namespace FMGPU_NS

@@ -227,27 +227,21 @@ static int run_sm(Index* x, const uint8_t* qbuf, const uint64_t* qoff, uint64_t 
     if (out_count) *out_count = 0;
     if (nq == 0) return 0;
     if (!qbuf || !qoff || (!out && capacity) || !out_count) return fail(FMGPU_ERR_INVALID, "qbuf / qoff / out / out_count is null");
+    const int flags = kernel_flags();                              // the call's options, read once
+    const bool heavy_first = opt_on(FMGPU_OPT_HEAVY_FIRST);
     SchemeDev sd{};
     uint32_t max_u = 0;
     bool nothing = false;
-    if (int prc = parse_scheme(x, scheme, max_hits, sd, max_u, nothing)) return prc;
+    if (int prc = parse_scheme(x, scheme, max_hits, flags, sd, max_u, nothing)) return prc;
     if (scheme->edit != 0) return fail(FMGPU_ERR_INVALID, "search_hamming_sm is a Hamming search: scheme->edit must be 0");
     if (x->bwt.sigma > 32) return fail(FMGPU_ERR_UNSUPPORTED, "search_hamming_sm needs sigma <= 32 (the masks are one word), this index has sigma = " + std::to_string(x->bwt.sigma));
     std::vector<uint32_t> rows;
     if (int mrc = parse_matrix(x, matrix, rows)) return mrc;
     if (nothing) return 0;
-    Staged soff, sbuf, sout;
+    StagedBatch batch;
     int rc;
-    if ((rc = soff.in(qoff, (nq + 1) * 8, stream))) return rc;
-    uint64_t total = 0;
-    uint32_t maxlen = 0, minlen = 0;
-    const bool have_shape = is_device_pointer(qoff);             // offsets in HBM: total and length range come back in one copy
-    if (have_shape) { if ((rc = query_shape((const uint64_t*)soff.dev, nq, stream, &maxlen, &minlen, &total))) return rc; }
-    else total = qoff[nq];
-    if ((rc = sbuf.in(qbuf, total, stream))) return rc;
-    if ((rc = sout.out(out, capacity * sizeof(fmgpu_hit), stream))) return rc;
-    if (!have_shape && (rc = query_len_range((const uint64_t*)soff.dev, nq, stream, &maxlen, &minlen))) return rc;
-    if (maxlen > 0xfffeu) return fail(FMGPU_ERR_UNSUPPORTED, "queries longer than 65534 symbols");
+    if ((rc = batch.stage(qbuf, qoff, nq, out, capacity, stream))) return rc;
+    const uint32_t maxlen = batch.maxlen;
     DBuf dmasks;
     if ((rc = dmasks.alloc(rows.size() * 4))) return rc;
     FM_HIP(hipMemcpyAsync(dmasks.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
@@ -260,21 +254,14 @@ static int run_sm(Index* x, const uint8_t* qbuf, const uint64_t* qoff, uint64_t 
     const size_t stage_budget = (size_t)64 * 1024 - (size_t)(kWide ? 24 : 17) * 1024;
     if ((size_t)qwords * 1024 > stage_budget) qwords = 0;
     const size_t lds_bytes = (size_t)qwords * 1024;
-    static std::mutex occ_mu; static std::map<std::tuple<int, int, size_t>, int> occ_cache;      // resident blocks per instantiation and LDS size (queried once: the call is slow)
-    int bpc = 8;
-    const auto occ_key = std::make_tuple(x->bwt.search_family(), x->bwt.sigma, lds_bytes);
-    bool occ_known = false;
-    { std::lock_guard<std::mutex> g(occ_mu); auto it = occ_cache.find(occ_key); if (it != occ_cache.end()) { bpc = it->second; occ_known = true; } }
-    if (!occ_known) {
+    const int bpc = resident_blocks({DfsKernel::scheme_sm, x->bwt.search_family(), x->bwt.sigma, lds_bytes}, 8, [&] {
+        int nb = 0;
         dispatch_occ(x->bwt, [&](auto occ, auto ms) {
-            if constexpr (decltype(ms)::value <= 32) {
-                int nb = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_scheme_sm<decltype(occ), decltype(ms)::value>, 256, lds_bytes) == hipSuccess && nb > 0) bpc = nb; else (void)hipGetLastError();
-            }
+            if constexpr (decltype(ms)::value <= 32) nb = max_resident_blocks(k_scheme_sm<decltype(occ), decltype(ms)::value>, lds_bytes);
             return 0;
         });
-        std::lock_guard<std::mutex> g(occ_mu); occ_cache[occ_key] = bpc;
-    }
+        return nb;
+    });
     DfsWorkspace ws;
     EventTimer timer(stream, stats != nullptr);
     const idx_t n = (idx_t)x->bwt.n;
@@ -282,49 +269,21 @@ static int run_sm(Index* x, const uint8_t* qbuf, const uint64_t* qoff, uint64_t 
     // the reads of high-copy repeats are handed out first, as for the general kernel of run_dfs (a read whose last 16 symbols hold a code >= sigma is not flagged)
     uint32_t* order = nullptr;
     float prepass_ms = 0.f;
-    if (nq >= (1u << 16) && nq < 0x7fffffffull && minlen >= 1 && opt_on(FMGPU_OPT_HEAVY_FIRST)) {
-        int orc = 0;
-        const auto pre_t0 = std::chrono::steady_clock::now();
-        rc = dispatch_occ(x->bwt, [&](auto occ, auto) {
-            orc = heavy_first_order(nq, stream, [&](uint64_t count_reads, uint8_t* flags, uint32_t* cnt) {
-                k_heavy_flags_plain<decltype(occ)><<<dim3((unsigned)((count_reads + 255) / 256)), 256, 0, stream>>>(occ, n, (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev,
-                                                                                                                 count_reads, 0u, heavy_rows(), flags, cnt);
-            }, &order);
-            return 0;
-        });
-        if (rc || orc) return rc ? rc : orc;
-        if (order) prepass_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - pre_t0).count();
+    if (nq >= (1u << 16) && nq < 0x7fffffffull && batch.minlen >= 1 && heavy_first) {
+        rc = dispatch_occ(x->bwt, [&](auto occ, auto) { return heavy_first_on_blocks(occ, n, 0u, batch, nq, stream, &order, &prepass_ms); });
+        if (rc) return rc;
     }
     FM_HIP(hipMemsetAsync(&ws.ctr->next, 0, 8, stream));           // reads are handed out from 0, one reservation per wave
     timer.start();                                                  // kernel_ms = the search kernel alone
-    const DevString& rv = x->rev;
     rc = dispatch_occ(x->bwt, [&](auto occ, auto ms) {
         using O = decltype(occ);
-        if constexpr (decltype(ms)::value <= 32) {
-            O r{};
-            if constexpr (std::is_same_v<O, OccA<5>> || std::is_same_v<O, OccA<0>>) r = O{rv.va};
-            else if constexpr (std::is_same_v<O, OccM>) r = O{rv.vm};
-            else r = O{rv.vr};
-            k_scheme_sm<O, decltype(ms)::value><<<dim3(ws.grid), dim3(256), lds_bytes, stream>>>(occ, r, sd, dmasks.as<uint32_t>(), (const uint8_t*)sbuf.dev, (const uint64_t*)soff.dev, nq, n,
-                                                                                            max_hits, (fmgpu_hit*)sout.dev, capacity, ws.ctr, ws.view, qwords, qnib, order);
-        }
+        if constexpr (decltype(ms)::value <= 32)
+            k_scheme_sm<O, decltype(ms)::value><<<dim3(ws.grid), dim3(256), lds_bytes, stream>>>(occ, rev_occ<O>(x->rev), sd, dmasks.as<uint32_t>(), batch.q(), batch.off(), nq, n,
+                                                                                            max_hits, batch.hits(), capacity, ws.ctr, ws.view, qwords, qnib, order);
         return 0;
     });
     timer.stop();
-    hipError_t le = hipGetLastError();
-    Counters hc{};
-    if (le == hipSuccess) le = hipMemcpyAsync(&hc, ws.ctr, sizeof hc, hipMemcpyDeviceToHost, stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(stream);
-    if (le != hipSuccess) return hip_fail(le, "k_scheme_sm");
-    if (rc) return rc;
-    *out_count = hc.hits;
-    if (stats) { stats->lf_steps = hc.nodes; stats->hits = hc.hits; stats->kernel_ms = timer.ms(); stats->prepass_ms = prepass_ms; stats->table_bytes = hc.table_bytes; stats->table_accesses = hc.table_accesses; }
-    if (hc.hits > capacity) {
-        if (sout.writeback) { sout.bytes = capacity * sizeof(fmgpu_hit); (void)sout.finish(); }
-        return fail(FMGPU_ERR_CAPACITY, "result buffer holds " + std::to_string(capacity) + " records, " + std::to_string(hc.hits) + " produced");
-    }
-    if (sout.writeback) sout.bytes = hc.hits * sizeof(fmgpu_hit);
-    return sout.finish();
+    return finish_dfs("k_scheme_sm", rc, ws, timer, prepass_ms, batch, capacity, out_count, stats, stream);
 }
 
 int fmgpu_search_hamming_sm(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* scheme, const fmgpu_scoring_matrix* matrix,
