@@ -804,6 +804,19 @@ class Feed:
         del keep
         return (hits, st) if want_stats else hits
 
+    def map(self, queries, errors=None, schemes=None, ng21=False, edit=True, n=UINT64_MAX, locate=True, want_hits=False, want_stratum=False, want_stats=False,
+            first_records=0, out=None):
+        """fmgpu_feed_map: what map_reads returns, chunk by chunk (a PackedQueries is not taken).  `out` = a POSITION_DTYPE array to write into (a pinned one is
+        written in place; it must hold every position)."""
+        suffix, a, b, nq, keep = self._batch(queries)
+        if suffix == "_q4":
+            raise ValueError("a feed maps byte batches")
+        what, alive = _map_query(errors, schemes, ng21, edit, n, locate, first_records)
+        call = getattr(capi.lib(), "fmgpu_feed_map" + suffix)
+        res = _run_map(lambda *args: call(self._f, a, b, nq, C.byref(what), *args), nq, what, want_hits, want_stratum, want_stats, out, False)
+        del keep, alive
+        return res
+
 
 class Replicas:
     """one index file on several GPUs of this process (fmgpu_replicas_*; SURVEY 8b `fmgpu_set_devices`): a batch is cut into contiguous ranges, one per
@@ -1109,6 +1122,82 @@ def search_locate(index, queries, errors, n=UINT64_MAX, edit=True, compat_auto_s
     if len(parts) > 1:
         pos = pos[np.argsort(pos["qidx"], kind="stable")]     # the two length classes hold different queries: ascending qidx, each query's rows in order
     return pos[fields]
+
+
+def _map_query(errors, schemes, ng21, edit, n, locate, first_records):
+    """(capi.MapQuery, objects to keep alive) for map_reads / Feed.map.  errors=k: k == 0 is exact search (FMGPU_MAP_EXACT), k > 0 the ladder h2(j + 2, 0, j), j = 0 .. k,
+    with uniform partitions (Hamming for edit=False).  schemes=[...]: an explicit ladder — (scheme, partition) pairs, or bare (pi, l, u) schemes; with ng21=True expanded
+    schemes (search_scheme.expand) for the search_ng21 ladder."""
+    if (errors is None) == (schemes is None):
+        raise ValueError("give either errors or schemes")
+    what = capi.MapQuery()
+    what.max_hits_per_query, what.locate, what.first_records = n, 1 if locate else 0, int(first_records or 0)
+    if schemes is None and int(errors) == 0:
+        what.kind = capi.MAP_EXACT
+        return what, None
+    if schemes is None:
+        schemes = [(search_scheme.h2(j + 2, 0, j), None) for j in range(int(errors) + 1)]
+    if ng21:
+        keep = [tuple(_u64(x) for x in sch) for sch in schemes]
+        arr = (capi.ExpandedScheme * len(keep))()
+        for sc, (pi, l, u) in zip(arr, keep):
+            sc.n_searches, sc.length = (pi.shape if pi.ndim == 2 else (0, 0))
+            sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
+        what.kind = capi.MAP_NG21
+    else:
+        pairs = [s if len(s) == 2 else (s, None) for s in schemes]
+        keep = [tuple(_u64(x) for x in sch) + ((_u64(part),) if part is not None else (None,)) for sch, part in pairs]
+        arr = (capi.Scheme * len(keep))()
+        for sc, (pi, l, u, part) in zip(arr, keep):
+            sc.n_searches, sc.n_parts = pi.shape
+            sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
+            sc.partition = part.ctypes.data_as(capi.u64p) if part is not None else None
+            sc.edit = 1 if edit else 0
+        what.kind = capi.MAP_SCHEME
+    what.n_schemes, what.schemes = len(keep), C.cast(arr, C.c_void_p)
+    return what, (keep, arr)
+
+
+def _run_map(call, nq, what, want_hits, want_stratum, want_stats, out, with_stream):
+    """one fmgpu_map / fmgpu_feed_map call into host arrays: the counts are exact also on FMGPU_ERR_CAPACITY, so one more call with them always fits"""
+    nst = max(1, what.n_schemes)
+    stratum = np.full(max(nq, 1), 255, dtype=np.uint8) if want_stratum else None
+    sstats, lstats = (capi.Stats * nst)(), capi.Stats()
+    cap = len(out) if out is not None else (max(1024, 4 * nq) if what.locate else 0)
+    hcap = max(1024, 4 * nq) if want_hits else 0
+    cnt, hcnt = C.c_uint64(), C.c_uint64()
+    for _ in range(2):
+        pos = out if out is not None else np.zeros(max(cap, 1), dtype=POSITION_DTYPE)
+        hits = np.zeros(max(hcap, 1), dtype=HIT_DTYPE) if want_hits else None
+        args = (capi.ptr(pos), cap, C.byref(cnt), capi.ptr(hits), hcap, C.byref(hcnt), capi.ptr(stratum), sstats if want_stats else None,
+                C.byref(lstats) if want_stats else None) + ((None,) if with_stream else ())
+        rc = call(*args)
+        if rc != capi.FMGPU_ERR_CAPACITY or out is not None:
+            break
+        cap, hcap = max(cap, int(cnt.value)), (max(hcap, int(hcnt.value)) if want_hits else 0)
+    capi.check(rc)
+    res = (pos[: cnt.value],)
+    if want_hits:
+        res += (np.ascontiguousarray(hits[: hcnt.value]),)
+    if want_stratum:
+        res += (stratum[:nq],)
+    if want_stats:
+        res += (([sstats[i] for i in range(nst)], lstats),)
+    return res if len(res) > 1 else res[0]
+
+
+def map_reads(index, queries, errors=None, schemes=None, ng21=False, edit=True, n=UINT64_MAX, locate=True, want_hits=False, want_stratum=False, want_stats=False,
+              first_records=0):
+    """fmgpu_map: fmc::Search's whole path in one call — search (exact, a best-stratum ladder of schemes, or a search_ng21 ladder), the records put into callback order
+    and every row located, all on the device.  `queries` as for the searches (list of reads, (qbuf, qoff) of numpy arrays or DeviceBuffers, PackedQueries); see
+    _map_query for errors / schemes.  Returns the POSITION_DTYPE records (qidx, seq_id, pos, errors, hit) in the reference's report order[, the HIT_DTYPE records `hit`
+    indexes][, the uint8 stratum of every read, 255 = unfound][, (search stats per stratum, locate stats)].  locate=False stops after the hit records."""
+    qbuf, qoff, nq = _queries(queries)
+    what, alive = _map_query(errors, schemes, ng21, edit, n, locate, first_records)
+    call = _q4(queries, capi.lib().fmgpu_map, capi.lib().fmgpu_map_q4)
+    res = _run_map(lambda *args: call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(what), *args), nq, what, want_hits, want_stratum, want_stats, None, True)
+    del alive
+    return res
 
 
 def reconstruct_text(index, seq_nbr=None):

@@ -125,6 +125,16 @@ class FeedConfig(C.Structure):
                 ("pack4", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MapQuery(C.Structure):
+    """fmgpu_map_query: what fmgpu_map / fmgpu_feed_map run over a batch (kind: MAP_EXACT, MAP_SCHEME, MAP_NG21)"""
+    _fields_ = [("kind", C.c_int32), ("n_schemes", C.c_int32), ("schemes", C.c_void_p), ("max_hits_per_query", C.c_uint64),
+                ("locate", C.c_int32), ("reserved", C.c_int32), ("first_records", C.c_uint64)]
+
+
+MAP_EXACT, MAP_SCHEME, MAP_NG21 = 0, 1, 2
+assert C.sizeof(MapQuery) == 40
+
+
 # every symbol include/fmgpu.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "fmgpu_abi_version", "fmgpu_last_error", "fmgpu_device_count", "fmgpu_set_device",
@@ -144,6 +154,7 @@ EXPORTS = [
     "fmgpu_search_smems", "fmgpu_search_smems_q4", "fmgpu_search_hamming_sm",
     "fmgpu_feed_create", "fmgpu_feed_destroy", "fmgpu_feed_plan", "fmgpu_feed_search_exact", "fmgpu_feed_search_exact_q4", "fmgpu_feed_search_exact_v",
     "fmgpu_feed_search_scheme", "fmgpu_feed_search_scheme_v", "fmgpu_feed_info", "fmgpu_malloc_host", "fmgpu_free_host",
+    "fmgpu_map", "fmgpu_map_q4", "fmgpu_hits_from_intervals", "fmgpu_feed_map", "fmgpu_feed_map_v",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -281,6 +292,13 @@ def lib():
         L.fmgpu_feed_info.argtypes = [C.c_void_p, u64p, u64p, u64p, u64p, u64p]
         L.fmgpu_malloc_host.argtypes = [C.POINTER(C.c_void_p), C.c_uint64]
         L.fmgpu_free_host.argtypes = [C.c_void_p]
+    if hasattr(L, "fmgpu_map"):                               # (FMGPU_LIBRARY may name an older build of the same ABI: tools/map_probe.py times one)
+        L.fmgpu_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MapQuery), C.c_void_p, C.c_uint64, u64p,
+                                C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(Stats), C.POINTER(Stats), C.c_void_p]
+        L.fmgpu_map_q4.argtypes = L.fmgpu_map.argtypes
+        L.fmgpu_hits_from_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p]
+        L.fmgpu_feed_map.argtypes = L.fmgpu_map.argtypes[:-1]
+        L.fmgpu_feed_map_v.argtypes = L.fmgpu_feed_map.argtypes
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

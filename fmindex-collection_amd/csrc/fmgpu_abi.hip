@@ -169,6 +169,10 @@ int search_exact_shaped(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
     ROUTE(h, search_exact_shaped(h, qbuf, qoff, nq, out_lb, out_len, stats, stream, q4, total, longest, shortest));
 }
 int exact_reads_nibbles_on(fmgpu_index_t h, int32_t* yes) { ROUTE(h, exact_reads_nibbles_on(h, yes)); }
+int hits_from_intervals_on(fmgpu_index_t h, const uint64_t* lb, const uint64_t* len, const uint64_t* qoff, uint64_t nq, uint64_t qidx_base, uint64_t max_rows, fmgpu_hit* out,
+                           uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, void* stream) {
+    ROUTE(h, hits_from_intervals(lb, len, qoff, nq, qidx_base, max_rows, out, capacity, out_count, out_stratum, stream));
+}
 int handle_device(fmgpu_index_t h, int32_t* device) {
     const IndexHeader* hd = header_of(h);
     if (!hd) return fail(FMGPU_ERR_INVALID, "index handle is null or not a handle of this library");
@@ -326,6 +330,10 @@ int fmgpu_search_smems_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t
                           fmgpu_hit* out, fmgpu_seed_span* out_span, uint64_t capacity, uint64_t* out_count, uint32_t* out_match_len, fmgpu_stats* stats, void* stream) {
     if (nq == 0) { if (out_count) *out_count = 0; if (stats) *stats = fmgpu_stats{}; return 0; }
     ROUTE(h, fmgpu_search_smems_q4(h, packed, qoff, nq, min_len, max_rows, out, out_span, capacity, out_count, out_match_len, stats, stream));
+}
+int fmgpu_hits_from_intervals(const uint64_t* lb, const uint64_t* len, const uint64_t* qoff, uint64_t nq, uint64_t qidx_base, uint64_t max_rows_per_query, fmgpu_hit* out,
+                              uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, void* stream) {
+    return fmgpu32::api::hits_from_intervals(lb, len, qoff, nq, qidx_base, max_rows_per_query, out, capacity, out_count, out_stratum, stream);
 }
 int fmgpu_index_accelerate_extract(fmgpu_index_t h, int32_t enable) { ROUTE(h, fmgpu_index_accelerate_extract(h, enable)); }
 int fmgpu_sequence_lengths(fmgpu_index_t h, uint64_t* seq_ids, uint64_t* lengths, uint64_t capacity, uint64_t* out_count) {

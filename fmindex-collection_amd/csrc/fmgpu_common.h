@@ -215,6 +215,23 @@ int search_exact_shaped(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
 int exact_reads_nibbles_on(fmgpu_index_t h, int32_t* yes);
 int handle_device(fmgpu_index_t h, int32_t* device);
 
+// fmgpu_map's chain on device buffers (fmgpu_map.hip), shared by the one-shot call and the feeds (fmgpu_feed.hip).  A MapBuffer is device memory that grows on demand
+// (contents are not kept): the call's own scratch, or a feed slot's buffer.
+struct MapBuffer {
+    void* p = nullptr; size_t bytes = 0;
+    virtual int need(size_t nbytes) = 0;                      // afterwards bytes >= nbytes
+    virtual ~MapBuffer() = default;
+};
+int check_map_query(const fmgpu_map_query* what);             // kind, n_schemes, reserved: before anything else is looked at
+int check_map_schemes(fmgpu_index_t h, const fmgpu_map_query* what, bool packed);      // the schemes, the handle's kind, sigma for `_q4`, the annotated array
+// dq / doff / dstratum (may be null) are device memory; hits and positions hold H and P afterwards (*hit_count, *pos_count records); stats as fmgpu_map's
+int map_device(fmgpu_index_t h, const uint8_t* dq, const uint64_t* doff, uint64_t nq, const fmgpu_map_query* what, bool packed, MapBuffer* hits, MapBuffer* positions,
+               MapBuffer* intervals, uint8_t* dstratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, hipStream_t stream, uint64_t* hit_count, uint64_t* pos_count);
+// qidx += first in both lists, fmgpu_position::hit += hit_base (low 32 bits): a chunk's records renumbered for the caller's batch
+int map_rebase(fmgpu_hit* hits, uint64_t hit_count, fmgpu_position* positions, uint64_t pos_count, uint64_t first, uint64_t hit_base, hipStream_t stream);
+int hits_from_intervals_on(fmgpu_index_t h, const uint64_t* lb, const uint64_t* len, const uint64_t* qoff, uint64_t nq, uint64_t qidx_base, uint64_t max_rows, fmgpu_hit* out,
+                           uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, void* stream);      // fmgpu_hits_from_intervals in the build of the handle's row width
+
 struct Built {   // host copies of construction by-products (fmgpu_build_index with keep_host)
     std::vector<std::vector<uint8_t>> part;
 };

@@ -52,14 +52,16 @@ struct Grown {            // a buffer that only ever grows: device memory or pin
 };
 
 struct Slot {
-    Grown d_q, d_off, d_lb, d_len, d_hits;                   // device
-    Grown p_q, p_off, p_lb, p_len, p_hits;                   // pinned
+    Grown d_q, d_off, d_lb, d_len, d_hits, d_pos, d_str;     // device (d_pos, d_str: the positions and strata of fmgpu_feed_map)
+    Grown p_q, p_off, p_lb, p_len, p_hits, p_pos, p_str;     // pinned
     hipEvent_t ev_up = nullptr, ev_comp = nullptr, ev_down = nullptr;
     bool busy = false;                                       // a chunk is in flight: ev_down has been recorded
     uint64_t first = 0, reads = 0;                           // ... its reads
     uint64_t hits = 0, produced = 0;                         // ... scheme search: its records and the records of the chunks before it
+    uint64_t positions = 0, located = 0;                     // ... map: its positions and the positions of the chunks before it
     bool hits_in_place = false, results_in_place = false;
-    Slot() { p_q.pinned = p_off.pinned = p_lb.pinned = p_len.pinned = p_hits.pinned = true; }
+    bool hits_down = false, pos_down = false, pos_in_place = false, str_down = false, str_in_place = false;      // ... map: what its download carries, and where to
+    Slot() { p_q.pinned = p_off.pinned = p_lb.pinned = p_len.pinned = p_hits.pinned = p_pos.pinned = p_str.pinned = true; }
 };
 
 }  // namespace
@@ -373,6 +375,115 @@ int no_device_memory(std::initializer_list<const void*> ptrs) {
     return 0;
 }
 
+// ---- fmgpu_feed_map: fmgpu_map's chain (map_device, fmgpu_map.hip) per chunk on the slot's buffers
+struct SlotBuffer : MapBuffer {                                          // a slot's device buffer as the chain's growing scratch
+    Grown* g; uint64_t* tally;
+    SlotBuffer(Grown* g_, uint64_t* tally_) : g(g_), tally(tally_) { p = g->p; bytes = g->bytes; }
+    int need(size_t nbytes) override {
+        const int rc = g->need(nbytes, tally);
+        p = g->p; bytes = g->bytes;
+        return rc;
+    }
+};
+
+struct MapOut {                                                          // the caller's arrays
+    fmgpu_position* out; uint64_t capacity;
+    fmgpu_hit* out_hits; uint64_t hits_capacity;
+    uint8_t* out_stratum;
+};
+
+// wait for the chunk a slot holds and hand what came through the pinned slot to the caller
+int retire_map(Feed* f, Slot& sl, const MapOut& o) {
+    if (!sl.busy) return 0;
+    FM_HIP(hipEventSynchronize(sl.ev_down));
+    sl.busy = false;
+    fh::Workers& w = *f->workers;
+    const auto copy = [&](void* dst, const void* src, size_t bytes) {
+        w.run([&](uint32_t t, uint32_t parts) {
+            const size_t a = (size_t)fh::slice_cut(bytes, parts, t), b = (size_t)fh::slice_cut(bytes, parts, t + 1);
+            if (b > a) std::memcpy((uint8_t*)dst + a, (const uint8_t*)src + a, b - a);
+        });
+        f->last_staged += bytes;
+    };
+    if (sl.hits_down && !sl.hits_in_place) copy(o.out_hits + sl.produced, sl.p_hits.p, (size_t)sl.hits * sizeof(fmgpu_hit));
+    if (sl.pos_down && !sl.pos_in_place) copy(o.out + sl.located, sl.p_pos.p, (size_t)sl.positions * sizeof(fmgpu_position));
+    if (sl.str_down && !sl.str_in_place) copy(o.out_stratum + sl.first, sl.p_str.p, (size_t)sl.reads);
+    return 0;
+}
+
+int run_map(Feed* f, const Batch& b, const fmgpu_map_query* what, const MapOut& o, uint64_t* out_count, uint64_t* out_hit_count, fmgpu_stats* search_stats,
+            fmgpu_stats* locate_stats) {
+    begin_call(f);
+    const bool pos_pinned = o.capacity && pointer_kind(o.out) == 1, hits_pinned = o.hits_capacity && pointer_kind(o.out_hits) == 1;
+    const bool str_pinned = o.out_stratum && pointer_kind(o.out_stratum) == 1;
+    const int32_t nstats = std::max(1, what->n_schemes);
+    uint64_t max_reads = 0, max_symbols = 0;
+    int rc;
+    if ((rc = make_plan(f, b, &max_reads, &max_symbols))) return rc;
+    if ((rc = size_slots(f, max_reads, max_symbols, false, true, b.in_pinned))) return rc;
+    const uint64_t chunks = f->plan.size() - 1;
+    f->last_chunks = chunks;
+    uint64_t produced = 0, located = 0;
+    std::vector<fmgpu_stats> cs((size_t)nstats);
+    auto body = [&]() -> int {
+        for (uint64_t c = 0; c < chunks; ++c) {
+            Slot& sl = f->slot[c % (uint64_t)f->slots];
+            int r;
+            if ((r = retire_map(f, sl, o))) return r;
+            Staged1 st;
+            if ((r = upload_chunk(f, b, sl, c, false, &st))) return r;
+            if (o.out_stratum && (r = sl.d_str.need((size_t)st.reads, &f->device_bytes))) return r;
+            FM_HIP(hipStreamWaitEvent(f->comp, sl.ev_up, 0));
+            // the chain on the slot's buffers (they only ever grow; a stage that overflows one grows it and runs again), then the chunk's records renumbered for the batch
+            SlotBuffer bh(&sl.d_hits, &f->device_bytes), bp(&sl.d_pos, &f->device_bytes), bi(&sl.d_lb, &f->device_bytes);
+            uint64_t cnt = 0, pcnt = 0;
+            fmgpu_stats ls{};
+            if ((r = map_device(f->h, st.dq, sl.d_off.as<uint64_t>(), st.reads, what, false, &bh, &bp, &bi, o.out_stratum ? sl.d_str.as<uint8_t>() : nullptr,
+                                search_stats ? cs.data() : nullptr, locate_stats ? &ls : nullptr, f->comp, &cnt, &pcnt))) return r;
+            if ((r = map_rebase(sl.d_hits.as<fmgpu_hit>(), cnt, sl.d_pos.as<fmgpu_position>(), pcnt, f->plan[c], produced, f->comp))) return r;
+            if (search_stats) for (int32_t i = 0; i < nstats; ++i) add_stats(&search_stats[i], cs[(size_t)i]);
+            if (locate_stats) add_stats(locate_stats, ls);
+            FM_HIP(hipEventRecord(sl.ev_comp, f->comp));
+            FM_HIP(hipStreamWaitEvent(f->down, sl.ev_comp, 0));
+            sl.first = f->plan[c]; sl.reads = st.reads; sl.hits = cnt; sl.produced = produced; sl.positions = pcnt; sl.located = located;
+            // records beyond the caller's capacity are counted, not written
+            sl.hits_down = o.out_hits && cnt && produced + cnt <= o.hits_capacity; sl.hits_in_place = hits_pinned;
+            sl.pos_down = pcnt && located + pcnt <= o.capacity; sl.pos_in_place = pos_pinned;
+            sl.str_down = o.out_stratum != nullptr; sl.str_in_place = str_pinned;
+            if (sl.hits_down) {
+                void* target = o.out_hits + produced;
+                if (!hits_pinned) { if ((r = sl.p_hits.need((size_t)cnt * sizeof(fmgpu_hit), &f->pinned_bytes))) return r; target = sl.p_hits.p; }
+                FM_HIP(hipMemcpyAsync(target, sl.d_hits.p, (size_t)cnt * sizeof(fmgpu_hit), hipMemcpyDeviceToHost, f->down));
+            }
+            if (sl.pos_down) {
+                void* target = o.out + located;
+                if (!pos_pinned) { if ((r = sl.p_pos.need((size_t)pcnt * sizeof(fmgpu_position), &f->pinned_bytes))) return r; target = sl.p_pos.p; }
+                FM_HIP(hipMemcpyAsync(target, sl.d_pos.p, (size_t)pcnt * sizeof(fmgpu_position), hipMemcpyDeviceToHost, f->down));
+            }
+            if (sl.str_down) {
+                void* target = o.out_stratum + sl.first;
+                if (!str_pinned) { if ((r = sl.p_str.need((size_t)st.reads, &f->pinned_bytes))) return r; target = sl.p_str.p; }
+                FM_HIP(hipMemcpyAsync(target, sl.d_str.p, (size_t)st.reads, hipMemcpyDeviceToHost, f->down));
+            }
+            FM_HIP(hipEventRecord(sl.ev_down, f->down));
+            sl.busy = true;
+            produced += cnt; located += pcnt;
+        }
+        for (uint64_t k = 0; k < (uint64_t)f->slots; ++k) {
+            Slot& sl = f->slot[(chunks + k) % (uint64_t)f->slots];
+            if (int r = retire_map(f, sl, o)) return r;
+        }
+        return 0;
+    };
+    rc = body();
+    if (rc) { drain(f); return rc; }
+    *out_count = located;
+    if (out_hit_count) *out_hit_count = produced;
+    if (located > o.capacity) return fail(FMGPU_ERR_CAPACITY, "position buffer holds " + std::to_string(o.capacity) + " records, " + std::to_string(located) + " produced");
+    if (o.out_hits && produced > o.hits_capacity) return fail(FMGPU_ERR_CAPACITY, "hit buffer holds " + std::to_string(o.hits_capacity) + " records, " + std::to_string(produced) + " produced");
+    return 0;
+}
+
 }  // namespace
 }  // namespace fmgpu
 
@@ -427,7 +538,8 @@ int fmgpu_feed_destroy(fmgpu_feed_t f) {
     if (f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is not a feed of this library");
     drain(f);
     for (Slot& sl : f->slot) {
-        for (Grown* g : {&sl.d_q, &sl.d_off, &sl.d_lb, &sl.d_len, &sl.d_hits, &sl.p_q, &sl.p_off, &sl.p_lb, &sl.p_len, &sl.p_hits}) g->release(nullptr);
+        for (Grown* g : {&sl.d_q, &sl.d_off, &sl.d_lb, &sl.d_len, &sl.d_hits, &sl.d_pos, &sl.d_str, &sl.p_q, &sl.p_off, &sl.p_lb, &sl.p_len, &sl.p_hits, &sl.p_pos, &sl.p_str})
+            g->release(nullptr);
         for (hipEvent_t ev : {sl.ev_up, sl.ev_comp, sl.ev_down}) if (ev) (void)hipEventDestroy(ev);
     }
     for (hipStream_t s : {f->up, f->comp, f->down}) if (s) (void)hipStreamDestroy(s);
@@ -500,6 +612,41 @@ int fmgpu_feed_search_scheme_v(fmgpu_feed_t f, const uint8_t* const* reads, cons
     if (nq && !reads) return (f && f->magic == 0x46454544u) ? fail(FMGPU_ERR_INVALID, "reads / lens / out / out_count is null") : fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
     Batch b; b.reads = reads; b.lens = lens; b.nq = nq;
     return feed_scheme(f, b, scheme, max_hits_per_query, out, capacity, out_count, stats);
+}
+
+static int feed_map(fmgpu_feed_t f, Batch b, const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits,
+                    uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
+    if (out_count) *out_count = 0;
+    if (out_hit_count) *out_hit_count = 0;
+    if (int rc = check_map_query(what)) return rc;
+    if (search_stats) for (int32_t i = 0; i < std::max(1, what->n_schemes); ++i) search_stats[i] = fmgpu_stats{};
+    if (locate_stats) *locate_stats = fmgpu_stats{};
+    if (b.nq == 0) return 0;                                                              // (before the feed is looked at; out_stratum untouched)
+    if (!f || f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    if (int rc = check_feed(f)) return rc;
+    if (int rc = check_map_schemes(f->h, what, false)) return rc;
+    if ((b.reads ? !b.lens : (!b.qbuf || !b.qoff)) || !out_count || (!out && capacity) || (!out_hits && hits_capacity))
+        return fail(FMGPU_ERR_INVALID, b.reads || b.lens ? "reads / lens / out / out_count / out_hits is null" : "qbuf / qoff / out / out_count / out_hits is null");
+    if (int rc = no_device_memory({b.qbuf, b.qoff, b.reads, b.lens, out, out_count, out_hits, out_hit_count, out_stratum})) return rc;
+    if (b.reads) if (int rc = no_device_memory({b.reads[0]})) return rc;
+    b.in_pinned = b.qbuf && pointer_kind(b.qbuf) == 1;
+    const MapOut o{out, capacity, out_hits, hits_capacity, out_stratum};
+    return run_map(f, b, what, o, out_count, out_hit_count, search_stats, locate_stats);
+}
+
+int fmgpu_feed_map(fmgpu_feed_t f, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity,
+                   uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats,
+                   fmgpu_stats* locate_stats) {
+    Batch b; b.qbuf = qbuf; b.qoff = qoff; b.nq = nq;
+    return feed_map(f, b, what, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats);
+}
+int fmgpu_feed_map_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t* lens, uint64_t nq, const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity,
+                     uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats,
+                     fmgpu_stats* locate_stats) {
+    if (nq && !reads && !check_map_query(what))
+        return (f && f->magic == 0x46454544u) ? fail(FMGPU_ERR_INVALID, "reads / lens / out / out_count / out_hits is null") : fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    Batch b; b.reads = reads; b.lens = lens; b.nq = nq;
+    return feed_map(f, b, what, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats);
 }
 
 }  // extern "C"

@@ -14,6 +14,9 @@
 //     complements are made on the device while packing (fmgpu_queries_pack4) instead of on the host.  The output is the same, byte for byte.
 //   * --feed (not in the reference): `noerror` and `ng26` (mode all) search through an fmc::Feed — the reads go to the device chunk by chunk, upload, search and
 //     download overlapped, the Sequences object is not flattened; with --packed the packed batch goes through the feed.  The output is the same, byte for byte.
+//   * --mode map (not in the reference): search, callback order and locate as ONE fmgpu_map call (fmc::map) — `noerror` as exact search, `ng26` / `ng21` as the best-hit
+//     ladder of `besthits`; with --feed through fmgpu_feed_map_v (fmc::Feed::map), chunk by chunk.  --save_output then holds "queryId seqId pos errors" per located row,
+//     in the reference's report order (fmc::Search's reportFunc arguments).
 #include "../../include/fmc_gpu.hpp"
 
 #include <algorithm>
@@ -36,7 +39,7 @@ namespace {
 // What the reference's example accepts (its argp.h), described as a table: flag, whether a value follows, what the value does.  Numbers are
 // read as floating point and truncated, so "--queries 1e5" works as it does there; a flag that needs a value but is the last token, and any
 // token that is no flag, is reported as "unknown commandline <token>".
-enum class HitMode { all, besthits };
+enum class HitMode { all, besthits, map };
 struct Options {
     std::string referenceFasta, readsFasta, outputFile;
     std::vector<std::string> algorithms;
@@ -78,7 +81,8 @@ FlagRule const kFlags[] = {
          std::string const m = v;
          if (m == "all") o.hitMode = HitMode::all;
          else if (m == "besthits") o.hitMode = HitMode::besthits;
-         else throw std::runtime_error("invalid mode \"" + m + "\", must be any of \"all\", \"besthits\"");
+         else if (m == "map") o.hitMode = HitMode::map;
+         else throw std::runtime_error("invalid mode \"" + m + "\", must be any of \"all\", \"besthits\", \"map\"");
      }},
     {"--no-reverse", false, [](Options& o, char const*) { o.withReverseComplement = false; }},
     {"--convertUnknownChar", false, [](Options& o, char const*) { o.unknownToA = true; }},
@@ -291,8 +295,46 @@ struct Run {
         return placed;
     }
 
+    // --mode map: the whole path as one fmgpu_map call (with --feed: fmgpu_feed_map_v); a packed batch goes through a feed as bytes
+    template <typename Queries>
+    fmc::MapResult mapThroughFeed(Queries const& reads, fmc::MapQuery const& query) const { return fmc::Feed{index}.map(reads, query); }
+    fmc::MapResult mapThroughFeed(fmc::PackedQueries const& reads, fmc::MapQuery const& query) const { return fmc::Feed{index}.map(reads.unpack(), query); }
+
+    template <typename Queries>
+    void oneErrorBudgetMapped(Algorithm kind, size_t k, Queries const& reads, size_t firstLength) const {
+        StopWatch clock;
+        fmc::MapQuery query;
+        if (config.hitsPerRead != 0) query.maxResults = config.hitsPerRead;
+        if (kind == Algorithm::ng26) {
+            query.kind = fmc::MapQuery::Kind::Schemes;
+            for (size_t j = 0; j <= k; ++j) query.schemes.emplace_back(schemeByName(config.schemeName, j, j), std::vector<size_t>{});
+        } else if (kind == Algorithm::ng21) {
+            query.kind = fmc::MapQuery::Kind::Ng21;
+            for (size_t j = 0; j <= k; ++j) query.expanded.push_back(stretch(schemeByName(config.schemeName, j, j), firstLength));
+        }
+        auto const mapped = config.feed ? mapThroughFeed(reads, query) : fmc::map(index, reads, query);
+        double const tMap = clock.reset();
+
+        std::vector<Placement> distinct;
+        distinct.reserve(mapped.positions.size());
+        for (auto const& p : mapped.positions) distinct.push_back({static_cast<size_t>(p.qidx), static_cast<uint32_t>(p.seq_id), static_cast<size_t>(p.pos), p.errors});
+        std::sort(distinct.begin(), distinct.end());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        std::unordered_set<size_t> readsWithHits;
+        for (auto const& h : mapped.hits) readsWithHits.insert(h.qidx > reads.size() / 2 ? h.qidx - reads.size() / 2 : h.qidx);
+        std::printf("%-15s %3zu: %10.3gs (%10.3gs+%10.3gs) %10.3gq/s - results: %10zu/%10zu/%10zu/%10zu - mem: %13zu\n", "str", k, tMap, tMap, 0.0,
+                    reads.size() / tMap, mapped.positions.size(), mapped.positions.size(), distinct.size(), readsWithHits.size(), size_t{0});
+        if (config.outputFile.empty()) return;
+        auto* out = std::fopen(config.outputFile.c_str(), "w");
+        if (!out) throw std::runtime_error("cannot write " + config.outputFile);
+        for (auto const& p : mapped.positions)
+            std::fprintf(out, "%zu %zu %zu %zu\n", static_cast<size_t>(p.qidx), static_cast<size_t>(static_cast<uint32_t>(p.seq_id)), static_cast<size_t>(p.pos), static_cast<size_t>(p.errors));
+        std::fclose(out);
+    }
+
     template <typename Queries>
     void oneErrorBudget(Algorithm kind, size_t k, Queries const& reads, size_t firstLength) const {
+        if (config.hitMode == HitMode::map) return oneErrorBudgetMapped(kind, k, reads, firstLength);
         StopWatch clock;
         auto const hits = search(kind, k, reads, firstLength);
         double const tSearch = clock.reset();
@@ -334,9 +376,10 @@ int main(int argc, char const* const* argv) try {
                     "          --max_k <int> (maximal number of errors)\\\n"
                     "          --stepSize_k <int> (steps of errors)\\\n"
                     "          --no-reverse (don't use reverse compliment)\\\n"
-                    "          --mode [all, besthits] (all: all hits with k errors (default), besthits: all hits with the lowest hit)\\\n"
+                    "          --mode [all, besthits, map] (all: all hits with k errors (default), besthits: all hits with the lowest hit,\\\n"
+                    "                 map: besthits as one search-order-locate call on the device; --save_output gets \"queryId seqId pos errors\")\\\n"
                     "          --packed (search the reads in the 4-bit packed form; reverse complements are made on the device)\\\n"
-                    "          --feed (noerror, ng26: search through a feed, chunk by chunk with upload, search and download overlapped)\\\n"
+                    "          --feed (noerror, ng26, and every algorithm under --mode map: search through a feed, chunk by chunk)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }

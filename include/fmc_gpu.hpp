@@ -1045,6 +1045,122 @@ struct Search {
 };
 template <typename I, typename Q, typename D> Search(I const&, Q const&, bool, size_t, std::optional<size_t>, D const&) -> Search<I, Q, D>;
 
+// fmc::map(index, queries, MapQuery) — include/fmgpu.h: fmgpu_map: the whole path of fmc::Search behind one call.  The search (exact, a best-hit ladder of schemes or of
+// expanded schemes), the callback order and the locate of every row run on the device; the hit records never visit the host in between.  MapResult::positions is in
+// fmc::Search's report order (position.hit indexes MapResult::hits); stratum[q] = the ladder's scheme that found read q (exact search: 0), 255 if none did.
+// MapQuery::search(errors, edit) is the query fmc::Search{index, queries, edit, errors, maxResults} runs: search_no_errors for 0 errors without maxResults, else the single
+// scheme h2(errors + 2, 0, errors) with uniform partitions (`parts` = another number of parts: a batch of 2-symbol reads, which the reference searches with
+// h2(errors + 1, 0, errors), takes parts = errors + 1; a scheme skips the reads that are shorter than its parts);
+// MapQuery::ladder(maxErrors, edit) is h2(k + 2, 0, k) for k = 0 .. maxErrors, the best-stratum mode of a read mapper.
+struct MapQuery {
+    enum class Kind { Exact, Schemes, Ng21 };
+    Kind kind{Kind::Exact};
+    std::vector<std::tuple<search_scheme::Scheme, std::vector<size_t>>> schemes;     // Kind::Schemes: (scheme, partition; empty = uniform per read)
+    std::vector<search_scheme::Scheme> expanded;                                      // Kind::Ng21: expanded schemes (search_scheme::expand)
+    bool   editDistance{true};
+    size_t maxResults{std::numeric_limits<size_t>::max()};
+    bool   locate{true};
+    size_t firstRecords{0};
+
+    static auto search(size_t errors, bool edit = true, std::optional<size_t> maxResults = {}, size_t parts = 0) -> MapQuery {
+        MapQuery q;
+        q.editDistance = edit;
+        if (maxResults) q.maxResults = *maxResults;
+        if (errors == 0 && !maxResults) return q;
+        q.kind = Kind::Schemes;
+        q.schemes.emplace_back(search_scheme::generator::h2(parts ? parts : errors + 2, 0, errors), std::vector<size_t>{});
+        return q;
+    }
+    static auto ladder(size_t maxErrors, bool edit = true) -> MapQuery {
+        MapQuery q;
+        q.kind = Kind::Schemes; q.editDistance = edit;
+        for (size_t k = 0; k <= maxErrors; ++k) q.schemes.emplace_back(search_scheme::generator::h2(k + 2, 0, k), std::vector<size_t>{});
+        return q;
+    }
+};
+struct MapResult {
+    std::vector<fmgpu_position> positions;
+    std::vector<fmgpu_hit>      hits;
+    std::vector<uint8_t>        stratum;
+};
+namespace detail {
+// a MapQuery flattened into the C struct (the arrays live as long as this object)
+struct FlatMapQuery {
+    struct Flat { std::vector<uint64_t> pi, l, u, part; };
+    std::vector<Flat> flat;
+    std::vector<fmgpu_scheme> ladder;
+    std::vector<fmgpu_expanded_scheme> expanded;
+    fmgpu_map_query what{};
+    FlatMapQuery(FlatMapQuery const&) = delete;
+    FlatMapQuery& operator=(FlatMapQuery const&) = delete;
+    explicit FlatMapQuery(MapQuery const& q) {
+        auto append = [](Flat& f, search_scheme::Scheme const& scheme, size_t width) {
+            for (auto const& s : scheme) {
+                if (s.pi.size() != width) throw std::runtime_error("fmindex-collection (gpu): searches of a scheme must have the same number of parts");
+                f.pi.insert(f.pi.end(), s.pi.begin(), s.pi.end()); f.l.insert(f.l.end(), s.l.begin(), s.l.end()); f.u.insert(f.u.end(), s.u.begin(), s.u.end());
+            }
+        };
+        flat.reserve(q.schemes.size() + q.expanded.size());
+        if (q.kind == MapQuery::Kind::Schemes) {
+            for (auto const& [scheme, partition] : q.schemes) {
+                size_t P = scheme.empty() ? 0 : scheme[0].pi.size();
+                auto& f = flat.emplace_back();
+                f.part.assign(partition.begin(), partition.end());
+                append(f, scheme, P);
+                ladder.push_back(fmgpu_scheme{static_cast<int32_t>(scheme.size()), static_cast<int32_t>(P), f.pi.data(), f.l.data(), f.u.data(),
+                                              f.part.empty() ? nullptr : f.part.data(), q.editDistance ? 1 : 0, 0});
+            }
+            what.kind = FMGPU_MAP_SCHEME; what.n_schemes = static_cast<int32_t>(ladder.size()); what.schemes = ladder.data();
+        } else if (q.kind == MapQuery::Kind::Ng21) {
+            for (auto const& scheme : q.expanded) {
+                size_t len = scheme.empty() ? 0 : scheme[0].pi.size();
+                auto& f = flat.emplace_back();
+                append(f, scheme, len);
+                expanded.push_back(fmgpu_expanded_scheme{static_cast<int32_t>(scheme.size()), 0, len, f.pi.data(), f.l.data(), f.u.data()});
+            }
+            what.kind = FMGPU_MAP_NG21; what.n_schemes = static_cast<int32_t>(expanded.size()); what.schemes = expanded.data();
+        }
+        what.max_hits_per_query = q.maxResults == std::numeric_limits<size_t>::max() ? UINT64_MAX : q.maxResults;
+        what.locate = q.locate ? 1 : 0;
+        what.first_records = q.firstRecords;
+    }
+};
+// the call into vectors: the counts are exact also on FMGPU_ERR_CAPACITY, so a second call with them fits
+template <typename Call>
+auto run_map(size_t nq, bool locate, Call&& call) -> MapResult {
+    MapResult r;
+    r.stratum.assign(nq, 255);
+    uint64_t cap = locate ? std::max<uint64_t>(1024, 4 * nq) : 0, hcap = std::max<uint64_t>(1024, 4 * nq), count = 0, hcount = 0;
+    for (int round = 0; round < 2; ++round) {
+        r.positions.resize(cap); r.hits.resize(hcap);
+        int rc = call(r.positions.data(), cap, &count, r.hits.data(), hcap, &hcount, r.stratum.data());
+        if (rc == FMGPU_ERR_CAPACITY && round == 0) { cap = std::max(cap, count); hcap = std::max(hcap, hcount); continue; }
+        check(rc);
+        break;
+    }
+    r.positions.resize(count); r.hits.resize(hcount);
+    return r;
+}
+}  // namespace detail
+template <typename Index, typename Queries>
+auto map(Index const& index, Queries const& queries, MapQuery const& query) -> MapResult {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    size_t nq = off.size() - 1;
+    detail::FlatMapQuery flat{query};
+    return detail::run_map(nq, query.locate, [&](fmgpu_position* out, uint64_t cap, uint64_t* count, fmgpu_hit* hits, uint64_t hcap, uint64_t* hcount, uint8_t* stratum) {
+        return fmgpu_map(index.handle, buf.data(), off.data(), nq, &flat.what, out, cap, count, hits, hcap, hcount, stratum, nullptr, nullptr, nullptr);
+    });
+}
+template <typename Index>
+auto map(Index const& index, PackedQueries const& queries, MapQuery const& query) -> MapResult {
+    size_t nq = queries.size();
+    detail::FlatMapQuery flat{query};
+    return detail::run_map(nq, query.locate, [&](fmgpu_position* out, uint64_t cap, uint64_t* count, fmgpu_hit* hits, uint64_t hcap, uint64_t* hcount, uint8_t* stratum) {
+        return fmgpu_map_q4(index.handle, queries.packed.data(), queries.qoff.data(), nq, &flat.what, out, cap, count, hits, hcap, hcount, stratum, nullptr, nullptr, nullptr);
+    });
+}
+
 // A feed (include/fmgpu.h: fmgpu_feed_*): host batches searched chunk by chunk on one index, upload, search and download overlapped.  What a caller that holds its
 // queries in host memory — the reference's Sequences — should search through: `fmc::Feed feed{index}; feed.search_no_errors(queries, delegate);`.  A Sequences object
 // (reads of one-byte symbols, each contiguous) goes down through the `_v` calls without being flattened, a PackedQueries through `_q4`.  The delegates are called as by
@@ -1108,6 +1224,17 @@ struct Feed {
     void search_ng26(PackedQueries const& queries, search_scheme::Scheme const& scheme, std::vector<size_t> const& partition, Delegate&& delegate,
                      size_t n = std::numeric_limits<size_t>::max()) const {
         search_ng26<Edit>(queries.unpack(), scheme, partition, std::forward<Delegate>(delegate), n);
+    }
+    // fmc::map chunk by chunk (fmgpu_feed_map_v): the same MapResult, the device-side hit and position buffers bounded by the chunk
+    template <typename Queries>
+    auto map(Queries const& queries, MapQuery const& query) const -> MapResult {
+        std::vector<uint8_t const*> reads; std::vector<uint64_t> lens;
+        scattered(queries, reads, lens);
+        size_t nq = reads.size();
+        detail::FlatMapQuery flat{query};
+        return detail::run_map(nq, query.locate, [&](fmgpu_position* out, uint64_t cap, uint64_t* count, fmgpu_hit* hits, uint64_t hcap, uint64_t* hcount, uint8_t* stratum) {
+            return fmgpu_feed_map_v(handle, reads.data(), lens.data(), nq, &flat.what, out, cap, count, hits, hcap, hcount, stratum, nullptr, nullptr);
+        });
     }
 
   private:

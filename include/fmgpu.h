@@ -569,6 +569,58 @@ int fmgpu_hits_pack24(const fmgpu_hit* hits, uint64_t count, uint64_t* out, void
  * seq = position of the record within its query, errors = the error count (upper bits cleared). */
 int fmgpu_hits_sort(fmgpu_hit* hits, uint64_t count, void* stream);
 
+/* ---- map: search, order and locate in one call ------------------------------------------------------------------------------------------------
+ * fmc::Search{index, queries, editDistance, errors, maxResults, reportFunc}() (search/search.h:48-75) behind one call: reads in, (qidx, seqId, pos, errors) out.  The
+ * pieces are the calls above — exact search or a best-stratum ladder, fmgpu_hits_sort or fmgpu_hits_from_intervals, fmgpu_locate_hits — chained on the device: the hit
+ * records never visit the host between them, and the capacity-retry loop every caller of the pieces writes lives here once.
+ *   - The hit list H: kinds FMGPU_MAP_SCHEME / FMGPU_MAP_NG21: exactly the records of fmgpu_search_best / fmgpu_search_best_ng21 with these schemes and
+ *     max_hits_per_query, after fmgpu_hits_sort (n_schemes = 1 is the single-scheme call).  Kind FMGPU_MAP_EXACT: fmgpu_hits_from_intervals(lb, len, qoff, nq, 0,
+ *     max_hits_per_query) over the results of fmgpu_search_exact.  The position list P = fmgpu_locate_hits(H).
+ *   - Outputs: out = P, out_hits = H, out_stratum as the ladder defines it (kind 0: 0 for a read with a record, 255 otherwise).  P is in fmc::Search's report order:
+ *     ascending qidx, then callback order, then the rows lb .. lb + len - 1; fmgpu_position::hit indexes H.  locate == 0 stops after H: *out_count = 0.
+ *   - Capacity and counts: H and P are always produced in the library's own device scratch, which starts at first_records records (0 = max(1024, 4 x reads)); a stage
+ *     that overflows it grows it to max(count, 2 x size) and reruns (the ladder within its documented n_schemes rounds).  So *out_hit_count and *out_count are exact
+ *     totals, on success and on FMGPU_ERR_CAPACITY alike.  FMGPU_ERR_CAPACITY: P exceeds `capacity`, or out_hits is non-NULL and H exceeds hits_capacity; the contents of
+ *     both output arrays are then unspecified.
+ *   - stats: search_stats[i] = stratum i's fmgpu_stats of the last run (max(1, n_schemes) entries or NULL; kind 0: one entry, fmgpu_search_exact's); locate_stats (one
+ *     entry or NULL) = what fmgpu_locate_hits reports.
+ *   - Errors: codes and messages of the pieces, unchanged: a bad scheme, a unidirectional handle for kinds 1 and 2, an index without an annotated array when locate != 0,
+ *     sigma > 15 for `_q4`, null pointers (what / qbuf / qoff / out_count; out while capacity > 0; out_hits while hits_capacity > 0).  kind, n_schemes (kinds 1, 2: 1 .. 254,
+ *     kind 0: 0) and reserved are checked first (FMGPU_ERR_INVALID), then the schemes.  nq == 0 returns 0 with zero counts and leaves a non-NULL out_stratum untouched,
+ *     decided before the handle is looked at.
+ *   - Every buffer may be host or device memory.  The call returns after completion, frees its scratch and uses no stream of its own.
+ *   - `_q4`: `packed` in place of qbuf, the rules of the other `_q4` calls.
+ *
+ * fmgpu_hits_from_intervals: the intervals of an exact search as hit records, in three device passes (flags, scan, scatter).
+ *   - Read q produces a record iff len[q] > 0, max_rows_per_query > 0 and — qoff given (nq + 1 entries) — qoff[q + 1] > qoff[q].  DEVIATION: an empty read's cursor is
+ *     the whole index and the reference would locate every row of it; here an empty read produces nothing, which is the best-stratum ladder's rule.
+ *   - The record: {qidx = qidx_base + q, lb = lb[q], lb_rev = 0, len = min(len[q], max_rows_per_query), errors = 0, seq = 0}; one per producing read, ascending q.
+ *   - *out_count is set on success and on FMGPU_ERR_CAPACITY alike; nothing is written to `out` when it exceeds `capacity`.  out_stratum (nq entries or NULL):
+ *     out_stratum[q] = 0 if read q produced a record, else 255.  nq == 0 returns 0 with *out_count = 0.  At most 2^31 - 2 reads (FMGPU_ERR_UNSUPPORTED).
+ *   - Host or device memory; asynchronous on `stream` for device buffers except for the one read-back of the count. */
+#define FMGPU_MAP_EXACT  0
+#define FMGPU_MAP_SCHEME 1   /* a ladder of fmgpu_scheme */
+#define FMGPU_MAP_NG21   2   /* a ladder of fmgpu_expanded_scheme */
+typedef struct fmgpu_map_query {
+    int32_t  kind;               /* FMGPU_MAP_EXACT = 0, FMGPU_MAP_SCHEME = 1 (fmgpu_scheme ladder), FMGPU_MAP_NG21 = 2 (fmgpu_expanded_scheme ladder) */
+    int32_t  n_schemes;          /* kinds 1, 2: 1 .. 254 (1 = a single scheme); kind 0: must be 0 */
+    const void* schemes;         /* kinds 1, 2: n_schemes entries of the kind's scheme struct; kind 0: NULL */
+    uint64_t max_hits_per_query; /* n of search_n; UINT64_MAX = unlimited */
+    int32_t  locate;             /* 0: stop after the ordered hit records (no positions computed, *out_count = 0) */
+    int32_t  reserved;           /* 0 */
+    uint64_t first_records;      /* records the library's own hit / position scratch holds at first; 0 = max(1024, 4 x reads of the call or chunk) */
+} fmgpu_map_query;               /* 40 bytes */
+int fmgpu_map(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what,
+              fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+              fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+              uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, void* stream);
+int fmgpu_map_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what,
+                 fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                 fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                 uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, void* stream);
+int fmgpu_hits_from_intervals(const uint64_t* lb, const uint64_t* len, const uint64_t* qoff, uint64_t nq, uint64_t qidx_base,
+                              uint64_t max_rows_per_query, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, void* stream);
+
 /* GPU index construction from sequences — replaces FMIndex(Sequences, samplingRate, threads) (fmindex/FMIndex.h:58-104) and
  * BiFMIndex(Sequences, samplingRate, threads) (fmindex/BiFMIndex.h:107-167), i.e. libsais (utils.h:97-129) + the String /
  * SparseArray constructors.  Sequence i = seqs[seq_off[i] .. seq_off[i+1]); a 0 delimiter follows every sequence
@@ -646,7 +698,14 @@ int fmgpu_replicas_locate(fmgpu_replicas_t r, const uint64_t* rows, uint64_t cou
  *   - Errors: codes and messages for a null handle (fmgpu_feed_create), null pointers, a bad scheme, a unidirectional handle and sigma > 15 for `_q4` are those of the
  *     one-shot calls.  nq == 0 returns 0 and touches nothing.  A failing HIP call stops the enqueuing, drains the three streams and returns its code; the feed can
  *     still be destroyed afterwards.
- * Not served through a feed: search_ng21, best-stratum search, backtracking, smems, locate; feeds over replicas. */
+ *   - fmgpu_feed_map / fmgpu_feed_map_v: fmgpu_map chunk by chunk.  Per chunk, on the compute stream: the search (a ladder or exact search), the ordering
+ *     (fmgpu_hits_sort or fmgpu_hits_from_intervals), fmgpu_locate_hits if `locate` is set, and a rebase (qidx counts in the caller's batch, fmgpu_position::hit in the
+ *     batch-wide H); the download stream then takes H, P and the chunk's out_stratum slice.  P, H and out_stratum equal, element for element, what fmgpu_map returns for the
+ *     flattened batch (chunks are runs of consecutive reads: the sorted chunks one after another are the sorted batch); the counts are batch totals, exact on success and
+ *     on FMGPU_ERR_CAPACITY alike, and every chunk still runs; stats are sums over the chunks.  The slots hold device and pinned buffers for hits, positions and strata
+ *     that only ever grow (fmgpu_feed_info counts them); first_records applies per chunk, and a buffer too small for its chunk is grown and the stage rerun.  Pinned
+ *     outputs are written in place.  Host memory only, the errors of fmgpu_map, one call at a time; no further stream.
+ * Not served through a feed: backtracking, smems, fmgpu_search_hamming_sm, `_q4` batches for map; feeds over replicas. */
 typedef struct fmgpu_feed* fmgpu_feed_t;
 typedef struct fmgpu_feed_config {
     uint64_t chunk_reads;    /* 0 = default */
@@ -672,6 +731,14 @@ int fmgpu_feed_search_scheme  (fmgpu_feed_t f, const uint8_t* qbuf, const uint64
 int fmgpu_feed_search_scheme_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t* lens, uint64_t nq,
                                const fmgpu_scheme* scheme, uint64_t max_hits_per_query,
                                fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats);
+int fmgpu_feed_map  (fmgpu_feed_t f, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what,
+                     fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                     fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                     uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats);
+int fmgpu_feed_map_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t* lens, uint64_t nq, const fmgpu_map_query* what,
+                     fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                     fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                     uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats);
 int fmgpu_feed_info(fmgpu_feed_t f, uint64_t* pinned_bytes, uint64_t* device_bytes,
                     uint64_t* last_chunks, uint64_t* last_staged_bytes, uint64_t* last_uploaded_bytes);
 
