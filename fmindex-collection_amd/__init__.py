@@ -14,12 +14,13 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import FmgpuError, DeviceBuffer, PinnedBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE
+from .capi import FmgpuError, DeviceBuffer, PinnedBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE, TEXT_SPAN_DTYPE
 from . import search_scheme  # noqa: F401
 
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
-           "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer"]
+           "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer",
+           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "TextError", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
 
 
 class _Options:
@@ -1228,3 +1229,156 @@ def reconstruct_text(index, seq_nbr=None):
             index.accelerate_extract(False)
     texts = [sym[int(off[i]): int(off[i + 1])] for i in range(len(pick))]
     return texts[0] if seq_nbr is not None else texts
+
+
+# ---- query text (fmgpu_queries_parse): LINES / FASTA / FASTQ bytes -> (qbuf, qoff) on the device --------------------------------------------
+LINES, FASTA, FASTQ = capi.TEXT_LINES, capi.TEXT_FASTA, capi.TEXT_FASTQ
+DROP, FOREIGN = capi.SYM_DROP, capi.SYM_FOREIGN
+_TEXT_FORMATS = {"lines": LINES, "fasta": FASTA, "fastq": FASTQ}
+
+
+def symbol_table(letters="ACGT", first_rank=1, case_insensitive=True, other=FOREIGN, drop=b"", extra={}):
+    """the 256-entry uint8 table fmgpu_queries_parse maps sequence bytes through: letters[i] -> first_rank + i (both cases unless case_insensitive is False), the bytes
+    of `drop` -> DROP (they produce nothing), `extra` = {byte or one-character string: value} on top, every other byte -> `other` (FOREIGN: written as 255 and counted)"""
+    t = np.full(256, other, dtype=np.uint8)
+    for i, ch in enumerate(letters):
+        for c in ((ch.upper(), ch.lower()) if case_insensitive else (ch,)):
+            t[ord(c)] = first_rank + i
+    for b in (drop.encode() if isinstance(drop, str) else bytes(drop)):
+        t[b] = DROP
+    for k, v in extra.items():
+        t[ord(k) if isinstance(k, str) else int(k)] = v
+    return t
+
+
+def _dna5(unknown_to_a=False):
+    """$ A C G T = 0 .. 4 (the example's and the datasets' ranks); any other byte is FOREIGN, or rank 1 with unknown_to_a (the example's --convertUnknownChar)"""
+    return symbol_table("ACGT", 1, True, 1 if unknown_to_a else FOREIGN, extra={"$": 0})
+
+
+def _dna6(unknown_to_n=False):
+    """$ A C G T N = 0 .. 5; any other byte is FOREIGN, or rank 5 with unknown_to_n"""
+    return symbol_table("ACGTN", 1, True, 5 if unknown_to_n else FOREIGN, extra={"$": 0})
+
+
+def _protein(letters="ACDEFGHIKLMNPQRSTVWY", **kw):
+    """the amino-acid letters in alphabetical order = ranks 1 .. 20 ('$' = 0); keyword arguments as symbol_table's (e.g. extra={"X": 21}, drop=b"*-")"""
+    kw.setdefault("extra", {"$": 0})
+    return symbol_table(letters, 1, **kw)
+
+
+symbol_table.dna5, symbol_table.dna6, symbol_table.protein = _dna5, _dna6, _protein
+
+
+class TextError(FmgpuError):
+    """a text error of fmgpu_queries_parse: `.line` (0-based) and `.offset` of the first offending line"""
+
+    def __init__(self, code, msg, line, offset):
+        super().__init__(code, msg)
+        self.line, self.offset = line, offset
+
+
+class ParsedQueries:
+    """what parse_queries returns: qbuf / qoff (numpy arrays, or DeviceBuffers with device=True), `batch` = (qbuf, qoff) as the search calls take it, reads / symbols,
+    names / quals (TEXT_SPAN_DTYPE arrays of spans into the text, or None), consumed (where the next chunk starts) and foreign (symbols written as 255)"""
+
+    def __init__(self, qbuf, qoff, result, names, quals):
+        self.qbuf, self.qoff, self.names, self.quals = qbuf, qoff, names, quals
+        self.reads, self.symbols, self.consumed, self.foreign = int(result.reads), int(result.symbols), int(result.consumed), int(result.foreign)
+
+    @property
+    def batch(self):
+        return self.qbuf, self.qoff
+
+    @staticmethod
+    def texts(data, spans):
+        """the bytes of each span of `data` (the text the spans were made from)"""
+        view = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1)
+        return [bytes(view[int(s["offset"]): int(s["offset"] + s["len"])]) for s in spans]
+
+
+def _text_buffer(data):
+    """(void*, bytes, keep-alive) of bytes, a numpy array, a torch tensor (host, pinned or device) or a DeviceBuffer / (ptr, nbytes) device view"""
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        data = np.frombuffer(data, dtype=np.uint8)
+    if isinstance(data, np.ndarray):
+        data = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    p, n = _buffer(data)
+    return p, n, data
+
+
+def parse_queries(data, format, table, final=True, device=False, want_names=False, want_quals=False, stream=None):
+    """fmgpu_queries_parse: the bytes of a read file (or of a chunk of one: final=False, continue at `.consumed`) -> ParsedQueries.  format: LINES / FASTA / FASTQ or
+    their lower-case names; table: symbol_table(...).  `data`: bytes, a numpy array, a torch tensor (host, pinned or device) or a DeviceBuffer.  device=True leaves qbuf / qoff
+    in HBM as DeviceBuffers, which every search call, pack_queries_device and map_reads take as they are.  A text error raises TextError with the line number."""
+    fmt = _TEXT_FORMATS[format] if isinstance(format, str) else int(format)
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.uint8))
+    if table.size != 256:
+        raise ValueError("a symbol table has 256 entries")
+    p, nbytes, alive = _text_buffer(data)
+    staged = None
+    if nbytes and isinstance(alive, np.ndarray):              # host text: uploaded once for the two calls below
+        staged = DeviceBuffer.from_array(alive)
+        p = capi.ptr(staged)
+    L, res = capi.lib(), capi.ParseResult()
+
+    def call(qbuf, ncap, qoff, rcap, names, quals):
+        rc = L.fmgpu_queries_parse(p, nbytes, fmt, 1 if final else 0, capi.ptr(table), capi.ptr(qbuf), ncap, capi.ptr(qoff), rcap, capi.ptr(names), capi.ptr(quals), C.byref(res), stream)
+        if rc == capi.FMGPU_ERR_INVALID and L.fmgpu_last_error().startswith(b"text error"):
+            raise TextError(rc, L.fmgpu_last_error().decode("utf-8", "replace"), int(res.error_line), int(res.error_offset))
+        capi.check(rc)
+
+    call(None, 0, None, 0, None, None)                        # the counting call sizes the outputs exactly
+    reads, symbols = int(res.reads), int(res.symbols)
+    if device:
+        qbuf, qoff = DeviceBuffer(max(symbols, 8)), DeviceBuffer((reads + 1) * 8)
+    else:
+        qbuf, qoff = np.zeros(max(symbols, 1), dtype=np.uint8), np.zeros(reads + 1, dtype=np.uint64)
+    names = np.zeros(reads, dtype=capi.TEXT_SPAN_DTYPE) if want_names else None
+    quals = np.zeros(reads, dtype=capi.TEXT_SPAN_DTYPE) if want_quals else None
+    call(qbuf, symbols, qoff, reads, names, quals)
+    del alive, staged
+    return ParsedQueries(qbuf, qoff, res, names, quals)
+
+
+def parse_stream(fileobj, format, table, chunk_bytes=64 << 20, max_chunk_bytes=1 << 30, device=False, want_names=False, want_quals=False):
+    """a generator of ParsedQueries over a binary file object: the file is read chunk by chunk into ONE pinned buffer (fmgpu_malloc_host), each chunk is parsed with
+    final=False and its unconsumed tail is carried to the front of the buffer; only the last chunk is final.  A chunk that holds no complete read makes the buffer grow
+    (doubling, up to max_chunk_bytes; beyond that ValueError).  With want_names / want_quals a batch carries `name_texts` / `qual_texts` (lists of bytes): the spans
+    point into the buffer, which the next chunk overwrites."""
+    size = max(int(chunk_bytes), 16)
+    pinned = PinnedBuffer(size)
+    try:
+        buf, fill, eof = pinned.array(np.uint8), 0, False
+        while not eof:
+            while fill < size:
+                got = fileobj.readinto(memoryview(buf)[fill:size])
+                if not got:
+                    eof = True
+                    break
+                fill += got
+            if eof and fill == 0:
+                break
+            batch = parse_queries(buf[:fill], format, table, final=eof, device=device, want_names=want_names, want_quals=want_quals)
+            if want_names:
+                batch.name_texts = ParsedQueries.texts(buf, batch.names)
+            if want_quals:
+                batch.qual_texts = ParsedQueries.texts(buf, batch.quals)
+            if batch.reads or eof:
+                yield batch
+            tail = fill - batch.consumed
+            if not eof and batch.consumed == 0:               # no complete read in a full buffer: a larger one
+                if size >= max_chunk_bytes:
+                    raise ValueError(f"no complete read in {size} bytes of text (max_chunk_bytes)")
+                bigger = PinnedBuffer(min(2 * size, int(max_chunk_bytes)))
+                bigger.array(np.uint8)[:fill] = buf[:fill]
+                del buf
+                pinned.free()
+                pinned, size = bigger, bigger.nbytes
+                buf = pinned.array(np.uint8)
+            elif batch.consumed:
+                buf[:tail] = buf[batch.consumed:fill].copy()
+            fill = tail
+    finally:
+        buf = None
+        pinned.free()

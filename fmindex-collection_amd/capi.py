@@ -135,6 +135,26 @@ MAP_EXACT, MAP_SCHEME, MAP_NG21 = 0, 1, 2
 assert C.sizeof(MapQuery) == 40
 
 
+class TextSpan(C.Structure):
+    """fmgpu_text_span: bytes offset .. offset + len - 1 of a parsed text (fmgpu_queries_parse: a read's name or quality line)"""
+    _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64)]
+
+
+TEXT_SPAN_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8")])
+assert TEXT_SPAN_DTYPE.itemsize == C.sizeof(TextSpan) == 16
+
+
+class ParseResult(C.Structure):
+    """fmgpu_parse_result: what fmgpu_queries_parse found (written on success, on a capacity error and on a text error alike)"""
+    _fields_ = [("reads", C.c_uint64), ("symbols", C.c_uint64), ("consumed", C.c_uint64), ("foreign", C.c_uint64),
+                ("error_line", C.c_uint64), ("error_offset", C.c_uint64)]
+
+
+assert C.sizeof(ParseResult) == 48
+TEXT_LINES, TEXT_FASTA, TEXT_FASTQ = 0, 1, 2
+SYM_DROP, SYM_FOREIGN = 254, 255
+
+
 # every symbol include/fmgpu.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "fmgpu_abi_version", "fmgpu_last_error", "fmgpu_device_count", "fmgpu_set_device",
@@ -155,6 +175,7 @@ EXPORTS = [
     "fmgpu_feed_create", "fmgpu_feed_destroy", "fmgpu_feed_plan", "fmgpu_feed_search_exact", "fmgpu_feed_search_exact_q4", "fmgpu_feed_search_exact_v",
     "fmgpu_feed_search_scheme", "fmgpu_feed_search_scheme_v", "fmgpu_feed_info", "fmgpu_malloc_host", "fmgpu_free_host",
     "fmgpu_map", "fmgpu_map_q4", "fmgpu_hits_from_intervals", "fmgpu_feed_map", "fmgpu_feed_map_v",
+    "fmgpu_queries_parse",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -299,6 +320,9 @@ def lib():
         L.fmgpu_hits_from_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p]
         L.fmgpu_feed_map.argtypes = L.fmgpu_map.argtypes[:-1]
         L.fmgpu_feed_map_v.argtypes = L.fmgpu_feed_map.argtypes
+    if hasattr(L, "fmgpu_queries_parse"):                     # (FMGPU_LIBRARY may name an older build of the same ABI)
+        L.fmgpu_queries_parse.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                          C.c_void_p, C.c_void_p, C.POINTER(ParseResult), C.c_void_p]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

@@ -17,6 +17,11 @@
 //   * --mode map (not in the reference): search, callback order and locate as ONE fmgpu_map call (fmc::map) — `noerror` as exact search, `ng26` / `ng21` as the best-hit
 //     ladder of `besthits`; with --feed through fmgpu_feed_map_v (fmc::Feed::map), chunk by chunk.  --save_output then holds "queryId seqId pos errors" per located row,
 //     in the reference's report order (fmc::Search's reportFunc arguments).
+//   * --device-parse (not in the reference): the --query file is read as bytes and parsed on the device (fmgpu_queries_parse through fmc::parseQueries); its first byte
+//     chooses FASTA ('>') or FASTQ ('@', read only this way).  On a well-formed FASTA — ends in a newline, no '>' inside sequence lines, no '\r' — the output is the
+//     same, byte for byte.  Elsewhere the device rules differ from the reader below: a '\r' in front of a newline belongs to the line end (the reader takes it for
+//     a symbol), a '>' that is not the first byte of its line is an ordinary byte (the reader starts a record there), a last line without a newline keeps its last
+//     base (the reader drops the file's last byte), and a name line at the very end of the file is an empty read (the reader yields no record).  The --index file keeps the reader below.
 #include "../../include/fmc_gpu.hpp"
 
 #include <algorithm>
@@ -47,7 +52,7 @@ struct Options {
     bool schemeDyn = false;
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false;
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -89,6 +94,7 @@ FlagRule const kFlags[] = {
     {"--help", false, [](Options& o, char const*) { o.wantHelp = true; }},
     {"--packed", false, [](Options& o, char const*) { o.packed = true; }},
     {"--feed", false, [](Options& o, char const*) { o.feed = true; }},
+    {"--device-parse", false, [](Options& o, char const*) { o.deviceParse = true; }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
     {"--ext", true, [](Options&, char const*) {}},
     {"--threads", true, [](Options&, char const*) {}},
@@ -154,6 +160,21 @@ std::vector<std::vector<uint8_t>> readFasta(std::string const& path, size_t sigm
         records.push_back(std::move(ranks));
         if (at + 1 >= size) break;                                 // stopped on the last byte of the file
     }
+    return records;
+}
+
+// --device-parse: the same ranks from the raw bytes of a FASTA or FASTQ file, parsed on the device (the line rules of fmgpu_queries_parse, include/fmgpu.h)
+std::vector<std::vector<uint8_t>> readQueriesOnDevice(std::string const& path, size_t sigma, bool unknownToA) {
+    std::vector<std::vector<uint8_t>> records;
+    if (path.empty() || !std::filesystem::exists(path)) return records;
+    std::ifstream in{path, std::ios::binary};
+    std::string const bytes{std::istreambuf_iterator<char>{in}, std::istreambuf_iterator<char>{}};
+    if (bytes.empty() || (bytes[0] != '>' && bytes[0] != '@')) throw std::runtime_error("can't read fasta file");
+    auto const table = sigma == 6 ? fmc::SymbolTable::dna6(unknownToA) : fmc::SymbolTable::dna5(unknownToA);
+    auto const parsed = fmc::parseQueries(bytes, bytes[0] == '@' ? fmc::TextFormat::Fastq : fmc::TextFormat::Fasta, table);
+    if (parsed.foreign > 0) throw std::runtime_error("unknown alphabet");
+    records.reserve(parsed.size());
+    for (auto const& read : parsed) records.emplace_back(read.begin(), read.end());
     return records;
 }
 
@@ -380,10 +401,13 @@ int main(int argc, char const* const* argv) try {
                     "                 map: besthits as one search-order-locate call on the device; --save_output gets \"queryId seqId pos errors\")\\\n"
                     "          --packed (search the reads in the 4-bit packed form; reverse complements are made on the device)\\\n"
                     "          --feed (noerror, ng26, and every algorithm under --mode map: search through a feed, chunk by chunk)\\\n"
+                    "          --device-parse (parse the query file on the device; FASTA or FASTQ by its first byte, '>' or '@'.  Same output on a\\\n"
+                    "                 well-formed FASTA.  Unlike the default reader: \"\\r\\n\" ends a line, a '>' inside a line is an ordinary byte,\\\n"
+                    "                 a last line without a newline keeps its last base, a name line at the end of the file is an empty read)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }
-    auto reads = readFasta(config.readsFasta, Sigma, config.unknownToA);
+    auto reads = config.deviceParse ? readQueriesOnDevice(config.readsFasta, Sigma, config.unknownToA) : readFasta(config.readsFasta, Sigma, config.unknownToA);
     // --packed: both strands come out of the device packer, unless reads get trimmed (the reference trims the doubled batch, and a trimmed reverse
     // complement is not the reverse complement of the trimmed read: then the strands are made here and only packed)
     bool const trims = config.trimTo != 0 && std::any_of(reads.begin(), reads.end(), [&](auto const& r) { return r.size() > config.trimTo; });

@@ -24,7 +24,9 @@
 #include <numeric>
 #include <optional>
 #include <stdexcept>
+#include <iterator>
 #include <string>
+#include <string_view>
 #include <tuple>
 #include <type_traits>
 #include <utility>
@@ -614,6 +616,97 @@ struct PackedQueries {
         return out;
     }
 };
+
+// ---- query text (include/fmgpu.h: fmgpu_queries_parse) ------------------------------------------------------------------------------------------
+// The bytes of a read file — one read per line, FASTA or FASTQ — parsed on the device: `auto reads = fmc::parseQueries(text, fmc::TextFormat::Fastq,
+// fmc::SymbolTable::dna5());`.  A SymbolTable says what every byte of a sequence line becomes: a rank, nothing (Drop), or 255 counted as foreign (Foreign).
+enum class TextFormat : int32_t { Lines = FMGPU_TEXT_LINES, Fasta = FMGPU_TEXT_FASTA, Fastq = FMGPU_TEXT_FASTQ };
+struct SymbolTable {
+    static constexpr uint8_t Drop = FMGPU_SYM_DROP, Foreign = FMGPU_SYM_FOREIGN;
+    std::array<uint8_t, 256> map;
+    // letters[i] -> firstRank + i (both cases unless caseInsensitive is false), the bytes of `drop` -> Drop, every other byte -> other
+    explicit SymbolTable(std::string_view letters = "ACGT", uint8_t firstRank = 1, bool caseInsensitive = true, uint8_t other = Foreign, std::string_view drop = {}) {
+        map.fill(other);
+        for (size_t i = 0; i < letters.size(); ++i) {
+            auto const c = static_cast<unsigned char>(letters[i]);
+            auto const rank = static_cast<uint8_t>(firstRank + i);
+            map[c] = rank;
+            if (caseInsensitive && c >= 'A' && c <= 'Z') map[c - 'A' + 'a'] = rank;
+            if (caseInsensitive && c >= 'a' && c <= 'z') map[c - 'a' + 'A'] = rank;
+        }
+        for (char c : drop) map[static_cast<unsigned char>(c)] = Drop;
+    }
+    auto set(char byte, uint8_t value) -> SymbolTable& { map[static_cast<unsigned char>(byte)] = value; return *this; }
+    // $ A C G T = 0 .. 4, the ranks of the example and the datasets; any other byte is Foreign, or rank 1 (the example's --convertUnknownChar)
+    static auto dna5(bool unknownToA = false) -> SymbolTable { return SymbolTable{"ACGT", 1, true, unknownToA ? uint8_t{1} : Foreign}.set('$', 0); }
+    // $ A C G T N = 0 .. 5; any other byte is Foreign, or rank 5
+    static auto dna6(bool unknownToN = false) -> SymbolTable { return SymbolTable{"ACGTN", 1, true, unknownToN ? uint8_t{5} : Foreign}.set('$', 0); }
+    // the amino-acid letters in alphabetical order = ranks 1 .. 20, $ = 0
+    static auto protein(std::string_view letters = "ACDEFGHIKLMNPQRSTVWY") -> SymbolTable { return SymbolTable{letters}.set('$', 0); }
+};
+
+// What parseQueries returns: the batch in the byte form plus where each read's name and quality line lie in the text.  It is a range of reads (contiguous one-byte
+// symbols), so every search call, PackedQueries::pack / packOnDevice, fmc::map and a Feed take it wherever they take a Sequences object.  Like
+// PackedQueries::packOnDevice the work happens on the device and the batch comes back to host vectors, which is what the calls of this mirror are handed.
+struct ParsedQueries {
+    struct Read {
+        uint8_t const* first; size_t count;
+        auto data() const -> uint8_t const* { return first; }
+        auto size() const -> size_t { return count; }
+        auto empty() const -> bool { return count == 0; }
+        auto begin() const -> uint8_t const* { return first; }
+        auto end() const -> uint8_t const* { return first + count; }
+        auto rbegin() const { return std::reverse_iterator<uint8_t const*>{end()}; }
+        auto rend() const { return std::reverse_iterator<uint8_t const*>{begin()}; }
+        auto operator[](size_t i) const -> uint8_t { return first[i]; }
+    };
+    struct iterator {
+        ParsedQueries const* batch; size_t q;
+        auto operator*() const -> Read { return (*batch)[q]; }
+        auto operator++() -> iterator& { ++q; return *this; }
+        bool operator!=(iterator const& o) const { return q != o.q; }
+        bool operator==(iterator const& o) const { return q == o.q; }
+    };
+    std::vector<uint8_t> qbuf;
+    std::vector<uint64_t> qoff{0};
+    std::vector<fmgpu_text_span> names, quals;
+    uint64_t consumed{0}, foreign{0};                                 // where the next chunk of the text starts; symbols written as 255
+
+    auto size() const -> size_t { return qoff.size() - 1; }
+    auto operator[](size_t q) const -> Read { return {qbuf.data() + qoff[q], static_cast<size_t>(qoff[q + 1] - qoff[q])}; }
+    auto begin() const -> iterator { return {this, 0}; }
+    auto end() const -> iterator { return {this, size()}; }
+    // the name (the header line without its first byte) and the quality line of read q, as views into the text that was parsed
+    auto name(std::string_view text, size_t q) const -> std::string_view { return text.substr(names[q].offset, names[q].len); }
+    auto quality(std::string_view text, size_t q) const -> std::string_view { return text.substr(quals[q].offset, quals[q].len); }
+};
+
+// final = false: `text` is a chunk of a longer input; only the records it proves complete are parsed and the next chunk starts at `.consumed`.
+// A text error throws std::runtime_error naming the line.
+inline auto parseQueries(std::string_view text, TextFormat format, SymbolTable const& table, bool final = true) -> ParsedQueries {
+    struct DeviceText {                                               // the text goes to the device once for the counting call and the call that writes
+        void* p{nullptr};
+        ~DeviceText() { if (p) fmgpu_free(p); }
+    } staged;
+    auto const* bytes = reinterpret_cast<uint8_t const*>(text.data());
+    if (!text.empty()) {
+        detail::check(fmgpu_malloc(&staged.p, text.size()));
+        detail::check(fmgpu_memcpy_h2d(staged.p, bytes, text.size()));
+        bytes = static_cast<uint8_t const*>(staged.p);
+    }
+    fmgpu_parse_result res{};
+    auto const fmt = static_cast<int32_t>(format);
+    detail::check(fmgpu_queries_parse(bytes, text.size(), fmt, final ? 1 : 0, table.map.data(), nullptr, 0, nullptr, 0, nullptr, nullptr, &res, nullptr));
+    ParsedQueries out;
+    out.qbuf.assign(std::max<size_t>(res.symbols, 1), 0);
+    out.qoff.assign(res.reads + 1, 0);
+    out.names.assign(res.reads, fmgpu_text_span{0, 0});
+    out.quals.assign(res.reads, fmgpu_text_span{0, 0});
+    detail::check(fmgpu_queries_parse(bytes, text.size(), fmt, final ? 1 : 0, table.map.data(), out.qbuf.data(), res.symbols, out.qoff.data(), res.reads,
+                                      out.names.data(), out.quals.data(), &res, nullptr));
+    out.consumed = res.consumed; out.foreign = res.foreign;
+    return out;
+}
 
 namespace search_no_errors {
 template <typename Index, typename Delegate>

@@ -742,6 +742,68 @@ int fmgpu_feed_map_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t
 int fmgpu_feed_info(fmgpu_feed_t f, uint64_t* pinned_bytes, uint64_t* device_bytes,
                     uint64_t* last_chunks, uint64_t* last_staged_bytes, uint64_t* last_uploaded_bytes);
 
+/* ---- query text: LINES / FASTA / FASTQ bytes to a query batch on the device --------------------------------------------------------------
+ * fmgpu_queries_parse turns the raw bytes of a read file (or of a chunk of one) into the byte form every search call takes: out_qbuf (one symbol per byte) and
+ * out_qoff (reads + 1 offsets, out_qoff[0] = 0).  No index handle is involved.  `text` and every output may each be host or device memory (host buffers are staged);
+ * symbol_of is host memory.  The call returns after completion and frees its scratch (about 0.8 byte per text byte for read files).
+ *   Lines
+ *   - The buffer is cut at '\n'.  A '\r' that is the last byte of a line belongs to the terminator and is not part of the line: a '\r' directly in front of
+ *     '\n', or the last byte of a `final` buffer.  Any other '\r' is an ordinary byte.  The last line may lack its '\n'; a buffer that ends in '\n' has no
+ *     further empty line behind it.  Lines are numbered from 0.
+ *   final
+ *   - final != 0: the buffer ends the input, so the last record is complete where the buffer ends.  final == 0: only the records the buffer proves complete are
+ *     parsed, and result->consumed tells where the next chunk starts: a file is parsed chunk by chunk with the unconsumed tail carried over.
+ *   FMGPU_TEXT_LINES
+ *   - Every line is a read, an empty line an empty read.  A line is complete when '\n' ends it, or with `final`.  consumed = the offset just behind the last complete line.
+ *   FMGPU_TEXT_FASTA
+ *   - A line whose first byte is '>' is a header and starts a record; every other non-empty line is a sequence line of the current record (multi-line records);
+ *     empty lines are ignored everywhere; a '>' that is not the first byte of its line is an ordinary byte.  A record without a sequence line is an empty read.
+ *   - A non-empty line in front of the first header is a text error.
+ *   - A record is complete when another header starts behind it inside the buffer, or with `final`.  consumed = the offset of that next header's '>', or `bytes`
+ *     with `final`.  final == 0 and fewer than two headers: the call succeeds with reads == 0, consumed == 0 (the caller needs a larger chunk).
+ *   FMGPU_TEXT_FASTQ
+ *   - Strict four-line records: lines 4r, 4r + 1, 4r + 2, 4r + 3 are header, sequence, separator and quality of read r.  The line's position alone decides its role
+ *     (a quality line that starts with '@' or '+' is a quality line); multi-line FASTQ is not supported.
+ *   - Text errors: a header whose first byte is not '@', a separator whose first byte is not '+', a quality line whose byte length differs from its sequence
+ *     line's (terminators excluded, before any dropping).
+ *   - With `final`, empty lines at the very end of the buffer are discarded first; a line count that is then no multiple of four is a text error (a truncated
+ *     file) at the first line of the incomplete record.  With final == 0 a trailing incomplete record is neither consumed nor validated.
+ *   - consumed = the offset just behind the last complete record's quality line and its terminator.
+ *   Symbols
+ *   - Every byte of a sequence line (terminator excluded) maps through symbol_of[256]: FMGPU_SYM_DROP produces nothing, FMGPU_SYM_FOREIGN is written as 255 (a
+ *     byte outside every alphabet) and counted in result->foreign, any other value is written as it is.  The entries for '\n' and for a terminating '\r' are never
+ *     consulted.  Header, separator and quality bytes produce nothing.  Reads keep the file's order.
+ *   Spans (NULL, or read_capacity entries; offsets relative to `text`)
+ *   - out_names[r] = the header line of read r without its first byte and without its terminator; LINES: {0, 0}.
+ *   - out_quals[r] = the quality line of read r; LINES and FASTA: {0, 0}.
+ *   Counts and capacity
+ *   - *result is written in full once the argument checks pass: on success, on FMGPU_ERR_CAPACITY and on a text error alike.  reads / symbols: the complete
+ *     records and the symbols they produce.  On a text error error_line / error_offset name the FIRST offending line (the lowest one, whatever else is wrong
+ *     behind it), reads / symbols / consumed / foreign describe the records in front of the offending record, and nothing is written to the outputs.
+ *   - FMGPU_ERR_CAPACITY: symbols > symbol_capacity or reads > read_capacity; nothing is written to the outputs.
+ *   - The counting call: out_qbuf == NULL && out_qoff == NULL (and both span pointers NULL) returns 0 with the counts and writes nothing.  A caller sizes its
+ *     buffers exactly with two calls, or takes the bound symbols <= bytes, reads <= bytes.
+ *   Errors
+ *   - FMGPU_ERR_INVALID: a text error; a null result or symbol_of; a null text while bytes > 0; exactly one of out_qbuf / out_qoff null; span pointers in a
+ *     counting call; an unknown format.  These argument checks come before the first use of the device.
+ *   - bytes == 0 returns 0 with a zero result (and out_qoff[0] = 0 if out_qoff is given).
+ *   - bytes > 2^32 - 2: FMGPU_ERR_UNSUPPORTED (positions are 32-bit words on the device): parse in chunks, each starting at the previous call's `consumed`. */
+#define FMGPU_TEXT_LINES 0   /* one read per line */
+#define FMGPU_TEXT_FASTA 1   /* '>' header lines, sequence lines concatenated (multi-line records) */
+#define FMGPU_TEXT_FASTQ 2   /* strict four-line records */
+#define FMGPU_SYM_DROP    254 /* symbol_of value: the byte produces nothing */
+#define FMGPU_SYM_FOREIGN 255 /* symbol_of value: written as 255 (a byte outside every alphabet) and counted */
+typedef struct fmgpu_text_span { uint64_t offset, len; } fmgpu_text_span;   /* bytes of the input buffer */
+typedef struct fmgpu_parse_result {
+    uint64_t reads, symbols;            /* complete records found; symbols they produce */
+    uint64_t consumed;                  /* bytes of the buffer those records span, from byte 0: the next chunk starts here */
+    uint64_t foreign;                   /* symbols written as 255 */
+    uint64_t error_line, error_offset;  /* a text error: 0-based line number and byte offset of the first offending line (0 otherwise) */
+} fmgpu_parse_result;
+int fmgpu_queries_parse(const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of,
+                        uint8_t* out_qbuf, uint64_t symbol_capacity, uint64_t* out_qoff, uint64_t read_capacity,
+                        fmgpu_text_span* out_names, fmgpu_text_span* out_quals, fmgpu_parse_result* result, void* stream);
+
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
 int fmgpu_free(void* ptr);
