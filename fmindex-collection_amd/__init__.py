@@ -20,7 +20,7 @@ from . import search_scheme  # noqa: F401
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer",
-           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "TextError", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
+           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
 
 
 class _Options:
@@ -817,6 +817,80 @@ class Feed:
         res = _run_map(lambda *args: call(self._f, a, b, nq, C.byref(what), *args), nq, what, want_hits, want_stratum, want_stats, out, False)
         del keep, alive
         return res
+
+    def map_text(self, data, format, table, final=True, chunk_bytes=0, want_hits=False, want_stratum=False, want_names=False, want_quals=False, want_lens=False,
+                 want_stats=False, errors=None, schemes=None, ng21=False, edit=True, n=UINT64_MAX, locate=True, first_records=0, out=None, capacities=None):
+        """fmgpu_feed_map_text: the bytes of a read file -> MappedText, what map_reads(parse_queries(data)) returns plus the spans of the whole-text parse.  The text is
+        the only thing uploaded: it travels in windows of chunk_bytes (0 = 64 MiB), each parsed and mapped on the device.  `data`: bytes, a numpy array (an np.memmap
+        included) or a pinned buffer (PinnedBuffer.array(...), copied from where it lies); format / table as parse_queries; the mapping arguments as Feed.map.  The
+        capacities (positions, hit records, reads) start as guesses, or as `capacities`; a capacity error reports the exact totals and the call runs once more with
+        them.  A text error raises TextError."""
+        fmt = _TEXT_FORMATS[format] if isinstance(format, str) else int(format)
+        table = np.ascontiguousarray(np.asarray(table, dtype=np.uint8))
+        if table.size != 256:
+            raise ValueError("a symbol table has 256 entries")
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            data = np.frombuffer(data, dtype=np.uint8)
+        if isinstance(data, np.ndarray):
+            if not data.flags.c_contiguous:
+                data = np.ascontiguousarray(data)
+            text = data.view(np.uint8).reshape(-1)
+            p, nbytes = (text.ctypes.data if text.size else None), text.size
+        else:
+            p, nbytes = _buffer(data)
+            text = data
+        what, alive = _map_query(errors, schemes, ng21, edit, n, locate, first_records)
+        nst = max(1, what.n_schemes)
+        sstats, lstats = (capi.Stats * nst)(), capi.Stats()
+        L, res = capi.lib(), capi.ParseResult()
+        want_reads = want_stratum or want_names or want_quals or want_lens
+        rcap = max(1024, nbytes // 64) if want_reads else 0
+        cap = len(out) if out is not None else (max(1024, 4 * rcap, nbytes // 16) if locate else 0)
+        hcap = max(1024, 4 * rcap, nbytes // 16) if want_hits else 0
+        if capacities is not None:
+            cap, hcap, rcap = (len(out) if out is not None else (int(capacities[0]) if locate else 0)), (int(capacities[1]) if want_hits else 0), (int(capacities[2]) if want_reads else 0)
+        cnt, hcnt = C.c_uint64(), C.c_uint64()
+        for _ in range(2):
+            pos = out if out is not None else np.zeros(max(cap, 1), dtype=POSITION_DTYPE)
+            hits = np.zeros(max(hcap, 1), dtype=HIT_DTYPE) if want_hits else None
+            stratum = np.full(max(rcap, 1), 255, dtype=np.uint8) if want_stratum else None
+            names = np.zeros(max(rcap, 1), dtype=capi.TEXT_SPAN_DTYPE) if want_names else None
+            quals = np.zeros(max(rcap, 1), dtype=capi.TEXT_SPAN_DTYPE) if want_quals else None
+            lens = np.zeros(max(rcap, 1), dtype=np.uint64) if want_lens else None
+            rc = L.fmgpu_feed_map_text(self._f, p, nbytes, fmt, 1 if final else 0, capi.ptr(table), int(chunk_bytes or 0), C.byref(what), capi.ptr(pos), cap, C.byref(cnt),
+                                       capi.ptr(hits), hcap, C.byref(hcnt), capi.ptr(stratum), capi.ptr(names), capi.ptr(quals), capi.ptr(lens), rcap, C.byref(res),
+                                       sstats if want_stats else None, C.byref(lstats) if want_stats else None)
+            if rc != capi.FMGPU_ERR_CAPACITY:
+                break
+            if out is not None and int(cnt.value) > cap:
+                break
+            cap = cap if out is not None else max(cap, int(cnt.value))
+            hcap = max(hcap, int(hcnt.value)) if want_hits else 0
+            rcap = max(rcap, int(res.reads)) if want_reads else 0
+        if rc == capi.FMGPU_ERR_INVALID and L.fmgpu_last_error().startswith(b"text error"):
+            raise TextError(rc, L.fmgpu_last_error().decode("utf-8", "replace"), int(res.error_line), int(res.error_offset))
+        capi.check(rc)
+        del alive, text
+        reads = int(res.reads)
+        m = MappedText()
+        m.positions = pos[: cnt.value]
+        m.hits = np.ascontiguousarray(hits[: hcnt.value]) if want_hits else None
+        m.stratum, m.names, m.quals, m.lens = (None if a is None else a[:reads] for a in (stratum, names, quals, lens))
+        m.reads, m.symbols, m.consumed, m.foreign = reads, int(res.symbols), int(res.consumed), int(res.foreign)
+        m.stats = ([sstats[i] for i in range(nst)], lstats) if want_stats else None
+        return m
+
+    def map_file(self, path, format, table, **kw):
+        """map_text over the file's bytes as they lie in the page cache (np.memmap): the file is never read into a Python object"""
+        if os.path.getsize(path) == 0:
+            return self.map_text(b"", format, table, **kw)
+        return self.map_text(np.memmap(path, dtype=np.uint8, mode="r"), format, table, **kw)
+
+
+class MappedText:
+    """what Feed.map_text returns: positions (POSITION_DTYPE, qidx = the read's number in the text), hits (HIT_DTYPE) / stratum / names / quals / lens where asked for
+    (else None; names and quals are TEXT_SPAN_DTYPE spans into the text), reads / symbols / consumed / foreign of the whole-text parse, stats = (search stats per
+    stratum, locate stats) or None"""
 
 
 class Replicas:

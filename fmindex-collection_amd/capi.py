@@ -175,7 +175,7 @@ EXPORTS = [
     "fmgpu_feed_create", "fmgpu_feed_destroy", "fmgpu_feed_plan", "fmgpu_feed_search_exact", "fmgpu_feed_search_exact_q4", "fmgpu_feed_search_exact_v",
     "fmgpu_feed_search_scheme", "fmgpu_feed_search_scheme_v", "fmgpu_feed_info", "fmgpu_malloc_host", "fmgpu_free_host",
     "fmgpu_map", "fmgpu_map_q4", "fmgpu_hits_from_intervals", "fmgpu_feed_map", "fmgpu_feed_map_v",
-    "fmgpu_queries_parse",
+    "fmgpu_queries_parse", "fmgpu_feed_map_text",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -323,6 +323,10 @@ def lib():
     if hasattr(L, "fmgpu_queries_parse"):                     # (FMGPU_LIBRARY may name an older build of the same ABI)
         L.fmgpu_queries_parse.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                           C.c_void_p, C.c_void_p, C.POINTER(ParseResult), C.c_void_p]
+    if hasattr(L, "fmgpu_feed_map_text"):
+        L.fmgpu_feed_map_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(MapQuery),
+                                          C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ParseResult), C.POINTER(Stats), C.POINTER(Stats)]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

@@ -229,6 +229,18 @@ int map_device(fmgpu_index_t h, const uint8_t* dq, const uint64_t* doff, uint64_
                MapBuffer* intervals, uint8_t* dstratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, hipStream_t stream, uint64_t* hit_count, uint64_t* pos_count);
 // qidx += first in both lists, fmgpu_position::hit += hit_base (low 32 bits): a chunk's records renumbered for the caller's batch
 int map_rebase(fmgpu_hit* hits, uint64_t hit_count, fmgpu_position* positions, uint64_t pos_count, uint64_t first, uint64_t hit_base, hipStream_t stream);
+// fmgpu_queries_parse's passes on device text and growing buffers (fmgpu_parse.hip), shared by the one-shot call and fmgpu_feed_map_text.  names / quals may be null (not
+// wanted); qbuf is asked for symbols + qpad bytes.  `piece`: the text is a feed's piece with a window behind it — what only later bytes can settle stays unconsumed.
+struct ParseBuffers {
+    MapBuffer *acc = nullptr, *lnbase = nullptr, *kcnt = nullptr, *hcnt = nullptr, *tmp = nullptr, *ls = nullptr;      // accumulator, line bases, counts, scan scratch, line starts
+    MapBuffer *qbuf = nullptr, *qoff = nullptr, *names = nullptr, *quals = nullptr;
+    size_t qpad = 0;
+};
+int parse_device(const uint8_t* dtext, uint64_t bytes, int32_t format, int32_t final, int32_t piece, const uint8_t* dtable, ParseBuffers* b, bool counting,
+                 uint64_t symbol_capacity, uint64_t read_capacity, uint64_t line_base, uint64_t offset_base, fmgpu_parse_result* result, uint64_t* next_line,
+                 bool* is_text_error, hipStream_t stream);
+// a piece's spans rebased to the caller's text (offset += base) and lens[r] = qoff[r + 1] - qoff[r]; any of the three arrays may be null
+int parse_piece_spans(fmgpu_text_span* names, fmgpu_text_span* quals, uint64_t* lens, const uint64_t* qoff, uint64_t reads, uint64_t base, int32_t format, hipStream_t stream);
 int hits_from_intervals_on(fmgpu_index_t h, const uint64_t* lb, const uint64_t* len, const uint64_t* qoff, uint64_t nq, uint64_t qidx_base, uint64_t max_rows, fmgpu_hit* out,
                            uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, void* stream);      // fmgpu_hits_from_intervals in the build of the handle's row width
 

@@ -61,7 +61,17 @@ struct Slot {
     uint64_t positions = 0, located = 0;                     // ... map: its positions and the positions of the chunks before it
     bool hits_in_place = false, results_in_place = false;
     bool hits_down = false, pos_down = false, pos_in_place = false, str_down = false, str_in_place = false;      // ... map: what its download carries, and where to
-    Slot() { p_q.pinned = p_off.pinned = p_lb.pinned = p_len.pinned = p_hits.pinned = p_pos.pinned = p_str.pinned = true; }
+    // fmgpu_feed_map_text: the slot's text (the window from byte `headroom` on, the carry in front of it), the parse scratch, the spans and lengths of its reads
+    Grown d_text, d_acc, d_lnbase, d_kcnt, d_hcnt, d_tmp, d_ls, d_names, d_quals, d_rlen;
+    Grown p_text, p_names, p_quals, p_rlen;
+    hipEvent_t ev_text = nullptr;                            // the slot's text has been read: its piece is parsed and what it did not consume is copied out
+    uint64_t headroom = 0, unconsumed = 0;                   // ... and where in d_text the unconsumed bytes start
+    bool reads_down = false, names_in_place = false, quals_in_place = false, rlen_in_place = false;
+    Slot() { p_q.pinned = p_off.pinned = p_lb.pinned = p_len.pinned = p_hits.pinned = p_pos.pinned = p_str.pinned = p_text.pinned = p_names.pinned = p_quals.pinned = p_rlen.pinned = true; }
+    std::vector<Grown*> buffers() {
+        return {&d_q, &d_off, &d_lb, &d_len, &d_hits, &d_pos, &d_str, &p_q, &p_off, &p_lb, &p_len, &p_hits, &p_pos, &p_str,
+                &d_text, &d_acc, &d_lnbase, &d_kcnt, &d_hcnt, &d_tmp, &d_ls, &d_names, &d_quals, &d_rlen, &p_text, &p_names, &p_quals, &p_rlen};
+    }
 };
 
 }  // namespace
@@ -78,6 +88,7 @@ struct fmgpu_feed {
     fmgpu::Slot slot[fmgpu::kMaxSlots];
     std::vector<uint64_t> plan;                              // first read of every chunk of the current call, and nq behind them
     uint64_t hit_hint = 0;                                   // records the largest chunk so far produced: what a slot's hit buffer is sized for before it runs
+    fmgpu::Grown d_table;                                    // fmgpu_feed_map_text: the call's symbol table
     uint64_t pinned_bytes = 0, device_bytes = 0, last_chunks = 0, last_staged = 0, last_uploaded = 0;
 };
 
@@ -484,6 +495,206 @@ int run_map(Feed* f, const Batch& b, const fmgpu_map_query* what, const MapOut& 
     return 0;
 }
 
+// ---- fmgpu_feed_map_text: the raw text travels, piece by piece; every piece is parsed (parse_device, fmgpu_parse.hip) and mapped (map_device) on the compute stream
+// One piece c in slot s = c % slots, on the calling thread:
+//   compute: D2D the carry (what piece c - 1 left) from slot s - 1 into [H - carry, H) of slot s, event T(s - 1)           -> slot s - 1 may take its next window
+//   upload : window c + 1 into slot s + 1 at byte H (after that slot's download D has been waited for and behind its T), event U(s + 1)
+//   compute: wait U(s), parse [H - carry, H + window), event T(s), map, rebase of records and spans, event C -> download: wait C, D2H, event D
+// A window's place does not depend on a parse result: its upload runs beside the parse and the search of the piece before it.
+struct TextOut {
+    MapOut m;
+    fmgpu_text_span* names; fmgpu_text_span* quals; uint64_t* lens;
+    uint64_t read_capacity;
+    bool read_arrays() const { return m.out_stratum || names || quals || lens; }
+};
+
+int retire_text(Feed* f, Slot& sl, const TextOut& o) {
+    if (!sl.busy) return 0;
+    const bool reads_down = sl.reads_down;
+    const uint64_t first = sl.first, reads = sl.reads;
+    if (int rc = retire_map(f, sl, o.m)) return rc;
+    if (!reads_down || !reads) return 0;
+    fh::Workers& w = *f->workers;
+    const auto copy = [&](void* dst, const void* src, size_t bytes) {
+        w.run([&](uint32_t t, uint32_t parts) {
+            const size_t a = (size_t)fh::slice_cut(bytes, parts, t), b = (size_t)fh::slice_cut(bytes, parts, t + 1);
+            if (b > a) std::memcpy((uint8_t*)dst + a, (const uint8_t*)src + a, b - a);
+        });
+        f->last_staged += bytes;
+    };
+    if (o.names && !sl.names_in_place) copy(o.names + first, sl.p_names.p, (size_t)reads * sizeof(fmgpu_text_span));
+    if (o.quals && !sl.quals_in_place) copy(o.quals + first, sl.p_quals.p, (size_t)reads * sizeof(fmgpu_text_span));
+    if (o.lens && !sl.rlen_in_place) copy(o.lens + first, sl.p_rlen.p, (size_t)reads * 8);
+    return 0;
+}
+
+// a carry longer than the slot's headroom: a larger text buffer with the window (already uploaded) moved to its new place.  Rare, and synchronised.
+int regrow_text(Feed* f, Slot& sl, uint64_t carry, uint64_t window) {
+    const uint64_t H = fh::text_headroom_for(sl.headroom, carry);
+    FM_HIP(hipStreamSynchronize(f->up));
+    FM_HIP(hipStreamSynchronize(f->comp));
+    Grown fresh;
+    if (int rc = fresh.need((size_t)(H + std::max<uint64_t>(window, sl.d_text.bytes - std::min<uint64_t>(sl.d_text.bytes, sl.headroom)) + 32), &f->device_bytes)) return rc;
+    if (window) {
+        const hipError_t e = hipMemcpy(fresh.as<uint8_t>() + H, sl.d_text.as<uint8_t>() + sl.headroom, (size_t)window, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { fresh.release(&f->device_bytes); return hip_fail(e, "hipMemcpy(feed text regrow)"); }
+    }
+    sl.d_text.release(&f->device_bytes);
+    sl.d_text = fresh;
+    sl.headroom = H;
+    return 0;
+}
+
+int run_map_text(Feed* f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of, uint64_t B, const fmgpu_map_query* what,
+                 const TextOut& o, uint64_t* out_count, uint64_t* out_hit_count, fmgpu_parse_result* result, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
+    begin_call(f);
+    const bool in_pinned = pointer_kind(text) == 1;
+    const bool pos_pinned = o.m.capacity && pointer_kind(o.m.out) == 1, hits_pinned = o.m.hits_capacity && pointer_kind(o.m.out_hits) == 1;
+    const bool str_pinned = o.m.out_stratum && pointer_kind(o.m.out_stratum) == 1;
+    const bool names_pinned = o.names && pointer_kind(o.names) == 1, quals_pinned = o.quals && pointer_kind(o.quals) == 1, lens_pinned = o.lens && pointer_kind(o.lens) == 1;
+    const int32_t nstats = std::max(1, what->n_schemes);
+    const uint64_t windows = fh::text_windows(bytes, B), slots = (uint64_t)f->slots;
+    f->last_chunks = windows;
+    const uint64_t widest = std::min(B, bytes);
+    int rc;
+    for (uint64_t s = 0; s < std::min(slots, windows); ++s) {
+        Slot& sl = f->slot[s];
+        sl.headroom = std::max(sl.headroom, fh::text_headroom(B));
+        if ((rc = sl.d_text.need((size_t)(sl.headroom + widest + 32), &f->device_bytes))) return rc;
+        if (!in_pinned && (rc = sl.p_text.need((size_t)widest, &f->pinned_bytes))) return rc;
+        for (hipEvent_t* ev : {&sl.ev_up, &sl.ev_comp, &sl.ev_down, &sl.ev_text}) if (!*ev) FM_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    }
+    if ((rc = f->d_table.need(256, &f->device_bytes))) return rc;
+    FM_HIP(hipMemcpyAsync(f->d_table.p, symbol_of, 256, hipMemcpyHostToDevice, f->comp));
+
+    fmgpu_parse_result total;
+    std::memset(&total, 0, sizeof total);
+    uint64_t produced = 0, located = 0, carry = 0, line_base = 0;         // total.consumed: the offset of the current piece in `text`
+    std::vector<fmgpu_stats> cs((size_t)nstats);
+    bool text_error = false;
+
+    const auto upload = [&](uint64_t c) -> int {                          // window c into its slot, once the slot is free
+        Slot& sl = f->slot[c % slots];
+        if (int r = retire_text(f, sl, o)) return r;
+        const uint64_t w0 = fh::text_window_begin(c, B), len = fh::text_window_end(bytes, c, B) - w0;
+        const uint8_t* src = text + w0;
+        if (!in_pinned) {
+            uint8_t* pt = sl.p_text.as<uint8_t>();
+            f->workers->run([&](uint32_t t, uint32_t parts) {
+                const size_t a = (size_t)fh::slice_cut(len, parts, t), b = (size_t)fh::slice_cut(len, parts, t + 1);
+                if (b > a) std::memcpy(pt + a, src + a, b - a);
+            });
+            src = pt;
+            f->last_staged += len;
+        }
+        if (sl.headroom + len + 16 > sl.d_text.bytes) return fail(FMGPU_ERR_HIP, "feed: a window outgrew its slot");
+        FM_HIP(hipStreamWaitEvent(f->up, sl.ev_text, 0));
+        FM_HIP(hipMemcpyAsync(sl.d_text.as<uint8_t>() + sl.headroom, src, (size_t)len, hipMemcpyHostToDevice, f->up));
+        FM_HIP(hipEventRecord(sl.ev_up, f->up));
+        f->last_uploaded += len;
+        return 0;
+    };
+
+    auto body = [&]() -> int {
+        int r;
+        if ((r = upload(0))) return r;
+        for (uint64_t c = 0; c < windows; ++c) {
+            Slot& sl = f->slot[c % slots];
+            const uint64_t len = fh::text_window_end(bytes, c, B) - fh::text_window_begin(c, B);
+            if (!fh::text_piece_fits(carry, len))
+                return fail(FMGPU_ERR_UNSUPPORTED, "fmgpu_feed_map_text: a piece (the unconsumed bytes and the next window) may hold at most 2^32 - 2 bytes: no record ends within " + std::to_string(carry) + " bytes");
+            if (carry) {
+                Slot& prev = f->slot[(c - 1) % slots];
+                if (carry > sl.headroom && (r = regrow_text(f, sl, carry, len))) return r;
+                FM_HIP(hipMemcpyAsync(sl.d_text.as<uint8_t>() + sl.headroom - carry, prev.d_text.as<uint8_t>() + prev.unconsumed, (size_t)carry, hipMemcpyDeviceToDevice, f->comp));
+                FM_HIP(hipEventRecord(prev.ev_text, f->comp));
+            }
+            if (c + 1 < windows && (r = upload(c + 1))) return r;
+            FM_HIP(hipStreamWaitEvent(f->comp, sl.ev_up, 0));
+
+            // the piece, parsed on the slot's buffers
+            SlotBuffer bacc(&sl.d_acc, &f->device_bytes), bln(&sl.d_lnbase, &f->device_bytes), bk(&sl.d_kcnt, &f->device_bytes), bhc(&sl.d_hcnt, &f->device_bytes),
+                btmp(&sl.d_tmp, &f->device_bytes), bls(&sl.d_ls, &f->device_bytes), bq(&sl.d_q, &f->device_bytes), boff(&sl.d_off, &f->device_bytes),
+                bn(&sl.d_names, &f->device_bytes), bql(&sl.d_quals, &f->device_bytes);
+            ParseBuffers pb;
+            pb.acc = &bacc; pb.lnbase = &bln; pb.kcnt = &bk; pb.hcnt = &bhc; pb.tmp = &btmp; pb.ls = &bls; pb.qbuf = &bq; pb.qoff = &boff;
+            pb.names = o.names ? &bn : nullptr; pb.quals = o.quals ? &bql : nullptr; pb.qpad = 64;
+            const uint64_t start = sl.headroom - carry, n = carry + len;
+            fmgpu_parse_result pr;
+            uint64_t next_line = 0;
+            r = parse_device(sl.d_text.as<uint8_t>() + start, n, format, fh::text_piece_final(c, windows, final) ? 1 : 0, c + 1 < windows ? 1 : 0, f->d_table.as<uint8_t>(), &pb, false, ~0ull, ~0ull,
+                             line_base, total.consumed, &pr, &next_line, &text_error, f->comp);
+            if (text_error) {                                             // the counts of the records in front of the offending one, in the caller's text
+                total.reads += pr.reads; total.symbols += pr.symbols; total.foreign += pr.foreign;
+                total.error_line = line_base + pr.error_line; total.error_offset = total.consumed + pr.error_offset;
+                total.consumed += pr.consumed;
+                return r;
+            }
+            if (r) return r;
+            FM_HIP(hipEventRecord(sl.ev_text, f->comp));
+            sl.unconsumed = start + pr.consumed;
+            const uint64_t reads = pr.reads, first = total.reads;
+
+            // its reads, mapped: run_map's chain and rebase, and the spans rebased to the caller's text
+            uint64_t cnt = 0, pcnt = 0;
+            if (reads) {
+                if (o.m.out_stratum && (r = sl.d_str.need((size_t)reads, &f->device_bytes))) return r;
+                if (o.lens && (r = sl.d_rlen.need((size_t)reads * 8, &f->device_bytes))) return r;
+                SlotBuffer bh(&sl.d_hits, &f->device_bytes), bp(&sl.d_pos, &f->device_bytes), bi(&sl.d_lb, &f->device_bytes);
+                fmgpu_stats ls{};
+                if ((r = map_device(f->h, sl.d_q.as<uint8_t>(), sl.d_off.as<uint64_t>(), reads, what, false, &bh, &bp, &bi, o.m.out_stratum ? sl.d_str.as<uint8_t>() : nullptr,
+                                    search_stats ? cs.data() : nullptr, locate_stats ? &ls : nullptr, f->comp, &cnt, &pcnt))) return r;
+                if ((r = map_rebase(sl.d_hits.as<fmgpu_hit>(), cnt, sl.d_pos.as<fmgpu_position>(), pcnt, first, produced, f->comp))) return r;
+                if ((r = parse_piece_spans(o.names ? sl.d_names.as<fmgpu_text_span>() : nullptr, o.quals ? sl.d_quals.as<fmgpu_text_span>() : nullptr,
+                                           o.lens ? sl.d_rlen.as<uint64_t>() : nullptr, sl.d_off.as<uint64_t>(), reads, total.consumed, format, f->comp))) return r;
+                if (search_stats) for (int32_t i = 0; i < nstats; ++i) add_stats(&search_stats[i], cs[(size_t)i]);
+                if (locate_stats) add_stats(locate_stats, ls);
+            }
+            FM_HIP(hipEventRecord(sl.ev_comp, f->comp));
+            FM_HIP(hipStreamWaitEvent(f->down, sl.ev_comp, 0));
+            sl.first = first; sl.reads = reads; sl.hits = cnt; sl.produced = produced; sl.positions = pcnt; sl.located = located;
+            // records and reads beyond the caller's capacity are counted, not written
+            sl.hits_down = o.m.out_hits && cnt && produced + cnt <= o.m.hits_capacity; sl.hits_in_place = hits_pinned;
+            sl.pos_down = pcnt && located + pcnt <= o.m.capacity; sl.pos_in_place = pos_pinned;
+            sl.reads_down = reads && o.read_arrays() && first + reads <= o.read_capacity;
+            sl.str_down = sl.reads_down && o.m.out_stratum; sl.str_in_place = str_pinned;
+            sl.names_in_place = names_pinned; sl.quals_in_place = quals_pinned; sl.rlen_in_place = lens_pinned;
+            const auto download = [&](bool wanted, bool in_place, void* target, Grown& pinned, const Grown& dev, size_t nbytes) -> int {
+                if (!wanted || !nbytes) return 0;
+                if (!in_place) { if (int e = pinned.need(nbytes, &f->pinned_bytes)) return e; target = pinned.p; }
+                FM_HIP(hipMemcpyAsync(target, dev.p, nbytes, hipMemcpyDeviceToHost, f->down));
+                return 0;
+            };
+            if ((r = download(sl.hits_down, hits_pinned, o.m.out_hits + produced, sl.p_hits, sl.d_hits, (size_t)cnt * sizeof(fmgpu_hit)))) return r;
+            if ((r = download(sl.pos_down, pos_pinned, o.m.out + located, sl.p_pos, sl.d_pos, (size_t)pcnt * sizeof(fmgpu_position)))) return r;
+            if ((r = download(sl.str_down, str_pinned, o.m.out_stratum + first, sl.p_str, sl.d_str, (size_t)reads))) return r;
+            if ((r = download(sl.reads_down && o.names, names_pinned, o.names + first, sl.p_names, sl.d_names, (size_t)reads * sizeof(fmgpu_text_span)))) return r;
+            if ((r = download(sl.reads_down && o.quals, quals_pinned, o.quals + first, sl.p_quals, sl.d_quals, (size_t)reads * sizeof(fmgpu_text_span)))) return r;
+            if ((r = download(sl.reads_down && o.lens, lens_pinned, o.lens + first, sl.p_rlen, sl.d_rlen, (size_t)reads * 8))) return r;
+            FM_HIP(hipEventRecord(sl.ev_down, f->down));
+            sl.busy = true;
+            produced += cnt; located += pcnt;
+            total.reads += reads; total.symbols += pr.symbols; total.foreign += pr.foreign; total.consumed += pr.consumed;
+            line_base += next_line;
+            carry = n - pr.consumed;
+        }
+        for (uint64_t k = 0; k < slots; ++k) {
+            Slot& sl = f->slot[(windows + k) % slots];
+            if (int r2 = retire_text(f, sl, o)) return r2;
+        }
+        return 0;
+    };
+    rc = body();
+    *result = total;
+    *out_count = located;
+    if (out_hit_count) *out_hit_count = produced;
+    if (rc) { drain(f); return rc; }
+    if (located > o.m.capacity) return fail(FMGPU_ERR_CAPACITY, "position buffer holds " + std::to_string(o.m.capacity) + " records, " + std::to_string(located) + " produced");
+    if (o.m.out_hits && produced > o.m.hits_capacity) return fail(FMGPU_ERR_CAPACITY, "hit buffer holds " + std::to_string(o.m.hits_capacity) + " records, " + std::to_string(produced) + " produced");
+    if (o.read_arrays() && total.reads > o.read_capacity) return fail(FMGPU_ERR_CAPACITY, "the read arrays hold " + std::to_string(o.read_capacity) + " entries, the text has " + std::to_string(total.reads) + " reads");
+    return 0;
+}
+
 }  // namespace
 }  // namespace fmgpu
 
@@ -538,10 +749,10 @@ int fmgpu_feed_destroy(fmgpu_feed_t f) {
     if (f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is not a feed of this library");
     drain(f);
     for (Slot& sl : f->slot) {
-        for (Grown* g : {&sl.d_q, &sl.d_off, &sl.d_lb, &sl.d_len, &sl.d_hits, &sl.d_pos, &sl.d_str, &sl.p_q, &sl.p_off, &sl.p_lb, &sl.p_len, &sl.p_hits, &sl.p_pos, &sl.p_str})
-            g->release(nullptr);
-        for (hipEvent_t ev : {sl.ev_up, sl.ev_comp, sl.ev_down}) if (ev) (void)hipEventDestroy(ev);
+        for (Grown* g : sl.buffers()) g->release(nullptr);
+        for (hipEvent_t ev : {sl.ev_up, sl.ev_comp, sl.ev_down, sl.ev_text}) if (ev) (void)hipEventDestroy(ev);
     }
+    f->d_table.release(nullptr);
     for (hipStream_t s : {f->up, f->comp, f->down}) if (s) (void)hipStreamDestroy(s);
     f->magic = 0;
     delete f;
@@ -647,6 +858,30 @@ int fmgpu_feed_map_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t
         return (f && f->magic == 0x46454544u) ? fail(FMGPU_ERR_INVALID, "reads / lens / out / out_count / out_hits is null") : fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
     Batch b; b.reads = reads; b.lens = lens; b.nq = nq;
     return feed_map(f, b, what, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats);
+}
+
+int fmgpu_feed_map_text(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of, uint64_t chunk_bytes,
+                        const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity,
+                        uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_text_span* out_names, fmgpu_text_span* out_quals, uint64_t* out_lens, uint64_t read_capacity,
+                        fmgpu_parse_result* result, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
+    if (out_count) *out_count = 0;
+    if (out_hit_count) *out_hit_count = 0;
+    if (result) std::memset(result, 0, sizeof *result);
+    if (!result || !symbol_of) return fail(FMGPU_ERR_INVALID, "result / symbol_of is null");
+    if (int rc = check_map_query(what)) return rc;
+    if (!out_count || (!out && capacity) || (!out_hits && hits_capacity)) return fail(FMGPU_ERR_INVALID, "out / out_count / out_hits is null");
+    if (format != FMGPU_TEXT_LINES && format != FMGPU_TEXT_FASTA && format != FMGPU_TEXT_FASTQ) return fail(FMGPU_ERR_INVALID, "unknown text format " + std::to_string(format));
+    if (!text && bytes) return fail(FMGPU_ERR_INVALID, "text is null");
+    if (chunk_bytes && chunk_bytes < fmgpu_feed_host::kTextMinWindow) return fail(FMGPU_ERR_INVALID, "chunk_bytes must be 0 or at least 16");
+    if (search_stats) for (int32_t i = 0; i < std::max(1, what->n_schemes); ++i) search_stats[i] = fmgpu_stats{};
+    if (locate_stats) *locate_stats = fmgpu_stats{};
+    if (!f || f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
+    if (bytes == 0) return 0;
+    if (int rc = check_feed(f)) return rc;
+    if (int rc = check_map_schemes(f->h, what, false)) return rc;
+    if (int rc = no_device_memory({text, symbol_of, out, out_count, out_hits, out_hit_count, out_stratum, out_names, out_quals, out_lens, result})) return rc;
+    const TextOut o{MapOut{out, capacity, out_hits, hits_capacity, out_stratum}, out_names, out_quals, out_lens, read_capacity};
+    return run_map_text(f, text, bytes, format, final, symbol_of, fmgpu_feed_host::text_window_bytes(chunk_bytes), what, o, out_count, out_hit_count, result, search_stats, locate_stats);
 }
 
 }  // extern "C"

@@ -160,6 +160,22 @@ inline void scatter_hits(const fmgpu_hit* src, uint64_t a, uint64_t b, uint64_t 
     for (uint64_t i = a; i < b; ++i) out[i].qidx += first;
 }
 
+// ---- text feeds (fmgpu_feed_map_text): the text is cut into windows of B bytes; piece c is what piece c - 1 left unconsumed (the carry) followed by window c.  A
+// slot's device text buffer holds the window from byte H (the headroom) on and the carry in the H bytes in front of it.
+constexpr uint64_t kTextDefaultWindow = 64ull << 20, kTextMinWindow = 16, kTextMaxHeadroom = 1ull << 20, kTextMaxPiece = 0xfffffffeull;
+inline uint64_t text_window_bytes(uint64_t chunk_bytes) { return chunk_bytes ? chunk_bytes : kTextDefaultWindow; }      // (values below kTextMinWindow are refused by the caller)
+inline uint64_t text_windows(uint64_t bytes, uint64_t B) { return bytes / B + (bytes % B ? 1 : 0); }
+inline uint64_t text_window_begin(uint64_t c, uint64_t B) { return c * B; }                                            // c < text_windows(bytes, B): no overflow
+inline uint64_t text_window_end(uint64_t bytes, uint64_t c, uint64_t B) { const uint64_t a = c * B; return bytes - a < B ? bytes : a + B; }
+inline bool text_piece_final(uint64_t c, uint64_t windows, int32_t final) { return final != 0 && c + 1 == windows; }
+inline uint64_t text_round16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
+// the headroom a slot starts with: a window's worth, at most 1 MiB, a multiple of 16 ...
+inline uint64_t text_headroom(uint64_t B) { return text_round16(B < kTextMaxHeadroom ? B : kTextMaxHeadroom); }
+// ... and the headroom it has once a carry has arrived: unchanged while the carry fits, else twice the carry
+inline uint64_t text_headroom_for(uint64_t H, uint64_t carry) { return carry <= H ? H : text_round16(2 * carry); }
+// a piece may hold 2^32 - 2 bytes (positions and line numbers are 32-bit words on the device)
+inline bool text_piece_fits(uint64_t carry, uint64_t window) { return carry <= kTextMaxPiece && window <= kTextMaxPiece - carry; }
+
 // ---- the workers: host_threads - 1 threads beside the calling one, which takes slice 0 itself.  run(fn) calls fn(t, parts) once for every t and returns when all have.
 // They copy and pack, each on its own slice, and never make a HIP call.
 class Workers {

@@ -2,7 +2,7 @@
 // width or on an index.  The text is walked in chunks of 16 bytes, one per lane and pass (one aligned 16-byte load; the first and last chunk byte by byte):
 //  k_count_newlines  '\n' per chunk                     -> hipcub exclusive scan = the line number of every chunk's first byte; the total is the call's first read-back
 //  k_line_starts     one word per line: its first byte  (ls[l], and ls[lines] = bytes)
-//  k_line_stats      per line (FASTA; FASTQ with `final`): lowest header / sequence line, highest header line, header count; highest non-empty line — block-reduced, one atomic per block
+//  k_line_stats      per line (FASTA; FASTQ with `final` or as a feed's piece): lowest header / sequence line, highest header line, header count; highest non-empty line — block-reduced, one atomic per block
 //  k_records         one thread: reads and consumed from those; k_validate_fastq per line of a complete record (atomicMin of the offending line); k_settle_error one thread
 //  k_symbols<false>  per chunk: the symbols its bytes below `consumed` produce, FOREIGN among them, FASTA headers -> two scans = output position / read number of every chunk
 //  (second read-back: counts, error; a text error, the counting call and FMGPU_ERR_CAPACITY return here, before anything is written)
@@ -20,9 +20,9 @@ constexpr uint64_t kParseMaxBytes = 0xfffffffeull;          // positions and lin
 struct ParseAcc {                                           // the device words the passes of one call share
     uint32_t first_hdr, first_seq;                          // FASTA: the lowest header line / non-empty line that is no header (kNoLine: none)
     uint32_t last_hdr1, headers;                            //        the highest header line + 1, the header lines
-    uint32_t last_nonempty1;                                // FASTQ with `final`: the highest non-empty line + 1
+    uint32_t last_nonempty1;                                // FASTQ with `final` or as a feed's piece: the highest non-empty line + 1
     uint32_t err_line;                                      // the lowest offending line (kNoLine: none)
-    uint32_t reads, pad;
+    uint32_t reads, next_line;                              // next_line: the line number of the first unconsumed byte (a feed's next piece starts there)
     unsigned long long consumed, err_offset, foreign;
 };
 
@@ -30,6 +30,7 @@ struct ParseText {
     const uint8_t* p; uint64_t n;
     uint32_t mis;                                           // p & 15: chunk c holds positions 16 c - mis .. 16 c - mis + 15, so every full chunk is one aligned load
     int32_t final, format;
+    int32_t piece;                                          // a feed's piece in front of the last one (fmgpu_feed_map_text): what only the bytes behind it can settle is left unconsumed
 };
 
 struct Chunk {
@@ -118,7 +119,9 @@ __global__ __launch_bounds__(256) void k_line_stats(ParseText t, const uint32_t*
     bool nonempty = false, hdr = false;
     if (live) {
         const uint32_t s = ls[l];
-        nonempty = line_end(t, ls, l, nl) > s;
+        uint32_t e = line_end(t, ls, l, nl);
+        if (t.piece && l >= nl && e > s && t.p[e - 1] == '\r') --e;                      // an unterminated "\r": the '\n' may follow in the next window
+        nonempty = e > s;
         hdr = nonempty && t.p[s] == '>';
     }
     if (t.format == FMGPU_TEXT_FASTA) {
@@ -149,12 +152,14 @@ __global__ void k_records(ParseText t, const uint32_t* __restrict__ ls, uint32_t
         else if (t.final) { reads = acc->headers; consumed = t.n; }
         else if (acc->headers >= 2) { reads = acc->headers - 1; consumed = ls[acc->last_hdr1 - 1]; }
     } else {
-        const uint32_t have = t.final ? acc->last_nonempty1 : nl;                       // `final`: empty lines at the very end are discarded first
+        // `final`: empty lines at the very end are discarded first; a piece leaves them (and the record they may truncate) to the pieces behind it
+        const uint32_t have = t.final ? acc->last_nonempty1 : (t.piece && acc->last_nonempty1 < nl ? acc->last_nonempty1 : nl);
         reads = have / 4;
         consumed = ls[4 * reads];
         if (t.final && (have & 3u)) err = 4 * reads;                                    // a truncated record
     }
     acc->reads = reads; acc->consumed = consumed; acc->err_line = err;
+    acc->next_line = t.format == FMGPU_TEXT_LINES ? reads : t.format == FMGPU_TEXT_FASTQ ? 4 * reads : (consumed && !t.final ? acc->last_hdr1 - 1 : (consumed ? lines : 0u));
 }
 
 __global__ __launch_bounds__(256) void k_validate_fastq(ParseText t, const uint32_t* __restrict__ ls, uint32_t nl, ParseAcc* acc) {
@@ -175,6 +180,7 @@ __global__ void k_settle_error(ParseText t, const uint32_t* __restrict__ ls, Par
     const uint32_t reads = t.format == FMGPU_TEXT_FASTQ ? err / 4 : 0u;
     acc->reads = reads;
     acc->consumed = t.format == FMGPU_TEXT_FASTQ ? ls[4 * reads] : 0u;
+    acc->next_line = 4 * reads;
 }
 
 struct ParseOut { uint8_t* qbuf; uint64_t* qoff; fmgpu_text_span* names; fmgpu_text_span* quals; };
@@ -255,8 +261,28 @@ __global__ __launch_bounds__(256) void k_symbols(ParseText t, uint64_t nchunks, 
     if (threadIdx.x == 0 && f) atomicAdd(&acc->foreign, (unsigned long long)f);
 }
 
-static int exclusive_sum(DBuf& tmp, size_t tmp_bytes, uint32_t* words, uint64_t count, hipStream_t stream) {
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, words, words, (size_t)count, stream));
+// a feed's piece (fmgpu_feed_map_text): the spans of its reads become spans of the caller's text (offset += base, in 64 bits), lens[r] = the read's symbols.  A lane
+// moves one span as one 16-byte word: consecutive lanes, consecutive words.
+__global__ __launch_bounds__(256) void k_piece_spans(fmgpu_text_span* __restrict__ names, fmgpu_text_span* __restrict__ quals, uint64_t* __restrict__ lens,
+                                                     const uint64_t* __restrict__ qoff, uint64_t reads, uint64_t base, int32_t shift_names, int32_t shift_quals) {
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < reads; r += (uint64_t)gridDim.x * blockDim.x) {
+        if (names && shift_names) { ulonglong2 v = reinterpret_cast<ulonglong2*>(names)[r]; v.x += base; reinterpret_cast<ulonglong2*>(names)[r] = v; }
+        if (quals && shift_quals) { ulonglong2 v = reinterpret_cast<ulonglong2*>(quals)[r]; v.x += base; reinterpret_cast<ulonglong2*>(quals)[r] = v; }
+        if (lens) lens[r] = qoff[r + 1] - qoff[r];
+    }
+}
+
+int parse_piece_spans(fmgpu_text_span* names, fmgpu_text_span* quals, uint64_t* lens, const uint64_t* qoff, uint64_t reads, uint64_t base, int32_t format, hipStream_t stream) {
+    const bool shift_names = base && format != FMGPU_TEXT_LINES, shift_quals = base && format == FMGPU_TEXT_FASTQ;      // (the other spans are {0, 0})
+    if (!reads || (!lens && !(names && shift_names) && !(quals && shift_quals))) return 0;
+    dim3 grid; if (int rc = grid_of(reads, &grid, 1u << 16)) return rc;
+    k_piece_spans<<<grid, dim3(256), 0, stream>>>(names, quals, lens, qoff, reads, base, shift_names ? 1 : 0, shift_quals ? 1 : 0);
+    FM_LAUNCHED("k_piece_spans");
+    return 0;
+}
+
+static int exclusive_sum(MapBuffer* tmp, size_t tmp_bytes, uint32_t* words, uint64_t count, hipStream_t stream) {
+    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp->p, tmp_bytes, words, words, (size_t)count, stream));
     return 0;
 }
 
@@ -269,6 +295,118 @@ static const char* text_error(int32_t format, uint64_t line) {
     }
 }
 
+// The passes of fmgpu_queries_parse on device text and on the caller's growing buffers (fmgpu_common.h): the one-shot call below hands it per-call buffers, a feed the
+// buffers of a slot.  bytes > 0.  Two read-backs synchronise `stream`.  *result describes this text alone; the message of a text error names line_base + the line and
+// offset_base + the offset (a feed's piece: its place in the caller's text), and *text_error tells it from the other causes of FMGPU_ERR_INVALID.
+int parse_device(const uint8_t* dtext, uint64_t bytes, int32_t format, int32_t final, int32_t piece, const uint8_t* dtable, ParseBuffers* b, bool counting,
+                 uint64_t symbol_capacity, uint64_t read_capacity, uint64_t line_base, uint64_t offset_base, fmgpu_parse_result* result, uint64_t* next_line,
+                 bool* is_text_error, hipStream_t stream) {
+    std::memset(result, 0, sizeof *result);
+    if (next_line) *next_line = 0;
+    if (is_text_error) *is_text_error = false;
+    if (bytes > kParseMaxBytes) return fail(FMGPU_ERR_UNSUPPORTED, "fmgpu_queries_parse takes at most 2^32 - 2 bytes per call: parse the text in chunks, each starting at the previous call's `consumed`");
+    int rc;
+    ParseText t;
+    t.p = dtext; t.n = bytes; t.mis = (uint32_t)((uintptr_t)dtext & 15u); t.final = final ? 1 : 0; t.format = format; t.piece = piece && !final ? 1 : 0;
+    const uint64_t nchunks = (t.mis + bytes + 15) / 16;
+    const bool fasta = format == FMGPU_TEXT_FASTA;
+
+    if ((rc = b->acc->need(sizeof(ParseAcc))) || (rc = b->lnbase->need((nchunks + 1) * 4)) || (rc = b->kcnt->need((nchunks + 1) * 4))) return rc;
+    if (fasta && (rc = b->hcnt->need((nchunks + 1) * 4))) return rc;
+    uint32_t* const lnbase = reinterpret_cast<uint32_t*>(b->lnbase->p);
+    uint32_t* const kcnt = reinterpret_cast<uint32_t*>(b->kcnt->p);
+    uint32_t* const hcnt = reinterpret_cast<uint32_t*>(b->hcnt->p);
+    size_t tb = 0;
+    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lnbase, lnbase, (size_t)(nchunks + 1), stream));
+    if ((rc = b->tmp->need(tb ? tb : 8))) return rc;
+    ParseAcc acc;
+    std::memset(&acc, 0, sizeof acc);
+    acc.first_hdr = acc.first_seq = acc.err_line = kNoLine;
+    FM_HIP(hipMemcpyAsync(b->acc->p, &acc, sizeof acc, hipMemcpyHostToDevice, stream));
+    ParseAcc* dacc = reinterpret_cast<ParseAcc*>(b->acc->p);
+
+    FM_GRID(cgrid, nchunks + 1);
+    k_count_newlines<<<cgrid, dim3(256), 0, stream>>>(t, nchunks, lnbase);
+    FM_LAUNCHED("k_count_newlines");
+    if ((rc = exclusive_sum(b->tmp, tb, lnbase, nchunks + 1, stream))) return rc;
+    uint32_t nl = 0;
+    uint8_t last = 0;
+    FM_HIP(hipMemcpyAsync(&nl, lnbase + nchunks, 4, hipMemcpyDeviceToHost, stream));
+    FM_HIP(hipMemcpyAsync(&last, t.p + bytes - 1, 1, hipMemcpyDeviceToHost, stream));
+    FM_HIP(hipStreamSynchronize(stream));
+    const uint32_t lines = nl + (last != '\n' ? 1u : 0u);                              // >= 1: the text is not empty
+
+    if ((rc = b->ls->need(((size_t)lines + 1) * 4))) return rc;
+    uint32_t* const ls = reinterpret_cast<uint32_t*>(b->ls->p);
+    k_line_starts<<<cgrid, dim3(256), 0, stream>>>(t, nchunks, lnbase, nl, lines, ls);
+    FM_LAUNCHED("k_line_starts");
+    FM_GRID(lgrid, lines);
+    if (fasta || (format == FMGPU_TEXT_FASTQ && (t.final || t.piece))) {
+        k_line_stats<<<lgrid, dim3(256), 0, stream>>>(t, ls, nl, lines, dacc);
+        FM_LAUNCHED("k_line_stats");
+    }
+    k_records<<<dim3(1), dim3(1), 0, stream>>>(t, ls, nl, lines, dacc);
+    FM_LAUNCHED("k_records");
+    if (format == FMGPU_TEXT_FASTQ) {
+        k_validate_fastq<<<lgrid, dim3(256), 0, stream>>>(t, ls, nl, dacc);
+        FM_LAUNCHED("k_validate_fastq");
+    }
+    if (format != FMGPU_TEXT_LINES) {
+        k_settle_error<<<dim3(1), dim3(1), 0, stream>>>(t, ls, dacc);
+        FM_LAUNCHED("k_settle_error");
+    }
+    ParseOut none = {nullptr, nullptr, nullptr, nullptr};
+    k_symbols<false><<<cgrid, dim3(256), 0, stream>>>(t, nchunks, dtable, lnbase, ls, nl, dacc, kcnt, hcnt, none);
+    FM_LAUNCHED("k_symbols<false>");
+    if ((rc = exclusive_sum(b->tmp, tb, kcnt, nchunks + 1, stream))) return rc;
+    if (fasta && (rc = exclusive_sum(b->tmp, tb, hcnt, nchunks + 1, stream))) return rc;
+    uint32_t symbols = 0;
+    FM_HIP(hipMemcpyAsync(&acc, dacc, sizeof acc, hipMemcpyDeviceToHost, stream));
+    FM_HIP(hipMemcpyAsync(&symbols, kcnt + nchunks, 4, hipMemcpyDeviceToHost, stream));
+    FM_HIP(hipStreamSynchronize(stream));
+
+    result->reads = acc.reads; result->symbols = symbols; result->consumed = acc.consumed; result->foreign = acc.foreign;
+    if (next_line) *next_line = acc.next_line;
+    if (acc.err_line != kNoLine) {
+        result->error_line = acc.err_line; result->error_offset = acc.err_offset;
+        if (is_text_error) *is_text_error = true;
+        return fail(FMGPU_ERR_INVALID, "text error in line " + std::to_string(line_base + acc.err_line) + " (0-based, byte offset " + std::to_string(offset_base + acc.err_offset) + "): " + text_error(format, acc.err_line));
+    }
+    if (counting) return 0;
+    if (symbols > symbol_capacity || acc.reads > read_capacity)
+        return fail(FMGPU_ERR_CAPACITY, "the text holds " + std::to_string(acc.reads) + " reads of " + std::to_string(symbols) + " symbols: more than the output buffers take");
+
+    if ((rc = b->qbuf->need((size_t)symbols + b->qpad)) || (rc = b->qoff->need(((size_t)acc.reads + 1) * 8))) return rc;
+    if (b->names && (rc = b->names->need((size_t)acc.reads * sizeof(fmgpu_text_span)))) return rc;
+    if (b->quals && (rc = b->quals->need((size_t)acc.reads * sizeof(fmgpu_text_span)))) return rc;
+    ParseOut out = {(uint8_t*)b->qbuf->p, (uint64_t*)b->qoff->p, b->names ? (fmgpu_text_span*)b->names->p : nullptr, b->quals ? (fmgpu_text_span*)b->quals->p : nullptr};
+    k_symbols<true><<<cgrid, dim3(256), 0, stream>>>(t, nchunks, dtable, lnbase, ls, nl, dacc, kcnt, hcnt, out);
+    FM_LAUNCHED("k_symbols<true>");
+    return 0;
+}
+
+namespace {
+
+struct OwnScratch : MapBuffer {                                     // the one-shot call's scratch: freed on return
+    DBuf d;
+    int need(size_t nbytes) override {
+        if (nbytes <= bytes) return 0;
+        const int rc = d.alloc(nbytes);
+        p = d.p; bytes = d.p ? d.bytes : 0;
+        return rc;
+    }
+};
+struct CallerOutput : MapBuffer {                                   // an output of the one-shot call: device memory in place, host memory staged; sized once
+    Staged s; void* target; hipStream_t stream;
+    CallerOutput(void* target_, hipStream_t stream_) : target(target_), stream(stream_) {}
+    int need(size_t nbytes) override {
+        const int rc = s.out(target, nbytes, stream);
+        p = s.dev; bytes = nbytes;
+        return rc;
+    }
+};
+
+}  // namespace
 }  // namespace fmgpu
 
 using namespace fmgpu;
@@ -297,80 +435,17 @@ int fmgpu_queries_parse(const uint8_t* text, uint64_t bytes, int32_t format, int
     int rc;
     Staged stext;
     if ((rc = stext.in(text, bytes, stream))) return rc;
-    ParseText t;
-    t.p = (const uint8_t*)stext.dev; t.n = bytes; t.mis = (uint32_t)((uintptr_t)stext.dev & 15u); t.final = final ? 1 : 0; t.format = format;
-    const uint64_t nchunks = (t.mis + bytes + 15) / 16;
-    const bool fasta = format == FMGPU_TEXT_FASTA;
-
-    DBuf table, accbuf, lnbase, kcnt, hcnt, tmp, ls;
-    if ((rc = table.alloc(256)) || (rc = accbuf.alloc(sizeof(ParseAcc))) || (rc = lnbase.alloc((nchunks + 1) * 4)) || (rc = kcnt.alloc((nchunks + 1) * 4))) return rc;
-    if (fasta && (rc = hcnt.alloc((nchunks + 1) * 4))) return rc;
-    size_t tb = 0;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lnbase.as<uint32_t>(), lnbase.as<uint32_t>(), (size_t)(nchunks + 1), stream));
-    if ((rc = tmp.alloc(tb))) return rc;
-    ParseAcc acc;
-    std::memset(&acc, 0, sizeof acc);
-    acc.first_hdr = acc.first_seq = acc.err_line = kNoLine;
+    OwnScratch table, acc, lnbase, kcnt, hcnt, tmp, ls;
+    if ((rc = table.need(256))) return rc;
     FM_HIP(hipMemcpyAsync(table.p, symbol_of, 256, hipMemcpyHostToDevice, stream));
-    FM_HIP(hipMemcpyAsync(accbuf.p, &acc, sizeof acc, hipMemcpyHostToDevice, stream));
-    ParseAcc* dacc = accbuf.as<ParseAcc>();
-
-    FM_GRID(cgrid, nchunks + 1);
-    k_count_newlines<<<cgrid, dim3(256), 0, stream>>>(t, nchunks, lnbase.as<uint32_t>());
-    FM_LAUNCHED("k_count_newlines");
-    if ((rc = exclusive_sum(tmp, tb, lnbase.as<uint32_t>(), nchunks + 1, stream))) return rc;
-    uint32_t nl = 0;
-    uint8_t last = 0;
-    FM_HIP(hipMemcpyAsync(&nl, lnbase.as<uint32_t>() + nchunks, 4, hipMemcpyDeviceToHost, stream));
-    FM_HIP(hipMemcpyAsync(&last, t.p + bytes - 1, 1, hipMemcpyDeviceToHost, stream));
-    FM_HIP(hipStreamSynchronize(stream));
-    const uint32_t lines = nl + (last != '\n' ? 1u : 0u);                              // >= 1: the text is not empty
-
-    if ((rc = ls.alloc(((size_t)lines + 1) * 4))) return rc;
-    k_line_starts<<<cgrid, dim3(256), 0, stream>>>(t, nchunks, lnbase.as<uint32_t>(), nl, lines, ls.as<uint32_t>());
-    FM_LAUNCHED("k_line_starts");
-    FM_GRID(lgrid, lines);
-    if (fasta || (format == FMGPU_TEXT_FASTQ && final)) {
-        k_line_stats<<<lgrid, dim3(256), 0, stream>>>(t, ls.as<uint32_t>(), nl, lines, dacc);
-        FM_LAUNCHED("k_line_stats");
-    }
-    k_records<<<dim3(1), dim3(1), 0, stream>>>(t, ls.as<uint32_t>(), nl, lines, dacc);
-    FM_LAUNCHED("k_records");
-    if (format == FMGPU_TEXT_FASTQ) {
-        k_validate_fastq<<<lgrid, dim3(256), 0, stream>>>(t, ls.as<uint32_t>(), nl, dacc);
-        FM_LAUNCHED("k_validate_fastq");
-    }
-    if (format != FMGPU_TEXT_LINES) {
-        k_settle_error<<<dim3(1), dim3(1), 0, stream>>>(t, ls.as<uint32_t>(), dacc);
-        FM_LAUNCHED("k_settle_error");
-    }
-    ParseOut none = {nullptr, nullptr, nullptr, nullptr};
-    k_symbols<false><<<cgrid, dim3(256), 0, stream>>>(t, nchunks, table.as<uint8_t>(), lnbase.as<uint32_t>(), ls.as<uint32_t>(), nl, dacc, kcnt.as<uint32_t>(), hcnt.as<uint32_t>(), none);
-    FM_LAUNCHED("k_symbols<false>");
-    if ((rc = exclusive_sum(tmp, tb, kcnt.as<uint32_t>(), nchunks + 1, stream))) return rc;
-    if (fasta && (rc = exclusive_sum(tmp, tb, hcnt.as<uint32_t>(), nchunks + 1, stream))) return rc;
-    uint32_t symbols = 0;
-    FM_HIP(hipMemcpyAsync(&acc, dacc, sizeof acc, hipMemcpyDeviceToHost, stream));
-    FM_HIP(hipMemcpyAsync(&symbols, kcnt.as<uint32_t>() + nchunks, 4, hipMemcpyDeviceToHost, stream));
-    FM_HIP(hipStreamSynchronize(stream));
-
-    result->reads = acc.reads; result->symbols = symbols; result->consumed = acc.consumed; result->foreign = acc.foreign;
-    if (acc.err_line != kNoLine) {
-        result->error_line = acc.err_line; result->error_offset = acc.err_offset;
-        return fail(FMGPU_ERR_INVALID, "text error in line " + std::to_string(acc.err_line) + " (0-based, byte offset " + std::to_string(acc.err_offset) + "): " + text_error(format, acc.err_line));
-    }
+    CallerOutput sq(out_qbuf, stream), so(out_qoff, stream), sn(out_names, stream), sl(out_quals, stream);
+    ParseBuffers b;
+    b.acc = &acc; b.lnbase = &lnbase; b.kcnt = &kcnt; b.hcnt = &hcnt; b.tmp = &tmp; b.ls = &ls;
+    b.qbuf = &sq; b.qoff = &so; b.names = out_names ? &sn : nullptr; b.quals = out_quals ? &sl : nullptr;
+    if ((rc = parse_device((const uint8_t*)stext.dev, bytes, format, final, 0, (const uint8_t*)table.p, &b, counting, symbol_capacity, read_capacity, 0, 0, result, nullptr,
+                           nullptr, stream))) return rc;
     if (counting) return 0;
-    if (symbols > symbol_capacity || acc.reads > read_capacity)
-        return fail(FMGPU_ERR_CAPACITY, "the text holds " + std::to_string(acc.reads) + " reads of " + std::to_string(symbols) + " symbols: more than the output buffers take");
-
-    Staged sq, so, sn, sl;
-    if ((rc = sq.out(out_qbuf, symbols, stream)) || (rc = so.out(out_qoff, ((size_t)acc.reads + 1) * 8, stream))) return rc;
-    if (out_names && (rc = sn.out(out_names, (size_t)acc.reads * sizeof(fmgpu_text_span), stream))) return rc;
-    if (out_quals && (rc = sl.out(out_quals, (size_t)acc.reads * sizeof(fmgpu_text_span), stream))) return rc;
-    ParseOut out = {(uint8_t*)sq.dev, (uint64_t*)so.dev, (fmgpu_text_span*)sn.dev, (fmgpu_text_span*)sl.dev};
-    k_symbols<true><<<cgrid, dim3(256), 0, stream>>>(t, nchunks, table.as<uint8_t>(), lnbase.as<uint32_t>(), ls.as<uint32_t>(), nl, dacc, kcnt.as<uint32_t>(), hcnt.as<uint32_t>(), out);
-    FM_LAUNCHED("k_symbols<true>");
-    if ((rc = sq.finish()) || (rc = so.finish()) || (rc = sn.finish()) || (rc = sl.finish())) return rc;
+    if ((rc = sq.s.finish()) || (rc = so.s.finish()) || (rc = sn.s.finish()) || (rc = sl.s.finish())) return rc;
     FM_HIP(hipStreamSynchronize(stream));
     return 0;
 }

@@ -17,6 +17,8 @@
 //   * --mode map (not in the reference): search, callback order and locate as ONE fmgpu_map call (fmc::map) — `noerror` as exact search, `ng26` / `ng21` as the best-hit
 //     ladder of `besthits`; with --feed through fmgpu_feed_map_v (fmc::Feed::map), chunk by chunk.  --save_output then holds "queryId seqId pos errors" per located row,
 //     in the reference's report order (fmc::Search's reportFunc arguments).
+//   * --mode map --feed --device-parse --no-reverse (no trimming, no read limit, not ng21): the bytes of the query file go through the feed as they are
+//     (fmgpu_feed_map_text through fmc::Feed::mapText); the reads are never vectors on the host.  The same --save_output file as without --device-parse.
 //   * --device-parse (not in the reference): the --query file is read as bytes and parsed on the device (fmgpu_queries_parse through fmc::parseQueries); its first byte
 //     chooses FASTA ('>') or FASTQ ('@', read only this way).  On a well-formed FASTA — ends in a newline, no '>' inside sequence lines, no '\r' — the output is the
 //     same, byte for byte.  Elsewhere the device rules differ from the reader below: a '\r' in front of a newline belongs to the line end (the reader takes it for
@@ -334,8 +336,27 @@ struct Run {
             for (size_t j = 0; j <= k; ++j) query.expanded.push_back(stretch(schemeByName(config.schemeName, j, j), firstLength));
         }
         auto const mapped = config.feed ? mapThroughFeed(reads, query) : fmc::map(index, reads, query);
-        double const tMap = clock.reset();
+        reportMapped(mapped, reads.size(), k, clock.reset());
+    }
 
+    // --mode map --feed --device-parse without reverse complements: the bytes of the query file go through the feed as they are (fmgpu_feed_map_text through
+    // fmc::Feed::mapText): parsed and mapped on the device window by window, no read ever a vector on the host
+    void oneErrorBudgetMappedText(Algorithm kind, size_t k, std::string const& text) const {
+        StopWatch clock;
+        fmc::MapQuery query;
+        if (config.hitsPerRead != 0) query.maxResults = config.hitsPerRead;
+        if (kind == Algorithm::ng26) {
+            query.kind = fmc::MapQuery::Kind::Schemes;
+            for (size_t j = 0; j <= k; ++j) query.schemes.emplace_back(schemeByName(config.schemeName, j, j), std::vector<size_t>{});
+        }
+        auto const table = Sigma == 6 ? fmc::SymbolTable::dna6(config.unknownToA) : fmc::SymbolTable::dna5(config.unknownToA);
+        auto const mapped = fmc::Feed{index}.mapText(std::string_view{text}, text[0] == '@' ? fmc::TextFormat::Fastq : fmc::TextFormat::Fasta, table, query);
+        if (mapped.foreign > 0) throw std::runtime_error("unknown alphabet");
+        reportMapped(mapped, mapped.size(), k, clock.reset());
+    }
+
+    void reportMapped(fmc::MapResult const& mapped, size_t nreads, size_t k, double tMap) const {
+        struct { size_t n; size_t size() const { return n; } } const reads{nreads};
         std::vector<Placement> distinct;
         distinct.reserve(mapped.positions.size());
         for (auto const& p : mapped.positions) distinct.push_back({static_cast<size_t>(p.qidx), static_cast<uint32_t>(p.seq_id), static_cast<size_t>(p.pos), p.errors});
@@ -405,6 +426,20 @@ int main(int argc, char const* const* argv) try {
                     "                 well-formed FASTA.  Unlike the default reader: \"\\r\\n\" ends a line, a '>' inside a line is an ordinary byte,\\\n"
                     "                 a last line without a newline keeps its last base, a name line at the end of the file is an empty read)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
+        return 0;
+    }
+    bool const needsFirstLength = std::any_of(config.algorithms.begin(), config.algorithms.end(), [](auto const& a) { return algorithmByName(a) == Algorithm::ng21; });
+    if (config.hitMode == HitMode::map && config.feed && config.deviceParse && !config.withReverseComplement && !config.packed && config.readLimit == 0 &&
+        config.trimTo == 0 && !needsFirstLength && !config.readsFasta.empty() && std::filesystem::exists(config.readsFasta)) {
+        std::ifstream in{config.readsFasta, std::ios::binary};
+        std::string const text{std::istreambuf_iterator<char>{in}, std::istreambuf_iterator<char>{}};
+        if (text.empty() || (text[0] != '>' && text[0] != '@')) throw std::runtime_error("can't read fasta file");
+        std::printf("loaded %zu bytes of query text\n", text.size());
+        Run run{config, openIndex(config)};
+        for (auto const& algorithm : config.algorithms) {
+            std::printf("using algorithm %s\n", algorithm.c_str());
+            for (size_t k = config.firstK; k <= config.lastK; k += config.stepK) run.oneErrorBudgetMappedText(algorithmByName(algorithm), k, text);
+        }
         return 0;
     }
     auto reads = config.deviceParse ? readQueriesOnDevice(config.readsFasta, Sigma, config.unknownToA) : readFasta(config.readsFasta, Sigma, config.unknownToA);

@@ -23,6 +23,9 @@
 #include <limits>
 #include <numeric>
 #include <optional>
+#if __has_include(<span>) && __cplusplus >= 202002L
+#include <span>
+#endif
 #include <stdexcept>
 #include <iterator>
 #include <string>
@@ -1328,6 +1331,51 @@ struct Feed {
         return detail::run_map(nq, query.locate, [&](fmgpu_position* out, uint64_t cap, uint64_t* count, fmgpu_hit* hits, uint64_t hcap, uint64_t* hcount, uint8_t* stratum) {
             return fmgpu_feed_map_v(handle, reads.data(), lens.data(), nq, &flat.what, out, cap, count, hits, hcap, hcount, stratum, nullptr, nullptr);
         });
+    }
+    // The bytes of a read file to positions (fmgpu_feed_map_text): what fmc::map(index, parseQueries(text, format, table), query) returns plus the name and quality
+    // spans and the length of every read, without the batch ever visiting the host: the text travels in windows of chunkBytes (0 = 64 MiB), each parsed and mapped
+    // on the device.  final = false: only the records the text proves complete; `consumed` tells where the next call starts.  A text error throws, naming the line.
+    struct TextResult : MapResult {
+        std::vector<fmgpu_text_span> names, quals;                    // spans into the text
+        std::vector<uint64_t> lens;                                   // symbols of every read
+        uint64_t symbols{0}, consumed{0}, foreign{0};
+        auto size() const -> size_t { return lens.size(); }
+        auto name(std::string_view text, size_t q) const -> std::string_view { return text.substr(names[q].offset, names[q].len); }
+        auto quality(std::string_view text, size_t q) const -> std::string_view { return text.substr(quals[q].offset, quals[q].len); }
+    };
+#ifdef __cpp_lib_span
+    auto mapText(std::span<uint8_t const> text, TextFormat format, SymbolTable const& table, MapQuery const& query, bool final = true, uint64_t chunkBytes = 0) const -> TextResult {
+        return mapText(ByteView{text.data(), text.size()}, format, table, query, final, chunkBytes);
+    }
+#endif
+    auto mapText(std::string_view text, TextFormat format, SymbolTable const& table, MapQuery const& query, bool final = true, uint64_t chunkBytes = 0) const -> TextResult {
+        return mapText(ByteView{reinterpret_cast<uint8_t const*>(text.data()), text.size()}, format, table, query, final, chunkBytes);
+    }
+    struct ByteView {                                                 // (what std::span<uint8_t const> is from C++20 on: this header also serves C++17)
+        uint8_t const* first; size_t count;
+        auto data() const -> uint8_t const* { return first; }
+        auto size() const -> size_t { return count; }
+    };
+    auto mapText(ByteView text, TextFormat format, SymbolTable const& table, MapQuery const& query, bool final = true, uint64_t chunkBytes = 0) const -> TextResult {
+        detail::FlatMapQuery flat{query};
+        TextResult r;
+        uint64_t rcap = std::max<uint64_t>(1024, text.size() / 64), cap = query.locate ? std::max<uint64_t>(4 * rcap, text.size() / 16) : 0;
+        uint64_t hcap = std::max<uint64_t>(4 * rcap, text.size() / 16), count = 0, hcount = 0;
+        fmgpu_parse_result res{};
+        for (int round = 0; round < 2; ++round) {                     // the counts are exact also on FMGPU_ERR_CAPACITY, so a second call with them fits
+            r.positions.resize(cap); r.hits.resize(hcap);
+            r.stratum.assign(rcap, 255); r.names.resize(rcap); r.quals.resize(rcap); r.lens.resize(rcap);
+            int rc = fmgpu_feed_map_text(handle, text.data(), text.size(), static_cast<int32_t>(format), final ? 1 : 0, table.map.data(), chunkBytes, &flat.what,
+                                         r.positions.data(), cap, &count, r.hits.data(), hcap, &hcount, r.stratum.data(), r.names.data(), r.quals.data(), r.lens.data(), rcap,
+                                         &res, nullptr, nullptr);
+            if (rc == FMGPU_ERR_CAPACITY && round == 0) { cap = std::max(cap, count); hcap = std::max(hcap, hcount); rcap = std::max<uint64_t>(rcap, res.reads); continue; }
+            detail::check(rc);
+            break;
+        }
+        r.positions.resize(count); r.hits.resize(hcount);
+        r.stratum.resize(res.reads); r.names.resize(res.reads); r.quals.resize(res.reads); r.lens.resize(res.reads);
+        r.symbols = res.symbols; r.consumed = res.consumed; r.foreign = res.foreign;
+        return r;
     }
 
   private:

@@ -705,7 +705,8 @@ int fmgpu_replicas_locate(fmgpu_replicas_t r, const uint64_t* rows, uint64_t cou
  *     on FMGPU_ERR_CAPACITY alike, and every chunk still runs; stats are sums over the chunks.  The slots hold device and pinned buffers for hits, positions and strata
  *     that only ever grow (fmgpu_feed_info counts them); first_records applies per chunk, and a buffer too small for its chunk is grown and the stage rerun.  Pinned
  *     outputs are written in place.  Host memory only, the errors of fmgpu_map, one call at a time; no further stream.
- * Not served through a feed: backtracking, smems, fmgpu_search_hamming_sm, `_q4` batches for map; feeds over replicas. */
+ * Read-file text (LINES / FASTA / FASTQ bytes) is served by fmgpu_feed_map_text, declared behind fmgpu_queries_parse below.
+ * Not served through a feed: backtracking, smems, fmgpu_search_hamming_sm, `_q4` batches for map, text for the plain search calls; feeds over replicas. */
 typedef struct fmgpu_feed* fmgpu_feed_t;
 typedef struct fmgpu_feed_config {
     uint64_t chunk_reads;    /* 0 = default */
@@ -803,6 +804,53 @@ typedef struct fmgpu_parse_result {
 int fmgpu_queries_parse(const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of,
                         uint8_t* out_qbuf, uint64_t symbol_capacity, uint64_t* out_qoff, uint64_t read_capacity,
                         fmgpu_text_span* out_names, fmgpu_text_span* out_quals, fmgpu_parse_result* result, void* stream);
+
+/* ---- read-file bytes to positions through a feed -------------------------------------------------------------------------------------------
+ * fmgpu_feed_map_text takes the raw bytes of a read file (host memory) and returns what fmgpu_map returns for its reads: the text is the only thing uploaded, it is
+ * parsed on the feed's compute stream in front of the search, and nothing but results comes back.  Device memory stays bounded by the window size, not by the file.
+ *   Results
+ *   - Let Q be what fmgpu_queries_parse(text, bytes, format, final, symbol_of, ...) produces for the whole text.  out, out_hits, out_stratum, *out_count and
+ *     *out_hit_count equal, element for element, what fmgpu_map returns for Q with the same `what`; qidx is the read's number in the file, fmgpu_position::hit indexes
+ *     the batch-wide hit list.  out_names[r] / out_quals[r] are the spans of the whole-text parse (offsets relative to `text`), out_lens[r] = Q.qoff[r + 1] - Q.qoff[r].
+ *   - *result equals the whole-text parse's result in every field; consumed counts from byte 0 of `text`, and with final == 0 tells where the next call starts.
+ *   Pieces
+ *   - B = chunk_bytes; 0 means 64 MiB; 1 .. 15 return FMGPU_ERR_INVALID.  Window c is text[c B, min((c + 1) B, bytes)), c = 0 .. ceil(bytes / B) - 1.  Piece c is the
+ *     carry followed by window c: the carry of piece 0 is empty, the carry of piece c + 1 is what piece c did not consume.  A piece is parsed under the rules of
+ *     fmgpu_queries_parse, with `final` for the last window of a call whose own `final` is set.  A piece with no complete record is carried whole.
+ *   - What only later bytes can settle, a piece in front of the last one leaves unconsumed: a '\r' as its last byte with no '\n' behind it yet counts as a terminator to come
+ *     (so such a line is empty, not a FASTA text error), and FASTQ records that lie wholly or partly in empty lines at the very end of the piece are not yet records
+ *     (the end of the text may discard those lines).  With this the pieces give the whole-text result for every text and every B.
+ *   - last_chunks (fmgpu_feed_info) is the number of windows.  chunk_reads / chunk_symbols of the feed's config do not apply: a piece is a chunk.
+ *   - A piece of more than 2^32 - 2 bytes returns FMGPU_ERR_UNSUPPORTED (a record longer than that, or B too large); the whole text may be larger.
+ *   Where the bytes go
+ *   - A slot's device text buffer holds window c from a fixed offset H (the headroom) on: the upload does not depend on any parse result, so window c + 1 travels
+ *     while piece c is parsed and searched.  Pageable text goes through the slot's pinned buffer, moved by the feed's host workers (last_staged_bytes counts it);
+ *     pinned text is copied from where it lies.  The carry is copied device to device, on the compute stream, from the previous slot into [H - carry, H).  H starts as
+ *     min(B, 1 MiB); a carry longer than H regrows that slot's buffer with a headroom of twice the carry (rare, synchronised, not visible).
+ *   - last_uploaded_bytes counts the text bytes (and nothing else: the 256-byte table is not counted).
+ *   Capacity and counts
+ *   - out_stratum, out_names, out_quals and out_lens each hold read_capacity entries; any may be NULL, and with all four NULL read_capacity is ignored.  More reads
+ *     than read_capacity with any of them given: FMGPU_ERR_CAPACITY.  Positions and hits overflow as in fmgpu_feed_map.  In every capacity case all pieces still run,
+ *     all counts and *result are exact totals, and the contents of the arrays are unspecified.
+ *   Text errors
+ *   - FMGPU_ERR_INVALID with the message of fmgpu_queries_parse ("text error in line ..."), line and offset those of the whole text; *result as the whole-text parse
+ *     reports it (the records in front of the offending one).  Pieces behind the error do not run; the arrays are unspecified.  The feed serves further calls.
+ *   Errors, memory, streams
+ *   - Before any use of the device, FMGPU_ERR_INVALID for: a null f, result, symbol_of, what or out_count; a null text with bytes > 0; a null out with capacity > 0; a
+ *     null out_hits with hits_capacity > 0; an unknown format; chunk_bytes in 1 .. 15; what fmgpu_feed_map refuses in `what`.  bytes == 0 returns 0 with zero counts
+ *     and a zero result.  A device pointer in any argument returns FMGPU_ERR_INVALID (the feed rule).
+ *   - Text, parse scratch, batch, records and spans live in the slots and only ever grow (fmgpu_feed_info counts them): in steady state a piece allocates nothing.
+ *     DESIGN.md §4.15 lists the bytes per slot.  The feed's three streams are used and no more; each piece's parse reads two
+ *     words back (the compute stream is synchronised, as the search behind it does anyway).  One call at a time per feed.
+ *   - Not built: gzip input, multi-line FASTQ, both-strand batches, `_q4` slots, text through the plain search calls (locate = 0 returns ordered hit records),
+ *     overlap of one piece's search with the next piece's parse (one compute stream). */
+int fmgpu_feed_map_text(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final,
+                        const uint8_t* symbol_of, uint64_t chunk_bytes, const fmgpu_map_query* what,
+                        fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                        fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                        uint8_t* out_stratum, fmgpu_text_span* out_names, fmgpu_text_span* out_quals, uint64_t* out_lens,
+                        uint64_t read_capacity, fmgpu_parse_result* result,
+                        fmgpu_stats* search_stats, fmgpu_stats* locate_stats);
 
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
