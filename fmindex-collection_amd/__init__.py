@@ -515,6 +515,65 @@ def pack_queries_device(queries, sigma, complement=None, stream=None):
     return PackedQueries(packed, out_qoff, nreads)
 
 
+DNA5_COMPLEMENT = (0, 4, 3, 2, 1)                           # ranks $ A C G T: what strands="dna5" names
+
+
+def _complement(complement):
+    """a complement table (or "dna5") as a contiguous uint8 array of 1 .. 256 entries"""
+    comp = np.ascontiguousarray(np.asarray(DNA5_COMPLEMENT if isinstance(complement, str) and complement == "dna5" else complement, dtype=np.uint8)).reshape(-1)
+    if not 1 <= comp.size <= 256:
+        raise ValueError("a complement table has 1 .. 256 entries")
+    return comp
+
+
+def both_strands(queries, complement="dna5"):
+    """(qbuf, qoff) or a list of sequences -> (qbuf, qoff) of the doubled batch, byte for byte what fmgpu_queries_strands makes: read 2q = read q, read 2q + 1 = read q
+    reversed with complement[c] for a byte c < len(complement) and the byte itself otherwise; the batch starts at symbol 0."""
+    comp = _complement(complement)
+    qbuf, qoff = _host_batch(queries)
+    nq = len(qoff) - 1
+    if nq <= 0:
+        return np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint64)
+    first, last = int(qoff[0]), int(qoff[-1])
+    sym = qbuf[first:last].astype(np.uint8)
+    start = (qoff[:-1] - qoff[0]).astype(np.int64)
+    lens = np.diff(qoff.astype(np.int64))
+    table = np.arange(256, dtype=np.uint8)
+    table[:comp.size] = comp
+    rid = np.repeat(np.arange(nq), lens)
+    j = np.arange(sym.size, dtype=np.int64) - start[rid]
+    out = np.zeros(2 * sym.size, dtype=np.uint8)
+    out[2 * start[rid] + j] = sym
+    out[2 * start[rid] + 2 * lens[rid] - 1 - j] = table[sym]
+    out_qoff = np.zeros(2 * nq + 1, dtype=np.uint64)
+    out_qoff[0:-1:2] = 2 * start
+    out_qoff[1::2] = 2 * start + lens
+    out_qoff[-1] = 2 * sym.size
+    return out, out_qoff
+
+
+def both_strands_device(queries, complement="dna5", stream=None):
+    """fmgpu_queries_strands: the batch ((qbuf, qoff) of numpy arrays or DeviceBuffers, or a list of sequences) doubled on the device -> (qbuf, qoff) of DeviceBuffers
+    (2 nq reads; the symbol buffer is padded by 16 bytes)"""
+    comp = _complement(complement)
+    qbuf, qoff, nq = _queries(queries)
+    ends = qoff if isinstance(qoff, np.ndarray) else qoff.to_array(np.uint64, nq + 1)
+    total = 2 * (int(ends[-1]) - int(ends[0])) if nq > 0 else 0
+    out, out_qoff = DeviceBuffer(total + 16), DeviceBuffer((2 * nq + 1) * 8)
+    capi.check(capi.lib().fmgpu_queries_strands(capi.ptr(qbuf), capi.ptr(qoff), nq, capi.ptr(comp), comp.size, capi.ptr(out), capi.ptr(out_qoff), stream))
+    return out, out_qoff
+
+
+def _strands(strands, pair):
+    """(capi.Strands or None, objects to keep alive) for map_reads / Feed.map / Feed.map_text"""
+    if strands is None:
+        if pair:
+            raise ValueError("pair=True needs strands=")
+        return None, None
+    comp = _complement(strands)
+    return capi.Strands(comp.ctypes.data_as(capi.u8p), comp.size, 1 if pair else 0), comp
+
+
 def _q4(queries, byte_call, q4_call):
     """the entry point that takes `queries`: the `_q4` one for a PackedQueries"""
     return q4_call if isinstance(queries, PackedQueries) else byte_call
@@ -806,25 +865,36 @@ class Feed:
         return (hits, st) if want_stats else hits
 
     def map(self, queries, errors=None, schemes=None, ng21=False, edit=True, n=UINT64_MAX, locate=True, want_hits=False, want_stratum=False, want_stats=False,
-            first_records=0, out=None):
+            first_records=0, out=None, strands=None, pair=False):
         """fmgpu_feed_map: what map_reads returns, chunk by chunk (a PackedQueries is not taken).  `out` = a POSITION_DTYPE array to write into (a pinned one is
-        written in place; it must hold every position)."""
+        written in place; it must hold every position).  strands= / pair= as map_reads (fmgpu_feed_map_strands; a flat batch)."""
         suffix, a, b, nq, keep = self._batch(queries)
         if suffix == "_q4":
             raise ValueError("a feed maps byte batches")
         what, alive = _map_query(errors, schemes, ng21, edit, n, locate, first_records)
+        st, comp = _strands(strands, pair)
+        if st is not None:
+            if suffix:                                       # (no `_v` form: a list of reads is flattened)
+                keep = flatten(queries)
+                a, b = capi.ptr(keep[0]), capi.ptr(keep[1])
+            res = _run_map(lambda *args: capi.lib().fmgpu_feed_map_strands(self._f, a, b, nq, C.byref(what), C.byref(st), *args), 2 * nq, what, want_hits, want_stratum,
+                           want_stats, out, False)
+            del keep, alive, comp
+            return res
         call = getattr(capi.lib(), "fmgpu_feed_map" + suffix)
         res = _run_map(lambda *args: call(self._f, a, b, nq, C.byref(what), *args), nq, what, want_hits, want_stratum, want_stats, out, False)
         del keep, alive
         return res
 
     def map_text(self, data, format, table, final=True, chunk_bytes=0, want_hits=False, want_stratum=False, want_names=False, want_quals=False, want_lens=False,
-                 want_stats=False, errors=None, schemes=None, ng21=False, edit=True, n=UINT64_MAX, locate=True, first_records=0, out=None, capacities=None):
+                 want_stats=False, errors=None, schemes=None, ng21=False, edit=True, n=UINT64_MAX, locate=True, first_records=0, out=None, capacities=None,
+                 strands=None, pair=False):
         """fmgpu_feed_map_text: the bytes of a read file -> MappedText, what map_reads(parse_queries(data)) returns plus the spans of the whole-text parse.  The text is
         the only thing uploaded: it travels in windows of chunk_bytes (0 = 64 MiB), each parsed and mapped on the device.  `data`: bytes, a numpy array (an np.memmap
         included) or a pinned buffer (PinnedBuffer.array(...), copied from where it lies); format / table as parse_queries; the mapping arguments as Feed.map.  The
         capacities (positions, hit records, reads) start as guesses, or as `capacities`; a capacity error reports the exact totals and the call runs once more with
-        them.  A text error raises TextError."""
+        them.  A text error raises TextError.  strands= / pair= as map_reads (fmgpu_feed_map_text_strands): qidx and the stratum array (2 entries per read) count
+        in the doubled batch; names, quals and lens stay per read of the file."""
         fmt = _TEXT_FORMATS[format] if isinstance(format, str) else int(format)
         table = np.ascontiguousarray(np.asarray(table, dtype=np.uint8))
         if table.size != 256:
@@ -844,6 +914,9 @@ class Feed:
         sstats, lstats = (capi.Stats * nst)(), capi.Stats()
         L, res = capi.lib(), capi.ParseResult()
         want_reads = want_stratum or want_names or want_quals or want_lens
+        st, comp = _strands(strands, pair)
+        mult = 2 if st is not None else 1
+        call = L.fmgpu_feed_map_text if st is None else (lambda *a: L.fmgpu_feed_map_text_strands(*a[:8], C.byref(st), *a[8:]))
         rcap = max(1024, nbytes // 64) if want_reads else 0
         cap = len(out) if out is not None else (max(1024, 4 * rcap, nbytes // 16) if locate else 0)
         hcap = max(1024, 4 * rcap, nbytes // 16) if want_hits else 0
@@ -853,11 +926,11 @@ class Feed:
         for _ in range(2):
             pos = out if out is not None else np.zeros(max(cap, 1), dtype=POSITION_DTYPE)
             hits = np.zeros(max(hcap, 1), dtype=HIT_DTYPE) if want_hits else None
-            stratum = np.full(max(rcap, 1), 255, dtype=np.uint8) if want_stratum else None
+            stratum = np.full(max(mult * rcap, 1), 255, dtype=np.uint8) if want_stratum else None
             names = np.zeros(max(rcap, 1), dtype=capi.TEXT_SPAN_DTYPE) if want_names else None
             quals = np.zeros(max(rcap, 1), dtype=capi.TEXT_SPAN_DTYPE) if want_quals else None
             lens = np.zeros(max(rcap, 1), dtype=np.uint64) if want_lens else None
-            rc = L.fmgpu_feed_map_text(self._f, p, nbytes, fmt, 1 if final else 0, capi.ptr(table), int(chunk_bytes or 0), C.byref(what), capi.ptr(pos), cap, C.byref(cnt),
+            rc = call(self._f, p, nbytes, fmt, 1 if final else 0, capi.ptr(table), int(chunk_bytes or 0), C.byref(what), capi.ptr(pos), cap, C.byref(cnt),
                                        capi.ptr(hits), hcap, C.byref(hcnt), capi.ptr(stratum), capi.ptr(names), capi.ptr(quals), capi.ptr(lens), rcap, C.byref(res),
                                        sstats if want_stats else None, C.byref(lstats) if want_stats else None)
             if rc != capi.FMGPU_ERR_CAPACITY:
@@ -875,7 +948,8 @@ class Feed:
         m = MappedText()
         m.positions = pos[: cnt.value]
         m.hits = np.ascontiguousarray(hits[: hcnt.value]) if want_hits else None
-        m.stratum, m.names, m.quals, m.lens = (None if a is None else a[:reads] for a in (stratum, names, quals, lens))
+        m.stratum = None if stratum is None else stratum[:mult * reads]
+        m.names, m.quals, m.lens = (None if a is None else a[:reads] for a in (names, quals, lens))
         m.reads, m.symbols, m.consumed, m.foreign = reads, int(res.symbols), int(res.consumed), int(res.foreign)
         m.stats = ([sstats[i] for i in range(nst)], lstats) if want_stats else None
         return m
@@ -991,17 +1065,20 @@ class search_ng21:
         return search_ng21.search(index, queries, scheme, capacity, want_stats, n)
 
     @staticmethod
-    def search_best(index, queries, schemes, n=UINT64_MAX, capacity=None, want_stratum=False, want_stats=False):
+    def search_best(index, queries, schemes, n=UINT64_MAX, capacity=None, want_stratum=False, want_stats=False, pairs=False):
         """search_ng21::search_best (:242-264): per query the first scheme of the list that reports any row — one fmgpu_search_best_ng21 call: the ladder is cut on
         the device, so `queries` may be DeviceBuffers or a PackedQueries as they are.  want_stratum: also the uint8 array out_stratum (255 = no scheme found the
-        read); want_stats: also the list of the strata's Stats.  Returned as (hits[, stratum][, stats])."""
+        read); want_stats: also the list of the strata's Stats.  Returned as (hits[, stratum][, stats]).  pairs=True: reads 2j and 2j + 1 are the strands of one read
+        (fmgpu_search_best_ng21_pairs; byte batches)."""
         qbuf, qoff, nq = _queries(queries)
         keep = [tuple(_u64(x) for x in sch) for sch in schemes]
         arr = (capi.ExpandedScheme * max(len(keep), 1))()
         for sc, (pi, l, u) in zip(arr, keep):
             sc.n_searches, sc.length = (pi.shape if pi.ndim == 2 else (0, 0))
             sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
-        call = _q4(queries, capi.lib().fmgpu_search_best_ng21, capi.lib().fmgpu_search_best_ng21_q4)
+        if pairs and isinstance(queries, PackedQueries):
+            raise ValueError("the pair ladder takes byte batches")
+        call = capi.lib().fmgpu_search_best_ng21_pairs if pairs else _q4(queries, capi.lib().fmgpu_search_best_ng21, capi.lib().fmgpu_search_best_ng21_q4)
         return _run_best(lambda out, c, cnt, stratum, st: call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, arr, len(keep), n, capi.ptr(out), c, C.byref(cnt),
                                                                capi.ptr(stratum), st, None), nq, len(keep), capacity, want_stratum, want_stats)
 
@@ -1058,13 +1135,16 @@ def search_n(index, queries, errors, n, edit=True, compat_auto_scheme=False):
     return _auto_scheme_search(index, queries, errors, n, edit, compat_auto_scheme)
 
 
-def search_best(index, queries, max_errors, n=UINT64_MAX, edit=True, schemes=None, capacity=None, want_stratum=False, want_stats=False):
+def search_best(index, queries, max_errors, n=UINT64_MAX, edit=True, schemes=None, capacity=None, want_stratum=False, want_stats=False, pairs=False):
     """search_ng26::search_best (search/SearchNg26.h:447-487).
     schemes=None: the convenience overload (:476-487) — the whole batch is searched with 0, 1, ... max_errors - 1 errors (the loop ends
     BEFORE max_errors, as in the reference) and stops at the first error count for which ANY query reports a hit: a host loop, nothing is cut per read.
     schemes=[(scheme, partition), ...]: the explicit overload (:447-473) — per query the first scheme that reports anything wins: one fmgpu_search_best call, the
     ladder is cut on the device, so `queries` may be DeviceBuffers or a PackedQueries as they are.  want_stratum: also the uint8 array out_stratum (255 = no scheme
-    found the read); want_stats: also the list of the strata's Stats.  Returned as (hits[, stratum][, stats])."""
+    found the read); want_stats: also the list of the strata's Stats.  Returned as (hits[, stratum][, stats]).  pairs=True (explicit schemes, byte batches): reads 2j and
+    2j + 1 are the two strands of one read — fmgpu_search_best_pairs: once either is found, neither goes on, and both stratum entries name that stratum."""
+    if pairs and (schemes is None or isinstance(queries, PackedQueries)):
+        raise ValueError("the pair ladder takes explicit schemes and byte batches")
     if schemes is None:
         for k in range(int(max_errors)):
             hits = _auto_scheme_search(index, queries, k, n, edit, False)
@@ -1079,7 +1159,7 @@ def search_best(index, queries, max_errors, n=UINT64_MAX, edit=True, schemes=Non
         sc.pi, sc.l, sc.u = (x.ctypes.data_as(capi.u64p) for x in (pi, l, u))
         sc.partition = part.ctypes.data_as(capi.u64p) if part is not None else None
         sc.edit = 1 if edit else 0
-    call = _q4(queries, capi.lib().fmgpu_search_best, capi.lib().fmgpu_search_best_q4)
+    call = capi.lib().fmgpu_search_best_pairs if pairs else _q4(queries, capi.lib().fmgpu_search_best, capi.lib().fmgpu_search_best_q4)
     return _run_best(lambda out, c, cnt, stratum, st: call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, arr, len(keep), n, capi.ptr(out), c, C.byref(cnt),
                                                            capi.ptr(stratum), st, None), nq, len(keep), capacity, want_stratum, want_stats)
 
@@ -1262,13 +1342,23 @@ def _run_map(call, nq, what, want_hits, want_stratum, want_stats, out, with_stre
 
 
 def map_reads(index, queries, errors=None, schemes=None, ng21=False, edit=True, n=UINT64_MAX, locate=True, want_hits=False, want_stratum=False, want_stats=False,
-              first_records=0):
+              first_records=0, strands=None, pair=False):
     """fmgpu_map: fmc::Search's whole path in one call — search (exact, a best-stratum ladder of schemes, or a search_ng21 ladder), the records put into callback order
     and every row located, all on the device.  `queries` as for the searches (list of reads, (qbuf, qoff) of numpy arrays or DeviceBuffers, PackedQueries); see
     _map_query for errors / schemes.  Returns the POSITION_DTYPE records (qidx, seq_id, pos, errors, hit) in the reference's report order[, the HIT_DTYPE records `hit`
-    indexes][, the uint8 stratum of every read, 255 = unfound][, (search stats per stratum, locate stats)].  locate=False stops after the hit records."""
+    indexes][, the uint8 stratum of every read, 255 = unfound][, (search stats per stratum, locate stats)].  locate=False stops after the hit records.
+    strands= (a complement table, or "dna5"): fmgpu_map_strands — both strands of every read, the second made on the device; qidx and the stratum array count in the
+    doubled batch (read = qidx >> 1, strand = qidx & 1).  pair=True: best stratum per read (the pair ladder)."""
     qbuf, qoff, nq = _queries(queries)
     what, alive = _map_query(errors, schemes, ng21, edit, n, locate, first_records)
+    st, comp = _strands(strands, pair)
+    if st is not None:
+        if isinstance(queries, PackedQueries):
+            raise ValueError("both strands are mapped from byte batches")
+        res = _run_map(lambda *args: capi.lib().fmgpu_map_strands(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(what), C.byref(st), *args), 2 * nq, what, want_hits,
+                       want_stratum, want_stats, None, True)
+        del alive, comp
+        return res
     call = _q4(queries, capi.lib().fmgpu_map, capi.lib().fmgpu_map_q4)
     res = _run_map(lambda *args: call(index._h, capi.ptr(qbuf), capi.ptr(qoff), nq, C.byref(what), *args), nq, what, want_hits, want_stratum, want_stats, None, True)
     del alive

@@ -135,6 +135,14 @@ MAP_EXACT, MAP_SCHEME, MAP_NG21 = 0, 1, 2
 assert C.sizeof(MapQuery) == 40
 
 
+class Strands(C.Structure):
+    """fmgpu_strands: the complement table (host memory, n entries) of the both-strand calls, and whether the ladder treats the two strands of a read as a pair"""
+    _fields_ = [("complement", u8p), ("n", C.c_int32), ("pair", C.c_int32)]
+
+
+assert C.sizeof(Strands) == 16
+
+
 class TextSpan(C.Structure):
     """fmgpu_text_span: bytes offset .. offset + len - 1 of a parsed text (fmgpu_queries_parse: a read's name or quality line)"""
     _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64)]
@@ -176,6 +184,7 @@ EXPORTS = [
     "fmgpu_feed_search_scheme", "fmgpu_feed_search_scheme_v", "fmgpu_feed_info", "fmgpu_malloc_host", "fmgpu_free_host",
     "fmgpu_map", "fmgpu_map_q4", "fmgpu_hits_from_intervals", "fmgpu_feed_map", "fmgpu_feed_map_v",
     "fmgpu_queries_parse", "fmgpu_feed_map_text",
+    "fmgpu_queries_strands", "fmgpu_search_best_pairs", "fmgpu_search_best_ng21_pairs", "fmgpu_map_strands", "fmgpu_feed_map_strands", "fmgpu_feed_map_text_strands",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -327,6 +336,13 @@ def lib():
         L.fmgpu_feed_map_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(MapQuery),
                                           C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ParseResult), C.POINTER(Stats), C.POINTER(Stats)]
+    if hasattr(L, "fmgpu_map_strands"):                       # (FMGPU_LIBRARY may name an older build of the same ABI)
+        L.fmgpu_queries_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmgpu_search_best_pairs.argtypes = L.fmgpu_search_best.argtypes
+        L.fmgpu_search_best_ng21_pairs.argtypes = L.fmgpu_search_best_ng21.argtypes
+        L.fmgpu_map_strands.argtypes = L.fmgpu_map.argtypes[:5] + [C.POINTER(Strands)] + L.fmgpu_map.argtypes[5:]
+        L.fmgpu_feed_map_strands.argtypes = L.fmgpu_map_strands.argtypes[:-1]
+        L.fmgpu_feed_map_text_strands.argtypes = L.fmgpu_feed_map_text.argtypes[:8] + [C.POINTER(Strands)] + L.fmgpu_feed_map_text.argtypes[8:]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

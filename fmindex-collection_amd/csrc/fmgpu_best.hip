@@ -1,6 +1,7 @@
 // fmgpu_best.hip — best-stratum search (include/fmgpu.h: fmgpu_search_best*): a ladder of schemes walked over one batch, every stratum over the reads that no earlier
 // stratum found.  Marking the found reads, selecting and compacting the others and renaming qidx happen here, on the device; the strata themselves are the routed
-// fmgpu_search_scheme / fmgpu_search_ng21 calls on device pointers.  Nothing here depends on the row width.
+// fmgpu_search_scheme / fmgpu_search_ng21 calls on device pointers.  The `_pairs` forms treat reads 2j and 2j + 1 as the two strands of one read: once either is
+// found, neither goes on (k_best_pairs).  Nothing here depends on the row width.
 #include "fmgpu_common.h"
 
 #include <hipcub/hipcub.hpp>
@@ -20,6 +21,20 @@ __global__ __launch_bounds__(256) void k_best_mark(fmgpu_hit* __restrict__ rec, 
             if (out_stratum) out_stratum[q] = (uint8_t)stratum;
         }
         rec[i].qidx = q;
+    }
+}
+
+// ---- the pair ladder: reads 2j and 2j + 1 of the sub-batch are the two strands of one read (selection keeps or drops both, so they stay adjacent).  A pair is found
+// when either of its reads is: both flags are set, and both entries of out_stratum name the stratum.  One thread per pair, after k_best_mark.
+__global__ __launch_bounds__(256) void k_best_pairs(uint8_t* __restrict__ found, uint64_t npairs, const uint32_t* __restrict__ qmap, uint8_t* __restrict__ out_stratum,
+                                                    uint32_t stratum) {
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < npairs; j += (uint64_t)gridDim.x * blockDim.x) {
+        if (!(found[2 * j] | found[2 * j + 1])) continue;
+        found[2 * j] = 1; found[2 * j + 1] = 1;
+        if (out_stratum) {
+            out_stratum[qmap ? qmap[2 * j] : 2 * j] = (uint8_t)stratum;
+            out_stratum[qmap ? qmap[2 * j + 1] : 2 * j + 1] = (uint8_t)stratum;
+        }
     }
 }
 
@@ -89,8 +104,9 @@ static int fill_unfound(uint8_t* out_stratum, uint64_t nq, hipStream_t stream) {
 
 template <class Scheme>
 static int run_best(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const Scheme* schemes, int32_t n_schemes, uint64_t max_hits, fmgpu_hit* out,
-                    uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, fmgpu_stats* stats, hipStream_t stream, bool packed) {
+                    uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, fmgpu_stats* stats, hipStream_t stream, bool packed, bool pairs = false) {
     if (n_schemes < 0 || n_schemes > 254) return fail(FMGPU_ERR_INVALID, "n_schemes must be in [0, 254] (out_stratum keeps 255 for an unfound read)");
+    if (pairs && (nq & 1)) return fail(FMGPU_ERR_INVALID, "a pair ladder takes an even number of reads (reads 2j and 2j + 1 are a pair)");
     if (out_count) *out_count = 0;
     if (stats) for (int32_t i = 0; i < n_schemes; ++i) stats[i] = fmgpu_stats{};
     if (n_schemes == 0 || nq == 0) return fill_unfound(out_stratum, nq, stream);
@@ -173,6 +189,11 @@ static int run_best(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, 
             dim3 grid; if ((rc = grid_of(cnt, &grid, 1u << 16))) return rc;
             k_best_mark<<<grid, dim3(256), 0, stream>>>(dout + produced, cnt, found, cur_n, cur_map, dstratum, (uint32_t)i);
             FM_LAUNCHED("k_best_mark");
+            if (pairs) {
+                dim3 pgrid; if ((rc = grid_of(cur_n / 2, &pgrid, 1u << 16))) return rc;
+                k_best_pairs<<<pgrid, dim3(256), 0, stream>>>(found, cur_n / 2, cur_map, dstratum, (uint32_t)i);
+                FM_LAUNCHED("k_best_pairs");
+            }
         }
         produced += cnt;
         if (i + 1 == n_schemes) break;
@@ -194,6 +215,7 @@ static int run_best(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, 
         FM_HIP(hipStreamSynchronize(stream));
         if (tally[0] == 0) break;                                   // every read has been found
         if (tally[0] > cur_n) return fail(FMGPU_ERR_HIP, "best-stratum selection returned more reads than it was given");
+        if (pairs && (tally[0] & 1)) return fail(FMGPU_ERR_HIP, "pair ladder: the selection split a pair");
         // one scratch for every remainder: the later ones are subsets of the first, and stream order puts a gather behind the search that read the scratch before
         if (!symbols.p && (rc = symbols.alloc(tally[1] + 16))) return rc;
         if (tally[1] + 16 > symbols.bytes) return fail(FMGPU_ERR_HIP, "best-stratum remainder grew");
@@ -226,6 +248,14 @@ int fmgpu_search_best(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff
 int fmgpu_search_best_ng21(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_expanded_scheme* schemes, int32_t n_schemes,
                            uint64_t max_hits_per_query, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, fmgpu_stats* stats, void* stream) {
     return run_best(h, qbuf, qoff, nq, schemes, n_schemes, max_hits_per_query, out, capacity, out_count, out_stratum, stats, (hipStream_t)stream, false);
+}
+int fmgpu_search_best_pairs(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* schemes, int32_t n_schemes, uint64_t max_hits_per_query,
+                            fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, fmgpu_stats* stats, void* stream) {
+    return run_best(h, qbuf, qoff, nq, schemes, n_schemes, max_hits_per_query, out, capacity, out_count, out_stratum, stats, (hipStream_t)stream, false, true);
+}
+int fmgpu_search_best_ng21_pairs(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_expanded_scheme* schemes, int32_t n_schemes,
+                                 uint64_t max_hits_per_query, fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, fmgpu_stats* stats, void* stream) {
+    return run_best(h, qbuf, qoff, nq, schemes, n_schemes, max_hits_per_query, out, capacity, out_count, out_stratum, stats, (hipStream_t)stream, false, true);
 }
 int fmgpu_search_best_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, const fmgpu_scheme* schemes, int32_t n_schemes, uint64_t max_hits_per_query,
                          fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, fmgpu_stats* stats, void* stream) {

@@ -225,8 +225,17 @@ struct MapBuffer {
 int check_map_query(const fmgpu_map_query* what);             // kind, n_schemes, reserved: before anything else is looked at
 int check_map_schemes(fmgpu_index_t h, const fmgpu_map_query* what, bool packed);      // the schemes, the handle's kind, sigma for `_q4`, the annotated array
 // dq / doff / dstratum (may be null) are device memory; hits and positions hold H and P afterwards (*hit_count, *pos_count records); stats as fmgpu_map's
+// pairs: reads 2j and 2j + 1 are the strands of one read and the ladder is the pair ladder (fmgpu_search_best_pairs; byte batches only)
 int map_device(fmgpu_index_t h, const uint8_t* dq, const uint64_t* doff, uint64_t nq, const fmgpu_map_query* what, bool packed, MapBuffer* hits, MapBuffer* positions,
-               MapBuffer* intervals, uint8_t* dstratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, hipStream_t stream, uint64_t* hit_count, uint64_t* pos_count);
+               MapBuffer* intervals, uint8_t* dstratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, hipStream_t stream, uint64_t* hit_count, uint64_t* pos_count,
+               bool pairs);
+// fmgpu_queries_strands' passes on device buffers (fmgpu_strands.hip), shared by the one-shot call, fmgpu_map_strands and the strands calls of the feeds: the doubled
+// batch of dq / doff (nq reads, doff[0] need not be 0) into q2 (asked for its symbols + 16 bytes: the search kernels load whole aligned 16-byte pieces) and off2
+// (2 nq + 1 offsets from 0, two words of scratch behind them).  dtable: 256 entries on the device (strands_table).  One read-back: the check of the offsets.
+constexpr uint64_t kMaxStrandReads = (1ull << 30) - 1;        // the doubled batch stays inside the ladder's 2^31 - 1 reads and the 2^31 - 2 of fmgpu_hits_from_intervals
+int check_strands(const fmgpu_strands* strands);              // null pointers, n, pair
+void strands_table(const uint8_t* complement, int32_t n, uint8_t* table);      // table[c] = complement[c] for c < n, c otherwise; 256 entries
+int strands_device(const uint8_t* dq, const uint64_t* doff, uint64_t nq, const uint8_t* dtable, MapBuffer* q2, MapBuffer* off2, hipStream_t stream);
 // qidx += first in both lists, fmgpu_position::hit += hit_base (low 32 bits): a chunk's records renumbered for the caller's batch
 int map_rebase(fmgpu_hit* hits, uint64_t hit_count, fmgpu_position* positions, uint64_t pos_count, uint64_t first, uint64_t hit_base, hipStream_t stream);
 // fmgpu_queries_parse's passes on device text and growing buffers (fmgpu_parse.hip), shared by the one-shot call and fmgpu_feed_map_text.  names / quals may be null (not

@@ -67,10 +67,14 @@ struct Slot {
     hipEvent_t ev_text = nullptr;                            // the slot's text has been read: its piece is parsed and what it did not consume is copied out
     uint64_t headroom = 0, unconsumed = 0;                   // ... and where in d_text the unconsumed bytes start
     bool reads_down = false, names_in_place = false, quals_in_place = false, rlen_in_place = false;
+    // the strands calls: the slot's doubled batch (fmgpu_strands.hip), made on the device behind the upload or the parse
+    Grown d_q2, d_off2;
+    uint64_t str_first = 0, str_reads = 0;                   // the chunk's slice of out_stratum (the doubled numbering where both strands are mapped)
     Slot() { p_q.pinned = p_off.pinned = p_lb.pinned = p_len.pinned = p_hits.pinned = p_pos.pinned = p_str.pinned = p_text.pinned = p_names.pinned = p_quals.pinned = p_rlen.pinned = true; }
     std::vector<Grown*> buffers() {
         return {&d_q, &d_off, &d_lb, &d_len, &d_hits, &d_pos, &d_str, &p_q, &p_off, &p_lb, &p_len, &p_hits, &p_pos, &p_str,
-                &d_text, &d_acc, &d_lnbase, &d_kcnt, &d_hcnt, &d_tmp, &d_ls, &d_names, &d_quals, &d_rlen, &p_text, &p_names, &p_quals, &p_rlen};
+                &d_text, &d_acc, &d_lnbase, &d_kcnt, &d_hcnt, &d_tmp, &d_ls, &d_names, &d_quals, &d_rlen, &p_text, &p_names, &p_quals, &p_rlen,
+                &d_q2, &d_off2};
     }
 };
 
@@ -89,6 +93,8 @@ struct fmgpu_feed {
     std::vector<uint64_t> plan;                              // first read of every chunk of the current call, and nq behind them
     uint64_t hit_hint = 0;                                   // records the largest chunk so far produced: what a slot's hit buffer is sized for before it runs
     fmgpu::Grown d_table;                                    // fmgpu_feed_map_text: the call's symbol table
+    fmgpu::Grown d_comp;                                     // the strands calls: the call's complement table (256 entries), and its host side (it outlives the copy)
+    uint8_t comp_host[256] = {};
     uint64_t pinned_bytes = 0, device_bytes = 0, last_chunks = 0, last_staged = 0, last_uploaded = 0;
 };
 
@@ -418,13 +424,23 @@ int retire_map(Feed* f, Slot& sl, const MapOut& o) {
     };
     if (sl.hits_down && !sl.hits_in_place) copy(o.out_hits + sl.produced, sl.p_hits.p, (size_t)sl.hits * sizeof(fmgpu_hit));
     if (sl.pos_down && !sl.pos_in_place) copy(o.out + sl.located, sl.p_pos.p, (size_t)sl.positions * sizeof(fmgpu_position));
-    if (sl.str_down && !sl.str_in_place) copy(o.out_stratum + sl.first, sl.p_str.p, (size_t)sl.reads);
+    if (sl.str_down && !sl.str_in_place) copy(o.out_stratum + sl.str_first, sl.p_str.p, (size_t)sl.str_reads);
     return 0;
 }
 
-int run_map(Feed* f, const Batch& b, const fmgpu_map_query* what, const MapOut& o, uint64_t* out_count, uint64_t* out_hit_count, fmgpu_stats* search_stats,
-            fmgpu_stats* locate_stats) {
+// the call's complement table on the device, in front of the first chunk on the compute stream
+int upload_complement(Feed* f, const fmgpu_strands* strands) {
+    strands_table(strands->complement, strands->n, f->comp_host);
+    if (int rc = f->d_comp.need(256, &f->device_bytes)) return rc;
+    FM_HIP(hipMemcpyAsync(f->d_comp.p, f->comp_host, 256, hipMemcpyHostToDevice, f->comp));
+    return 0;
+}
+
+// strands != null: every chunk is doubled on the device (strands_device) behind its upload and mapped as 2 x reads; records and strata count in the doubled numbering
+int run_map(Feed* f, const Batch& b, const fmgpu_map_query* what, const fmgpu_strands* strands, const MapOut& o, uint64_t* out_count, uint64_t* out_hit_count,
+            fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
     begin_call(f);
+    const uint64_t mult = strands ? 2 : 1;
     const bool pos_pinned = o.capacity && pointer_kind(o.out) == 1, hits_pinned = o.hits_capacity && pointer_kind(o.out_hits) == 1;
     const bool str_pinned = o.out_stratum && pointer_kind(o.out_stratum) == 1;
     const int32_t nstats = std::max(1, what->n_schemes);
@@ -434,6 +450,7 @@ int run_map(Feed* f, const Batch& b, const fmgpu_map_query* what, const MapOut& 
     if ((rc = size_slots(f, max_reads, max_symbols, false, true, b.in_pinned))) return rc;
     const uint64_t chunks = f->plan.size() - 1;
     f->last_chunks = chunks;
+    if (strands && (rc = upload_complement(f, strands))) return rc;
     uint64_t produced = 0, located = 0;
     std::vector<fmgpu_stats> cs((size_t)nstats);
     auto body = [&]() -> int {
@@ -443,20 +460,29 @@ int run_map(Feed* f, const Batch& b, const fmgpu_map_query* what, const MapOut& 
             if ((r = retire_map(f, sl, o))) return r;
             Staged1 st;
             if ((r = upload_chunk(f, b, sl, c, false, &st))) return r;
-            if (o.out_stratum && (r = sl.d_str.need((size_t)st.reads, &f->device_bytes))) return r;
+            const uint64_t nreads = mult * st.reads;
+            if (o.out_stratum && (r = sl.d_str.need((size_t)nreads, &f->device_bytes))) return r;
             FM_HIP(hipStreamWaitEvent(f->comp, sl.ev_up, 0));
+            const uint8_t* mq = st.dq;
+            const uint64_t* moff = sl.d_off.as<uint64_t>();
+            if (strands) {
+                SlotBuffer bq2(&sl.d_q2, &f->device_bytes), boff2(&sl.d_off2, &f->device_bytes);
+                if ((r = strands_device(st.dq, sl.d_off.as<uint64_t>(), st.reads, f->d_comp.as<uint8_t>(), &bq2, &boff2, f->comp))) return r;
+                mq = sl.d_q2.as<uint8_t>(); moff = sl.d_off2.as<uint64_t>();
+            }
             // the chain on the slot's buffers (they only ever grow; a stage that overflows one grows it and runs again), then the chunk's records renumbered for the batch
             SlotBuffer bh(&sl.d_hits, &f->device_bytes), bp(&sl.d_pos, &f->device_bytes), bi(&sl.d_lb, &f->device_bytes);
             uint64_t cnt = 0, pcnt = 0;
             fmgpu_stats ls{};
-            if ((r = map_device(f->h, st.dq, sl.d_off.as<uint64_t>(), st.reads, what, false, &bh, &bp, &bi, o.out_stratum ? sl.d_str.as<uint8_t>() : nullptr,
-                                search_stats ? cs.data() : nullptr, locate_stats ? &ls : nullptr, f->comp, &cnt, &pcnt))) return r;
-            if ((r = map_rebase(sl.d_hits.as<fmgpu_hit>(), cnt, sl.d_pos.as<fmgpu_position>(), pcnt, f->plan[c], produced, f->comp))) return r;
+            if ((r = map_device(f->h, mq, moff, nreads, what, false, &bh, &bp, &bi, o.out_stratum ? sl.d_str.as<uint8_t>() : nullptr,
+                                search_stats ? cs.data() : nullptr, locate_stats ? &ls : nullptr, f->comp, &cnt, &pcnt, strands && strands->pair != 0))) return r;
+            if ((r = map_rebase(sl.d_hits.as<fmgpu_hit>(), cnt, sl.d_pos.as<fmgpu_position>(), pcnt, mult * f->plan[c], produced, f->comp))) return r;
             if (search_stats) for (int32_t i = 0; i < nstats; ++i) add_stats(&search_stats[i], cs[(size_t)i]);
             if (locate_stats) add_stats(locate_stats, ls);
             FM_HIP(hipEventRecord(sl.ev_comp, f->comp));
             FM_HIP(hipStreamWaitEvent(f->down, sl.ev_comp, 0));
             sl.first = f->plan[c]; sl.reads = st.reads; sl.hits = cnt; sl.produced = produced; sl.positions = pcnt; sl.located = located;
+            sl.str_first = mult * sl.first; sl.str_reads = nreads;
             // records beyond the caller's capacity are counted, not written
             sl.hits_down = o.out_hits && cnt && produced + cnt <= o.hits_capacity; sl.hits_in_place = hits_pinned;
             sl.pos_down = pcnt && located + pcnt <= o.capacity; sl.pos_in_place = pos_pinned;
@@ -472,9 +498,9 @@ int run_map(Feed* f, const Batch& b, const fmgpu_map_query* what, const MapOut& 
                 FM_HIP(hipMemcpyAsync(target, sl.d_pos.p, (size_t)pcnt * sizeof(fmgpu_position), hipMemcpyDeviceToHost, f->down));
             }
             if (sl.str_down) {
-                void* target = o.out_stratum + sl.first;
-                if (!str_pinned) { if ((r = sl.p_str.need((size_t)st.reads, &f->pinned_bytes))) return r; target = sl.p_str.p; }
-                FM_HIP(hipMemcpyAsync(target, sl.d_str.p, (size_t)st.reads, hipMemcpyDeviceToHost, f->down));
+                void* target = o.out_stratum + sl.str_first;
+                if (!str_pinned) { if ((r = sl.p_str.need((size_t)nreads, &f->pinned_bytes))) return r; target = sl.p_str.p; }
+                FM_HIP(hipMemcpyAsync(target, sl.d_str.p, (size_t)nreads, hipMemcpyDeviceToHost, f->down));
             }
             FM_HIP(hipEventRecord(sl.ev_down, f->down));
             sl.busy = true;
@@ -546,7 +572,7 @@ int regrow_text(Feed* f, Slot& sl, uint64_t carry, uint64_t window) {
 }
 
 int run_map_text(Feed* f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of, uint64_t B, const fmgpu_map_query* what,
-                 const TextOut& o, uint64_t* out_count, uint64_t* out_hit_count, fmgpu_parse_result* result, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
+                 const fmgpu_strands* strands, const TextOut& o, uint64_t* out_count, uint64_t* out_hit_count, fmgpu_parse_result* result, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
     begin_call(f);
     const bool in_pinned = pointer_kind(text) == 1;
     const bool pos_pinned = o.m.capacity && pointer_kind(o.m.out) == 1, hits_pinned = o.m.hits_capacity && pointer_kind(o.m.out_hits) == 1;
@@ -566,6 +592,8 @@ int run_map_text(Feed* f, const uint8_t* text, uint64_t bytes, int32_t format, i
     }
     if ((rc = f->d_table.need(256, &f->device_bytes))) return rc;
     FM_HIP(hipMemcpyAsync(f->d_table.p, symbol_of, 256, hipMemcpyHostToDevice, f->comp));
+    if (strands && (rc = upload_complement(f, strands))) return rc;
+    const uint64_t mult = strands ? 2 : 1;
 
     fmgpu_parse_result total;
     std::memset(&total, 0, sizeof total);
@@ -638,13 +666,20 @@ int run_map_text(Feed* f, const uint8_t* text, uint64_t bytes, int32_t format, i
             // its reads, mapped: run_map's chain and rebase, and the spans rebased to the caller's text
             uint64_t cnt = 0, pcnt = 0;
             if (reads) {
-                if (o.m.out_stratum && (r = sl.d_str.need((size_t)reads, &f->device_bytes))) return r;
+                if (o.m.out_stratum && (r = sl.d_str.need((size_t)(mult * reads), &f->device_bytes))) return r;
                 if (o.lens && (r = sl.d_rlen.need((size_t)reads * 8, &f->device_bytes))) return r;
                 SlotBuffer bh(&sl.d_hits, &f->device_bytes), bp(&sl.d_pos, &f->device_bytes), bi(&sl.d_lb, &f->device_bytes);
                 fmgpu_stats ls{};
-                if ((r = map_device(f->h, sl.d_q.as<uint8_t>(), sl.d_off.as<uint64_t>(), reads, what, false, &bh, &bp, &bi, o.m.out_stratum ? sl.d_str.as<uint8_t>() : nullptr,
-                                    search_stats ? cs.data() : nullptr, locate_stats ? &ls : nullptr, f->comp, &cnt, &pcnt))) return r;
-                if ((r = map_rebase(sl.d_hits.as<fmgpu_hit>(), cnt, sl.d_pos.as<fmgpu_position>(), pcnt, first, produced, f->comp))) return r;
+                const uint8_t* mq = sl.d_q.as<uint8_t>();
+                const uint64_t* moff = sl.d_off.as<uint64_t>();
+                if (strands) {                                            // the piece's reads doubled on the device: the second strand never crosses the bus
+                    SlotBuffer bq2(&sl.d_q2, &f->device_bytes), boff2(&sl.d_off2, &f->device_bytes);
+                    if ((r = strands_device(mq, moff, reads, f->d_comp.as<uint8_t>(), &bq2, &boff2, f->comp))) return r;
+                    mq = sl.d_q2.as<uint8_t>(); moff = sl.d_off2.as<uint64_t>();
+                }
+                if ((r = map_device(f->h, mq, moff, mult * reads, what, false, &bh, &bp, &bi, o.m.out_stratum ? sl.d_str.as<uint8_t>() : nullptr,
+                                    search_stats ? cs.data() : nullptr, locate_stats ? &ls : nullptr, f->comp, &cnt, &pcnt, strands && strands->pair != 0))) return r;
+                if ((r = map_rebase(sl.d_hits.as<fmgpu_hit>(), cnt, sl.d_pos.as<fmgpu_position>(), pcnt, mult * first, produced, f->comp))) return r;
                 if ((r = parse_piece_spans(o.names ? sl.d_names.as<fmgpu_text_span>() : nullptr, o.quals ? sl.d_quals.as<fmgpu_text_span>() : nullptr,
                                            o.lens ? sl.d_rlen.as<uint64_t>() : nullptr, sl.d_off.as<uint64_t>(), reads, total.consumed, format, f->comp))) return r;
                 if (search_stats) for (int32_t i = 0; i < nstats; ++i) add_stats(&search_stats[i], cs[(size_t)i]);
@@ -653,6 +688,7 @@ int run_map_text(Feed* f, const uint8_t* text, uint64_t bytes, int32_t format, i
             FM_HIP(hipEventRecord(sl.ev_comp, f->comp));
             FM_HIP(hipStreamWaitEvent(f->down, sl.ev_comp, 0));
             sl.first = first; sl.reads = reads; sl.hits = cnt; sl.produced = produced; sl.positions = pcnt; sl.located = located;
+            sl.str_first = mult * first; sl.str_reads = mult * reads;
             // records and reads beyond the caller's capacity are counted, not written
             sl.hits_down = o.m.out_hits && cnt && produced + cnt <= o.m.hits_capacity; sl.hits_in_place = hits_pinned;
             sl.pos_down = pcnt && located + pcnt <= o.m.capacity; sl.pos_in_place = pos_pinned;
@@ -667,7 +703,7 @@ int run_map_text(Feed* f, const uint8_t* text, uint64_t bytes, int32_t format, i
             };
             if ((r = download(sl.hits_down, hits_pinned, o.m.out_hits + produced, sl.p_hits, sl.d_hits, (size_t)cnt * sizeof(fmgpu_hit)))) return r;
             if ((r = download(sl.pos_down, pos_pinned, o.m.out + located, sl.p_pos, sl.d_pos, (size_t)pcnt * sizeof(fmgpu_position)))) return r;
-            if ((r = download(sl.str_down, str_pinned, o.m.out_stratum + first, sl.p_str, sl.d_str, (size_t)reads))) return r;
+            if ((r = download(sl.str_down, str_pinned, o.m.out_stratum + mult * first, sl.p_str, sl.d_str, (size_t)(mult * reads)))) return r;
             if ((r = download(sl.reads_down && o.names, names_pinned, o.names + first, sl.p_names, sl.d_names, (size_t)reads * sizeof(fmgpu_text_span)))) return r;
             if ((r = download(sl.reads_down && o.quals, quals_pinned, o.quals + first, sl.p_quals, sl.d_quals, (size_t)reads * sizeof(fmgpu_text_span)))) return r;
             if ((r = download(sl.reads_down && o.lens, lens_pinned, o.lens + first, sl.p_rlen, sl.d_rlen, (size_t)reads * 8))) return r;
@@ -753,6 +789,7 @@ int fmgpu_feed_destroy(fmgpu_feed_t f) {
         for (hipEvent_t ev : {sl.ev_up, sl.ev_comp, sl.ev_down, sl.ev_text}) if (ev) (void)hipEventDestroy(ev);
     }
     f->d_table.release(nullptr);
+    f->d_comp.release(nullptr);
     for (hipStream_t s : {f->up, f->comp, f->down}) if (s) (void)hipStreamDestroy(s);
     f->magic = 0;
     delete f;
@@ -825,31 +862,39 @@ int fmgpu_feed_search_scheme_v(fmgpu_feed_t f, const uint8_t* const* reads, cons
     return feed_scheme(f, b, scheme, max_hits_per_query, out, capacity, out_count, stats);
 }
 
-static int feed_map(fmgpu_feed_t f, Batch b, const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits,
+static int feed_map(fmgpu_feed_t f, Batch b, const fmgpu_map_query* what, bool both, const fmgpu_strands* strands, fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits,
                     uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
     if (out_count) *out_count = 0;
     if (out_hit_count) *out_hit_count = 0;
     if (int rc = check_map_query(what)) return rc;
+    if (both) if (int rc = check_strands(strands)) return rc;
     if (search_stats) for (int32_t i = 0; i < std::max(1, what->n_schemes); ++i) search_stats[i] = fmgpu_stats{};
     if (locate_stats) *locate_stats = fmgpu_stats{};
     if (b.nq == 0) return 0;                                                              // (before the feed is looked at; out_stratum untouched)
+    if (both && b.nq > kMaxStrandReads) return fail(FMGPU_ERR_UNSUPPORTED, "a both-strand batch holds at most 2^30 - 1 reads");
     if (!f || f->magic != 0x46454544u) return fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
     if (int rc = check_feed(f)) return rc;
     if (int rc = check_map_schemes(f->h, what, false)) return rc;
     if ((b.reads ? !b.lens : (!b.qbuf || !b.qoff)) || !out_count || (!out && capacity) || (!out_hits && hits_capacity))
         return fail(FMGPU_ERR_INVALID, b.reads || b.lens ? "reads / lens / out / out_count / out_hits is null" : "qbuf / qoff / out / out_count / out_hits is null");
-    if (int rc = no_device_memory({b.qbuf, b.qoff, b.reads, b.lens, out, out_count, out_hits, out_hit_count, out_stratum})) return rc;
+    if (int rc = no_device_memory({b.qbuf, b.qoff, b.reads, b.lens, out, out_count, out_hits, out_hit_count, out_stratum, both ? strands->complement : nullptr})) return rc;
     if (b.reads) if (int rc = no_device_memory({b.reads[0]})) return rc;
     b.in_pinned = b.qbuf && pointer_kind(b.qbuf) == 1;
     const MapOut o{out, capacity, out_hits, hits_capacity, out_stratum};
-    return run_map(f, b, what, o, out_count, out_hit_count, search_stats, locate_stats);
+    return run_map(f, b, what, both ? strands : nullptr, o, out_count, out_hit_count, search_stats, locate_stats);
 }
 
 int fmgpu_feed_map(fmgpu_feed_t f, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity,
                    uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats,
                    fmgpu_stats* locate_stats) {
     Batch b; b.qbuf = qbuf; b.qoff = qoff; b.nq = nq;
-    return feed_map(f, b, what, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats);
+    return feed_map(f, b, what, false, nullptr, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats);
+}
+int fmgpu_feed_map_strands(fmgpu_feed_t f, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what, const fmgpu_strands* strands,
+                           fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                           uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
+    Batch b; b.qbuf = qbuf; b.qoff = qoff; b.nq = nq;
+    return feed_map(f, b, what, true, strands, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats);
 }
 int fmgpu_feed_map_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t* lens, uint64_t nq, const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity,
                      uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats,
@@ -857,18 +902,19 @@ int fmgpu_feed_map_v(fmgpu_feed_t f, const uint8_t* const* reads, const uint64_t
     if (nq && !reads && !check_map_query(what))
         return (f && f->magic == 0x46454544u) ? fail(FMGPU_ERR_INVALID, "reads / lens / out / out_count / out_hits is null") : fail(FMGPU_ERR_INVALID, "feed is null or not a feed of this library");
     Batch b; b.reads = reads; b.lens = lens; b.nq = nq;
-    return feed_map(f, b, what, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats);
+    return feed_map(f, b, what, false, nullptr, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats);
 }
 
-int fmgpu_feed_map_text(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of, uint64_t chunk_bytes,
-                        const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity,
-                        uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_text_span* out_names, fmgpu_text_span* out_quals, uint64_t* out_lens, uint64_t read_capacity,
-                        fmgpu_parse_result* result, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
+static int feed_map_text(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of, uint64_t chunk_bytes,
+                         const fmgpu_map_query* what, bool both, const fmgpu_strands* strands, fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits,
+                         uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_text_span* out_names, fmgpu_text_span* out_quals, uint64_t* out_lens,
+                         uint64_t read_capacity, fmgpu_parse_result* result, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
     if (out_count) *out_count = 0;
     if (out_hit_count) *out_hit_count = 0;
     if (result) std::memset(result, 0, sizeof *result);
     if (!result || !symbol_of) return fail(FMGPU_ERR_INVALID, "result / symbol_of is null");
     if (int rc = check_map_query(what)) return rc;
+    if (both) if (int rc = check_strands(strands)) return rc;
     if (!out_count || (!out && capacity) || (!out_hits && hits_capacity)) return fail(FMGPU_ERR_INVALID, "out / out_count / out_hits is null");
     if (format != FMGPU_TEXT_LINES && format != FMGPU_TEXT_FASTA && format != FMGPU_TEXT_FASTQ) return fail(FMGPU_ERR_INVALID, "unknown text format " + std::to_string(format));
     if (!text && bytes) return fail(FMGPU_ERR_INVALID, "text is null");
@@ -879,9 +925,25 @@ int fmgpu_feed_map_text(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int
     if (bytes == 0) return 0;
     if (int rc = check_feed(f)) return rc;
     if (int rc = check_map_schemes(f->h, what, false)) return rc;
-    if (int rc = no_device_memory({text, symbol_of, out, out_count, out_hits, out_hit_count, out_stratum, out_names, out_quals, out_lens, result})) return rc;
+    if (int rc = no_device_memory({text, symbol_of, out, out_count, out_hits, out_hit_count, out_stratum, out_names, out_quals, out_lens, result, both ? strands->complement : nullptr})) return rc;
     const TextOut o{MapOut{out, capacity, out_hits, hits_capacity, out_stratum}, out_names, out_quals, out_lens, read_capacity};
-    return run_map_text(f, text, bytes, format, final, symbol_of, fmgpu_feed_host::text_window_bytes(chunk_bytes), what, o, out_count, out_hit_count, result, search_stats, locate_stats);
+    return run_map_text(f, text, bytes, format, final, symbol_of, fmgpu_feed_host::text_window_bytes(chunk_bytes), what, both ? strands : nullptr, o, out_count, out_hit_count, result,
+                        search_stats, locate_stats);
+}
+
+int fmgpu_feed_map_text(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of, uint64_t chunk_bytes,
+                        const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity,
+                        uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_text_span* out_names, fmgpu_text_span* out_quals, uint64_t* out_lens, uint64_t read_capacity,
+                        fmgpu_parse_result* result, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
+    return feed_map_text(f, text, bytes, format, final, symbol_of, chunk_bytes, what, false, nullptr, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum,
+                         out_names, out_quals, out_lens, read_capacity, result, search_stats, locate_stats);
+}
+int fmgpu_feed_map_text_strands(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final, const uint8_t* symbol_of, uint64_t chunk_bytes,
+                                const fmgpu_map_query* what, const fmgpu_strands* strands, fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits,
+                                uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_text_span* out_names, fmgpu_text_span* out_quals, uint64_t* out_lens,
+                                uint64_t read_capacity, fmgpu_parse_result* result, fmgpu_stats* search_stats, fmgpu_stats* locate_stats) {
+    return feed_map_text(f, text, bytes, format, final, symbol_of, chunk_bytes, what, true, strands, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum,
+                         out_names, out_quals, out_lens, read_capacity, result, search_stats, locate_stats);
 }
 
 }  // extern "C"

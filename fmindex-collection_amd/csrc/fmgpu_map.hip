@@ -1,4 +1,4 @@
-// fmgpu_map.hip — fmgpu_map / fmgpu_map_q4 (include/fmgpu.h): search, order and locate chained on the device.  The stages are the library's own calls on device
+// fmgpu_map.hip — fmgpu_map / fmgpu_map_q4 / fmgpu_map_strands (include/fmgpu.h): search, order and locate chained on the device.  The stages are the library's own calls on device
 // pointers — fmgpu_search_best* or fmgpu_search_exact*, fmgpu_hits_sort or fmgpu_hits_from_intervals, fmgpu_locate_hits — and the capacity-retry loop around each of them
 // lives here once: the hit and position lists are produced in scratch that grows until the stage fits, so the counts a caller gets are exact.  map_device is the chain on
 // device buffers; the one-shot calls below stage a batch around it, the feeds (fmgpu_feed.hip) run it per chunk on their slots' buffers.  Nothing here depends on the
@@ -56,8 +56,10 @@ int check_map_schemes(fmgpu_index_t h, const fmgpu_map_query* what, bool packed)
 }
 
 int map_device(fmgpu_index_t h, const uint8_t* dq, const uint64_t* doff, uint64_t nq, const fmgpu_map_query* what, bool packed, MapBuffer* hits, MapBuffer* positions,
-               MapBuffer* intervals, uint8_t* dstratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, hipStream_t stream, uint64_t* hit_count, uint64_t* pos_count) {
+               MapBuffer* intervals, uint8_t* dstratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, hipStream_t stream, uint64_t* hit_count, uint64_t* pos_count,
+               bool pairs) {
     *hit_count = *pos_count = 0;
+    if (pairs && packed) return fail(FMGPU_ERR_UNSUPPORTED, "the pair ladder takes byte batches");
     const int32_t nstats = std::max(1, what->n_schemes);
     if (search_stats) for (int32_t i = 0; i < nstats; ++i) search_stats[i] = fmgpu_stats{};
     if (locate_stats) *locate_stats = fmgpu_stats{};
@@ -88,10 +90,12 @@ int map_device(fmgpu_index_t h, const uint8_t* dq, const uint64_t* doff, uint64_
             if (what->kind == FMGPU_MAP_SCHEME) {
                 const fmgpu_scheme* s = static_cast<const fmgpu_scheme*>(what->schemes);
                 rc = packed ? ::fmgpu_search_best_q4(h, dq, doff, nq, s, what->n_schemes, max_hits, dh, cap, &cnt, dstratum, search_stats, stream)
+                     : pairs ? ::fmgpu_search_best_pairs(h, dq, doff, nq, s, what->n_schemes, max_hits, dh, cap, &cnt, dstratum, search_stats, stream)
                             : ::fmgpu_search_best(h, dq, doff, nq, s, what->n_schemes, max_hits, dh, cap, &cnt, dstratum, search_stats, stream);
             } else {
                 const fmgpu_expanded_scheme* s = static_cast<const fmgpu_expanded_scheme*>(what->schemes);
                 rc = packed ? ::fmgpu_search_best_ng21_q4(h, dq, doff, nq, s, what->n_schemes, max_hits, dh, cap, &cnt, dstratum, search_stats, stream)
+                     : pairs ? ::fmgpu_search_best_ng21_pairs(h, dq, doff, nq, s, what->n_schemes, max_hits, dh, cap, &cnt, dstratum, search_stats, stream)
                             : ::fmgpu_search_best_ng21(h, dq, doff, nq, s, what->n_schemes, max_hits, dh, cap, &cnt, dstratum, search_stats, stream);
             }
             if (rc != FMGPU_ERR_CAPACITY || attempt > what->n_schemes) break;
@@ -132,14 +136,16 @@ struct OwnBuffer : MapBuffer {                                      // the one-s
 
 int run_map(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity,
             uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats,
-            fmgpu_stats* locate_stats, hipStream_t stream, bool packed) {
+            fmgpu_stats* locate_stats, hipStream_t stream, bool packed, bool both = false, const fmgpu_strands* strands = nullptr) {
     if (out_count) *out_count = 0;
     if (out_hit_count) *out_hit_count = 0;
     if (int rc = check_map_query(what)) return rc;
+    if (both) if (int rc = check_strands(strands)) return rc;
     const int32_t nstats = std::max(1, what->n_schemes);
     if (search_stats) for (int32_t i = 0; i < nstats; ++i) search_stats[i] = fmgpu_stats{};
     if (locate_stats) *locate_stats = fmgpu_stats{};
     if (nq == 0) return 0;                                          // (before the handle is looked at; out_stratum untouched)
+    if (both && nq > kMaxStrandReads) return fail(FMGPU_ERR_UNSUPPORTED, "a both-strand batch holds at most 2^30 - 1 reads");
     if (int rc = check_map_schemes(h, what, packed)) return rc;
     if (!qbuf || !qoff || !out_count || (!out && capacity) || (!out_hits && hits_capacity)) return fail(FMGPU_ERR_INVALID, "qbuf / qoff / out / out_count / out_hits is null");
 
@@ -152,12 +158,24 @@ int run_map(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t
     else last = qoff[nq];
     if ((rc = sbuf.in(qbuf, packed ? (last + 1) / 2 : last, stream))) return rc;
     const uint8_t* dq = sbuf.dev ? (const uint8_t*)sbuf.dev : qbuf;  // (a batch without a symbol: the pointer is never read through)
+    const uint64_t* doff = (const uint64_t*)soff.dev;
+    // both strands: only the forward strand was staged, the doubled batch is made in the call's scratch and the chain runs on it
+    OwnBuffer q2, off2;
+    DBuf dtable;
+    if (both) {
+        uint8_t table[256];
+        strands_table(strands->complement, strands->n, table);
+        if ((rc = dtable.alloc(256))) return rc;
+        FM_HIP(hipMemcpyAsync(dtable.p, table, 256, hipMemcpyHostToDevice, stream));
+        if ((rc = strands_device(dq, doff, nq, dtable.as<uint8_t>(), &q2, &off2, stream))) { (void)hipStreamSynchronize(stream); return rc; }      // (it synchronises: `table` is done with)
+        dq = reinterpret_cast<const uint8_t*>(q2.p); doff = reinterpret_cast<const uint64_t*>(off2.p); nq *= 2;
+    }
     if ((rc = sstratum.out(out_stratum, out_stratum ? nq : 0, stream))) return rc;
 
     OwnBuffer hits, positions, intervals;
     uint64_t cnt = 0, pcnt = 0;
-    if ((rc = map_device(h, dq, (const uint64_t*)soff.dev, nq, what, packed, &hits, &positions, &intervals, out_stratum ? (uint8_t*)sstratum.dev : nullptr, search_stats,
-                         locate_stats, stream, &cnt, &pcnt))) return rc;
+    if ((rc = map_device(h, dq, doff, nq, what, packed, &hits, &positions, &intervals, out_stratum ? (uint8_t*)sstratum.dev : nullptr, search_stats,
+                         locate_stats, stream, &cnt, &pcnt, both && strands->pair != 0))) return rc;
     *out_count = pcnt;
     if (out_hit_count) *out_hit_count = cnt;
     if ((rc = sstratum.finish())) return rc;
@@ -180,6 +198,12 @@ int fmgpu_map(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64
               uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats,
               fmgpu_stats* locate_stats, void* stream) {
     return run_map(h, qbuf, qoff, nq, what, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats, (hipStream_t)stream, false);
+}
+int fmgpu_map_strands(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what, const fmgpu_strands* strands,
+                      fmgpu_position* out, uint64_t capacity, uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                      uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, void* stream) {
+    return run_map(h, qbuf, qoff, nq, what, out, capacity, out_count, out_hits, hits_capacity, out_hit_count, out_stratum, search_stats, locate_stats, (hipStream_t)stream, false,
+                   true, strands);
 }
 int fmgpu_map_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t* qoff, uint64_t nq, const fmgpu_map_query* what, fmgpu_position* out, uint64_t capacity,
                  uint64_t* out_count, fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count, uint8_t* out_stratum, fmgpu_stats* search_stats,

@@ -19,6 +19,10 @@
 //     in the reference's report order (fmc::Search's reportFunc arguments).
 //   * --mode map --feed --device-parse --no-reverse (no trimming, no read limit, not ng21): the bytes of the query file go through the feed as they are
 //     (fmgpu_feed_map_text through fmc::Feed::mapText); the reads are never vectors on the host.  The same --save_output file as without --device-parse.
+//   * --pair-strands (not in the reference; --mode map, not --packed): the reverse complements are made on the device and the ladder stops for a read once either of its
+//     strands is found (fmgpu_map_strands with pair = 1 through fmc::map / fmc::Feed::map with an fmc::Strands).  queryId in --save_output then counts read by read,
+//     2 * read + strand, instead of the forward reads followed by the reverse complements.  With --feed --device-parse (no trimming, no read limit, not ng21) the
+//     bytes of the query file go through fmgpu_feed_map_text_strands.
 //   * --device-parse (not in the reference): the --query file is read as bytes and parsed on the device (fmgpu_queries_parse through fmc::parseQueries); its first byte
 //     chooses FASTA ('>') or FASTQ ('@', read only this way).  On a well-formed FASTA — ends in a newline, no '>' inside sequence lines, no '\r' — the output is the
 //     same, byte for byte.  Elsewhere the device rules differ from the reader below: a '\r' in front of a newline belongs to the line end (the reader takes it for
@@ -54,7 +58,7 @@ struct Options {
     bool schemeDyn = false;
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false;
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -97,6 +101,7 @@ FlagRule const kFlags[] = {
     {"--packed", false, [](Options& o, char const*) { o.packed = true; }},
     {"--feed", false, [](Options& o, char const*) { o.feed = true; }},
     {"--device-parse", false, [](Options& o, char const*) { o.deviceParse = true; }},
+    {"--pair-strands", false, [](Options& o, char const*) { o.pairStrands = true; }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
     {"--ext", true, [](Options&, char const*) {}},
     {"--threads", true, [](Options&, char const*) {}},
@@ -319,10 +324,19 @@ struct Run {
     }
 
     // --mode map: the whole path as one fmgpu_map call (with --feed: fmgpu_feed_map_v); a packed batch goes through a feed as bytes
+    // --pair-strands: the example's own complement rule (ranks 0 .. 5: A <-> T, C <-> G, the others stay), the pair ladder
+    static fmc::Strands pairStrands() { return fmc::Strands{{0, 4, 3, 2, 1, 5}, true}; }
     template <typename Queries>
-    fmc::MapResult mapThroughFeed(Queries const& reads, fmc::MapQuery const& query) const { return fmc::Feed{index}.map(reads, query); }
+    fmc::MapResult mapThroughFeed(Queries const& reads, fmc::MapQuery const& query) const {
+        return config.pairStrands ? fmc::Feed{index}.map(reads, query, pairStrands()) : fmc::Feed{index}.map(reads, query);
+    }
     fmc::MapResult mapThroughFeed(fmc::PackedQueries const& reads, fmc::MapQuery const& query) const { return fmc::Feed{index}.map(reads.unpack(), query); }
 
+    template <typename Queries>
+    fmc::MapResult mapAtOnce(Queries const& reads, fmc::MapQuery const& query) const {
+        if constexpr (std::is_same_v<Queries, fmc::PackedQueries>) return fmc::map(index, reads, query);
+        else return config.pairStrands ? fmc::map(index, reads, query, pairStrands()) : fmc::map(index, reads, query);
+    }
     template <typename Queries>
     void oneErrorBudgetMapped(Algorithm kind, size_t k, Queries const& reads, size_t firstLength) const {
         StopWatch clock;
@@ -335,8 +349,8 @@ struct Run {
             query.kind = fmc::MapQuery::Kind::Ng21;
             for (size_t j = 0; j <= k; ++j) query.expanded.push_back(stretch(schemeByName(config.schemeName, j, j), firstLength));
         }
-        auto const mapped = config.feed ? mapThroughFeed(reads, query) : fmc::map(index, reads, query);
-        reportMapped(mapped, reads.size(), k, clock.reset());
+        auto const mapped = config.feed ? mapThroughFeed(reads, query) : mapAtOnce(reads, query);
+        reportMapped(mapped, (config.pairStrands ? 2 : 1) * reads.size(), k, clock.reset());
     }
 
     // --mode map --feed --device-parse without reverse complements: the bytes of the query file go through the feed as they are (fmgpu_feed_map_text through
@@ -350,9 +364,11 @@ struct Run {
             for (size_t j = 0; j <= k; ++j) query.schemes.emplace_back(schemeByName(config.schemeName, j, j), std::vector<size_t>{});
         }
         auto const table = Sigma == 6 ? fmc::SymbolTable::dna6(config.unknownToA) : fmc::SymbolTable::dna5(config.unknownToA);
-        auto const mapped = fmc::Feed{index}.mapText(std::string_view{text}, text[0] == '@' ? fmc::TextFormat::Fastq : fmc::TextFormat::Fasta, table, query);
+        auto const format = text[0] == '@' ? fmc::TextFormat::Fastq : fmc::TextFormat::Fasta;
+        auto const mapped = config.pairStrands ? fmc::Feed{index}.mapText(std::string_view{text}, format, table, query, pairStrands())
+                                               : fmc::Feed{index}.mapText(std::string_view{text}, format, table, query);
         if (mapped.foreign > 0) throw std::runtime_error("unknown alphabet");
-        reportMapped(mapped, mapped.size(), k, clock.reset());
+        reportMapped(mapped, (config.pairStrands ? 2 : 1) * mapped.size(), k, clock.reset());
     }
 
     void reportMapped(fmc::MapResult const& mapped, size_t nreads, size_t k, double tMap) const {
@@ -363,7 +379,7 @@ struct Run {
         std::sort(distinct.begin(), distinct.end());
         distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
         std::unordered_set<size_t> readsWithHits;
-        for (auto const& h : mapped.hits) readsWithHits.insert(h.qidx > reads.size() / 2 ? h.qidx - reads.size() / 2 : h.qidx);
+        for (auto const& h : mapped.hits) readsWithHits.insert(config.pairStrands ? h.qidx / 2 : h.qidx > reads.size() / 2 ? h.qidx - reads.size() / 2 : h.qidx);
         std::printf("%-15s %3zu: %10.3gs (%10.3gs+%10.3gs) %10.3gq/s - results: %10zu/%10zu/%10zu/%10zu - mem: %13zu\n", "str", k, tMap, tMap, 0.0,
                     reads.size() / tMap, mapped.positions.size(), mapped.positions.size(), distinct.size(), readsWithHits.size(), size_t{0});
         if (config.outputFile.empty()) return;
@@ -425,11 +441,14 @@ int main(int argc, char const* const* argv) try {
                     "          --device-parse (parse the query file on the device; FASTA or FASTQ by its first byte, '>' or '@'.  Same output on a\\\n"
                     "                 well-formed FASTA.  Unlike the default reader: \"\\r\\n\" ends a line, a '>' inside a line is an ordinary byte,\\\n"
                     "                 a last line without a newline keeps its last base, a name line at the end of the file is an empty read)\\\n"
+                    "          --pair-strands (--mode map: reverse complements made on the device, best stratum per read: once either strand of a\\\n"
+                    "                 read is found, neither is searched with more errors; queryId = 2 * read + strand)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }
     bool const needsFirstLength = std::any_of(config.algorithms.begin(), config.algorithms.end(), [](auto const& a) { return algorithmByName(a) == Algorithm::ng21; });
-    if (config.hitMode == HitMode::map && config.feed && config.deviceParse && !config.withReverseComplement && !config.packed && config.readLimit == 0 &&
+    if (config.pairStrands && (config.hitMode != HitMode::map || config.packed)) throw std::runtime_error("--pair-strands needs --mode map and byte reads (no --packed)");
+    if (config.hitMode == HitMode::map && config.feed && config.deviceParse && (!config.withReverseComplement || config.pairStrands) && !config.packed && config.readLimit == 0 &&
         config.trimTo == 0 && !needsFirstLength && !config.readsFasta.empty() && std::filesystem::exists(config.readsFasta)) {
         std::ifstream in{config.readsFasta, std::ios::binary};
         std::string const text{std::istreambuf_iterator<char>{in}, std::istreambuf_iterator<char>{}};
@@ -446,7 +465,7 @@ int main(int argc, char const* const* argv) try {
     // --packed: both strands come out of the device packer, unless reads get trimmed (the reference trims the doubled batch, and a trimmed reverse
     // complement is not the reverse complement of the trimmed read: then the strands are made here and only packed)
     bool const trims = config.trimTo != 0 && std::any_of(reads.begin(), reads.end(), [&](auto const& r) { return r.size() > config.trimTo; });
-    bool const strandsOnDevice = config.packed && config.withReverseComplement && !trims;
+    bool const strandsOnDevice = (config.packed && config.withReverseComplement && !trims) || config.pairStrands;
     size_t const strands = strandsOnDevice ? 2 : 1;
     if (config.withReverseComplement && !strandsOnDevice) reads = withReverseComplements(reads);
     if (!reads.empty()) {

@@ -831,7 +831,8 @@ void search(Index const& index, PackedQueries const& queries, size_t maxErrors, 
 namespace detail2 {
 template <bool Edit, typename Index>
 std::vector<fmgpu_hit> run_best(Index const& index, std::vector<uint8_t> const& buf, std::vector<uint64_t> const& off,
-                                std::vector<std::tuple<search_scheme::Scheme, std::vector<size_t>>> const& schemes, size_t n, bool q4 = false) {
+                                std::vector<std::tuple<search_scheme::Scheme, std::vector<size_t>>> const& schemes, size_t n, bool q4 = false,
+                                bool pairs = false) {
     size_t nq = off.size() - 1;
     if (nq == 0 || n == 0) return {};
     struct Flat { std::vector<uint64_t> pi, l, u, part; };
@@ -853,7 +854,7 @@ std::vector<fmgpu_hit> run_best(Index const& index, std::vector<uint8_t> const& 
     }
     if (ladder.empty()) return {};
     return detail::run_hits(nq, [&](fmgpu_hit* out, uint64_t cap, uint64_t* count) {
-        return (q4 ? fmgpu_search_best_q4 : fmgpu_search_best)(index.handle, buf.data(), off.data(), nq, ladder.data(), static_cast<int32_t>(ladder.size()), n, out, cap, count,
+        return (pairs ? fmgpu_search_best_pairs : q4 ? fmgpu_search_best_q4 : fmgpu_search_best)(index.handle, buf.data(), off.data(), nq, ladder.data(), static_cast<int32_t>(ladder.size()), n, out, cap, count,
                                                                nullptr, nullptr, nullptr);
     }, true);
 }
@@ -870,6 +871,16 @@ template <bool Edit = true, typename Index, typename Delegate>
 void search_best(Index const& index, PackedQueries const& queries, std::vector<std::tuple<search_scheme::Scheme, std::vector<size_t>>> const& schemes,
                  Delegate&& delegate, size_t n = std::numeric_limits<size_t>::max()) {
     auto hits = detail2::run_best<Edit>(index, queries.packed, queries.qoff, schemes, n, true);
+    detail::report(index, hits, delegate);
+}
+// search_best_pairs<Edit>: search_best over a batch whose reads 2j and 2j + 1 are the two strands of one read (fmc::bothStrands): one fmgpu_search_best_pairs call —
+// once either strand of a read is found, neither goes on.  The delegate sees qidx of the doubled batch.
+template <bool Edit = true, typename Index, typename Queries, typename Delegate>
+void search_best_pairs(Index const& index, Queries const& queries, std::vector<std::tuple<search_scheme::Scheme, std::vector<size_t>>> const& schemes,
+                       Delegate&& delegate, size_t n = std::numeric_limits<size_t>::max()) {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    auto hits = detail2::run_best<Edit>(index, buf, off, schemes, n, false, true);
     detail::report(index, hits, delegate);
 }
 // search_best<Edit>(index, queries, maxErrors, delegate, n) — search/SearchNg26.h:476-487: the whole batch with 0, 1, ... maxErrors - 1
@@ -967,7 +978,7 @@ std::vector<fmgpu_hit> run(Index const& index, std::vector<uint8_t> const& buf, 
 // without a search finds nothing and is left out)
 template <typename Index, typename Delegate>
 void best(Index const& index, std::vector<uint8_t> const& buf, std::vector<uint64_t> const& off, std::vector<search_scheme::Scheme> const& schemes, size_t n,
-          Delegate&& delegate, bool q4 = false) {
+          Delegate&& delegate, bool q4 = false, bool pairs = false) {
     size_t nq = off.size() - 1;
     struct Flat { std::vector<uint64_t> pi, l, u; };
     std::vector<Flat> flat;
@@ -987,7 +998,7 @@ void best(Index const& index, std::vector<uint8_t> const& buf, std::vector<uint6
     std::vector<fmgpu_hit> hits;
     if (nq != 0 && !ladder.empty())
         hits = detail::run_hits(nq, [&](fmgpu_hit* out, uint64_t cap, uint64_t* count) {
-            return (q4 ? fmgpu_search_best_ng21_q4 : fmgpu_search_best_ng21)(index.handle, buf.data(), off.data(), nq, ladder.data(), static_cast<int32_t>(ladder.size()), n, out,
+            return (pairs ? fmgpu_search_best_ng21_pairs : q4 ? fmgpu_search_best_ng21_q4 : fmgpu_search_best_ng21)(index.handle, buf.data(), off.data(), nq, ladder.data(), static_cast<int32_t>(ladder.size()), n, out,
                                                                              cap, count, nullptr, nullptr, nullptr);
         }, true);
     detail::report(index, hits, delegate);
@@ -1030,6 +1041,14 @@ void search_best(Index const& index, Queries const& queries, std::vector<search_
 template <typename Index, typename Delegate>
 void search_best(Index const& index, PackedQueries const& queries, std::vector<search_scheme::Scheme> const& schemes, Delegate&& delegate) {
     detail2::best(index, queries.packed, queries.qoff, schemes, std::numeric_limits<size_t>::max(), std::forward<Delegate>(delegate), true);
+}
+// search_best_pairs: search_best_n over a batch whose reads 2j and 2j + 1 are the two strands of one read (one fmgpu_search_best_ng21_pairs call)
+template <typename Index, typename Queries, typename Delegate>
+void search_best_pairs(Index const& index, Queries const& queries, std::vector<search_scheme::Scheme> const& schemes, Delegate&& delegate,
+                       size_t n = std::numeric_limits<size_t>::max()) {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    detail2::best(index, buf, off, schemes, n, std::forward<Delegate>(delegate), false, true);
 }
 // search_best_n(index, queries, search_schemes, n, delegate) — :267-293
 template <typename Index, typename Queries, typename Delegate>
@@ -1248,6 +1267,40 @@ auto map(Index const& index, Queries const& queries, MapQuery const& query) -> M
         return fmgpu_map(index.handle, buf.data(), off.data(), nq, &flat.what, out, cap, count, hits, hcap, hcount, stratum, nullptr, nullptr, nullptr);
     });
 }
+// Both strands (include/fmgpu.h: fmgpu_map_strands): fmc::map(index, reads, query, strands) maps every read and its reverse complement, the second strand made on the
+// device.  qidx and MapResult::stratum count in the doubled batch: read = qidx >> 1, strand = qidx & 1; position.pos is where the searched string lies (strand 1: the
+// leftmost position of the reverse complement).  pair = true: the best stratum per read — once either strand is found, neither goes on.  Strands::dna5() is the
+// complement of the ranks $ A C G T.  bothStrands(seqs, complement) is the same doubled batch on the host: a symbol c < complement.size() becomes complement[c], any
+// other stays as it is.
+struct Strands {
+    std::vector<uint8_t> complement;
+    bool pair{false};
+    static auto dna5(bool pair = false) -> Strands { return Strands{{0, 4, 3, 2, 1}, pair}; }
+    auto c() const -> fmgpu_strands { return fmgpu_strands{complement.data(), static_cast<int32_t>(complement.size()), pair ? 1 : 0}; }
+};
+template <typename Queries>
+auto bothStrands(Queries const& seqs, std::vector<uint8_t> const& complement) -> std::vector<std::vector<uint8_t>> {
+    std::vector<std::vector<uint8_t>> out;
+    for (auto const& s : seqs) {
+        auto& fwd = out.emplace_back();
+        for (auto c : s) fwd.push_back(static_cast<uint8_t>(c));
+        std::vector<uint8_t> rev(fwd.rbegin(), fwd.rend());
+        for (auto& c : rev) if (c < complement.size()) c = complement[c];
+        out.push_back(std::move(rev));
+    }
+    return out;
+}
+template <typename Index, typename Queries>
+auto map(Index const& index, Queries const& queries, MapQuery const& query, Strands const& strands) -> MapResult {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(queries, buf, off);
+    size_t nq = off.size() - 1;
+    detail::FlatMapQuery flat{query};
+    fmgpu_strands st = strands.c();
+    return detail::run_map(2 * nq, query.locate, [&](fmgpu_position* out, uint64_t cap, uint64_t* count, fmgpu_hit* hits, uint64_t hcap, uint64_t* hcount, uint8_t* stratum) {
+        return fmgpu_map_strands(index.handle, buf.data(), off.data(), nq, &flat.what, &st, out, cap, count, hits, hcap, hcount, stratum, nullptr, nullptr, nullptr);
+    });
+}
 template <typename Index>
 auto map(Index const& index, PackedQueries const& queries, MapQuery const& query) -> MapResult {
     size_t nq = queries.size();
@@ -1332,6 +1385,18 @@ struct Feed {
             return fmgpu_feed_map_v(handle, reads.data(), lens.data(), nq, &flat.what, out, cap, count, hits, hcap, hcount, stratum, nullptr, nullptr);
         });
     }
+    // both strands chunk by chunk (fmgpu_feed_map_strands; the batch is flattened: there is no `_v` form): what fmc::map(index, queries, query, strands) returns
+    template <typename Queries>
+    auto map(Queries const& queries, MapQuery const& query, Strands const& strands) const -> MapResult {
+        std::vector<uint8_t> buf; std::vector<uint64_t> off;
+        detail::flatten(queries, buf, off);
+        size_t nq = off.size() - 1;
+        detail::FlatMapQuery flat{query};
+        fmgpu_strands st = strands.c();
+        return detail::run_map(2 * nq, query.locate, [&](fmgpu_position* out, uint64_t cap, uint64_t* count, fmgpu_hit* hits, uint64_t hcap, uint64_t* hcount, uint8_t* stratum) {
+            return fmgpu_feed_map_strands(handle, buf.data(), off.data(), nq, &flat.what, &st, out, cap, count, hits, hcap, hcount, stratum, nullptr, nullptr);
+        });
+    }
     // The bytes of a read file to positions (fmgpu_feed_map_text): what fmc::map(index, parseQueries(text, format, table), query) returns plus the name and quality
     // spans and the length of every read, without the batch ever visiting the host: the text travels in windows of chunkBytes (0 = 64 MiB), each parsed and mapped
     // on the device.  final = false: only the records the text proves complete; `consumed` tells where the next call starts.  A text error throws, naming the line.
@@ -1356,24 +1421,39 @@ struct Feed {
         auto data() const -> uint8_t const* { return first; }
         auto size() const -> size_t { return count; }
     };
-    auto mapText(ByteView text, TextFormat format, SymbolTable const& table, MapQuery const& query, bool final = true, uint64_t chunkBytes = 0) const -> TextResult {
+    // both strands of every read of the file (fmgpu_feed_map_text_strands): stratum holds two entries per read, names / quals / lens stay per read of the file
+    auto mapText(std::string_view text, TextFormat format, SymbolTable const& table, MapQuery const& query, Strands const& strands, bool final = true,
+                 uint64_t chunkBytes = 0) const -> TextResult {
+        return mapText(ByteView{reinterpret_cast<uint8_t const*>(text.data()), text.size()}, format, table, query, final, chunkBytes, &strands);
+    }
+    auto mapText(ByteView text, TextFormat format, SymbolTable const& table, MapQuery const& query, Strands const& strands, bool final = true,
+                 uint64_t chunkBytes = 0) const -> TextResult {
+        return mapText(text, format, table, query, final, chunkBytes, &strands);
+    }
+    auto mapText(ByteView text, TextFormat format, SymbolTable const& table, MapQuery const& query, bool final = true, uint64_t chunkBytes = 0,
+                 Strands const* strands = nullptr) const -> TextResult {
         detail::FlatMapQuery flat{query};
+        fmgpu_strands st = strands ? strands->c() : fmgpu_strands{};
+        const uint64_t mult = strands ? 2 : 1;
         TextResult r;
         uint64_t rcap = std::max<uint64_t>(1024, text.size() / 64), cap = query.locate ? std::max<uint64_t>(4 * rcap, text.size() / 16) : 0;
         uint64_t hcap = std::max<uint64_t>(4 * rcap, text.size() / 16), count = 0, hcount = 0;
         fmgpu_parse_result res{};
         for (int round = 0; round < 2; ++round) {                     // the counts are exact also on FMGPU_ERR_CAPACITY, so a second call with them fits
             r.positions.resize(cap); r.hits.resize(hcap);
-            r.stratum.assign(rcap, 255); r.names.resize(rcap); r.quals.resize(rcap); r.lens.resize(rcap);
-            int rc = fmgpu_feed_map_text(handle, text.data(), text.size(), static_cast<int32_t>(format), final ? 1 : 0, table.map.data(), chunkBytes, &flat.what,
-                                         r.positions.data(), cap, &count, r.hits.data(), hcap, &hcount, r.stratum.data(), r.names.data(), r.quals.data(), r.lens.data(), rcap,
-                                         &res, nullptr, nullptr);
+            r.stratum.assign(mult * rcap, 255); r.names.resize(rcap); r.quals.resize(rcap); r.lens.resize(rcap);
+            int rc = strands ? fmgpu_feed_map_text_strands(handle, text.data(), text.size(), static_cast<int32_t>(format), final ? 1 : 0, table.map.data(), chunkBytes, &flat.what,
+                                                           &st, r.positions.data(), cap, &count, r.hits.data(), hcap, &hcount, r.stratum.data(), r.names.data(), r.quals.data(),
+                                                           r.lens.data(), rcap, &res, nullptr, nullptr)
+                             : fmgpu_feed_map_text(handle, text.data(), text.size(), static_cast<int32_t>(format), final ? 1 : 0, table.map.data(), chunkBytes, &flat.what,
+                                                   r.positions.data(), cap, &count, r.hits.data(), hcap, &hcount, r.stratum.data(), r.names.data(), r.quals.data(), r.lens.data(), rcap,
+                                                   &res, nullptr, nullptr);
             if (rc == FMGPU_ERR_CAPACITY && round == 0) { cap = std::max(cap, count); hcap = std::max(hcap, hcount); rcap = std::max<uint64_t>(rcap, res.reads); continue; }
             detail::check(rc);
             break;
         }
         r.positions.resize(count); r.hits.resize(hcount);
-        r.stratum.resize(res.reads); r.names.resize(res.reads); r.quals.resize(res.reads); r.lens.resize(res.reads);
+        r.stratum.resize(mult * res.reads); r.names.resize(res.reads); r.quals.resize(res.reads); r.lens.resize(res.reads);
         r.symbols = res.symbols; r.consumed = res.consumed; r.foreign = res.foreign;
         return r;
     }

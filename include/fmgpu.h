@@ -842,7 +842,7 @@ int fmgpu_queries_parse(const uint8_t* text, uint64_t bytes, int32_t format, int
  *   - Text, parse scratch, batch, records and spans live in the slots and only ever grow (fmgpu_feed_info counts them): in steady state a piece allocates nothing.
  *     DESIGN.md §4.15 lists the bytes per slot.  The feed's three streams are used and no more; each piece's parse reads two
  *     words back (the compute stream is synchronised, as the search behind it does anyway).  One call at a time per feed.
- *   - Not built: gzip input, multi-line FASTQ, both-strand batches, `_q4` slots, text through the plain search calls (locate = 0 returns ordered hit records),
+ *   - Not built: gzip input, multi-line FASTQ, `_q4` slots (both strands: fmgpu_feed_map_text_strands below), text through the plain search calls (locate = 0 returns ordered hit records),
  *     overlap of one piece's search with the next piece's parse (one compute stream). */
 int fmgpu_feed_map_text(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final,
                         const uint8_t* symbol_of, uint64_t chunk_bytes, const fmgpu_map_query* what,
@@ -851,6 +851,77 @@ int fmgpu_feed_map_text(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int
                         uint8_t* out_stratum, fmgpu_text_span* out_names, fmgpu_text_span* out_quals, uint64_t* out_lens,
                         uint64_t read_capacity, fmgpu_parse_result* result,
                         fmgpu_stats* search_stats, fmgpu_stats* locate_stats);
+
+/* ---- both strands: the reverse complements made on the device, and the best stratum per read -----------------------------------------------------
+ * A DNA read mapper searches a read and its reverse complement.  These calls make the second strand on the device, so that only the forward strand crosses the
+ * bus, and teach the best-stratum ladder that two reads are the strands of one: once either strand is found, neither goes on.
+ * fmgpu_queries_strands: the doubled batch D of a byte batch, in the interleaved numbering fmgpu_queries_pack4 uses with a complement table: read 2q of D is read q,
+ * read 2q + 1 is read q reversed and complemented.
+ *   - complement: host memory, n entries, n in 1 .. 256.  A byte c < n becomes complement[c]; a byte >= n stays as it is (255 stays 255; fmgpu_queries_pack4 writes
+ *     15 instead).  The forward strand is copied as it is.
+ *   - out_qoff: 2 nq + 1 entries, closed-form: out_qoff[2q] = 2 (qoff[q] - qoff[0]), out_qoff[2q + 1] = out_qoff[2q] + (qoff[q + 1] - qoff[q]); out_qoff[0] = 0 and
+ *     qoff[0] need not be 0.  out_qbuf: 2 (qoff[nq] - qoff[0]) bytes.
+ *   - Every buffer but `complement` may be host or device memory (host buffers are staged).  One streaming pass: a thread makes 16 output bytes from aligned 16-byte
+ *     loads, reversed in registers for strand 1, and stores them as one aligned 16-byte piece (a device out_qbuf that is not 16-byte aligned is written byte by
+ *     byte).  The offsets are checked on the device and read back once before the symbols are touched; the call returns after completion.
+ *   - Errors: FMGPU_ERR_INVALID for n outside 1 .. 256, a null pointer while nq > 0, a decreasing qoff; FMGPU_ERR_UNSUPPORTED for nq > 2^30 - 1 (D stays inside the
+ *     ladder's 2^31 - 1 reads and the 2^31 - 2 of fmgpu_hits_from_intervals).  n and nq are checked before the first use of the device.  nq == 0 returns 0 and
+ *     writes out_qoff[0] = 0 if out_qoff is given.
+ * fmgpu_search_best_pairs / fmgpu_search_best_ng21_pairs: fmgpu_search_best / _ng21 over a batch whose reads 2j and 2j + 1 are a pair (the two strands of D).
+ *   - nq must be even (FMGPU_ERR_INVALID, checked with n_schemes before anything else).  Stratum i is the single-scheme call over the reads of the pairs still
+ *     unfound, in batch order.  A pair is found in stratum i if either of its reads produced a record with len > 0 there; both reads of a found pair leave the ladder.
+ *   - out_stratum (nq entries): BOTH entries of a found pair carry its stratum, an unfound pair's entries are 255; the records tell which strand has hits.
+ *   - Records, their order, max_hits_per_query (per read of the batch, that is per strand), the capacity rule, stats, error codes and the one read-back per stratum
+ *     are those of fmgpu_search_best.  An empty read, or an ng21 read shorter than the scheme, finds nothing; its pair is found through the other read only.
+ *   - The records are a sub-multiset of fmgpu_search_best's on the same batch: a strand that the independent ladder would search again in a later stratum is not.
+ * fmgpu_map_strands: fmgpu_map over both strands.  Let D = fmgpu_queries_strands(batch, strands->complement, strands->n).
+ *   - pair == 0: every output equals, element for element, what fmgpu_map returns for D.  pair == 1: the same with fmgpu_search_best_pairs / _ng21_pairs in place of
+ *     the ladder.  Kind FMGPU_MAP_EXACT has no ladder: pair is accepted and changes nothing.
+ *   - qidx in H and P counts in D: read = qidx >> 1, strand = qidx & 1.  out_stratum has 2 nq entries.  pos is where the searched string lies on the indexed text: for
+ *     strand 1 the leftmost position of the reverse complement (what a SAM record with flag 16 holds); nothing is converted.
+ *   - Only the forward strand is staged; D is made in the call's scratch (2 x symbols + 16 bytes, 16 nq + 24 bytes of offsets).
+ *   - Errors, in this order: what fmgpu_map checks first in `what`; FMGPU_ERR_INVALID for a null strands or complement, n outside 1 .. 256, pair outside 0 .. 1;
+ *     nq == 0 returns 0 with zero counts before the handle is looked at; nq > 2^30 - 1 is FMGPU_ERR_UNSUPPORTED; then the schemes, the handle and the null pointers
+ *     with the codes and messages of fmgpu_map.
+ * fmgpu_feed_map_strands / fmgpu_feed_map_text_strands: fmgpu_feed_map / fmgpu_feed_map_text with the same `strands`.
+ *   - Per chunk or piece, on the compute stream: the upload of the forward reads or of the text and the parse are unchanged; then the doubled batch is made in the
+ *     slot's own buffers (they only ever grow; fmgpu_feed_info counts them), the chain runs on 2 x reads, and the records are rebased by 2 x the chunk's first read.
+ *   - Results equal fmgpu_map_strands on the flattened batch (for text: on the whole-text parse), for every chunk and window size: chunks are runs of consecutive
+ *     reads, so a pair never straddles one.
+ *   - chunk_reads / chunk_symbols count forward reads.  out_stratum, where given, holds 2 x nq entries (text: 2 x read_capacity); out_names / out_quals / out_lens stay
+ *     per read of the file.  last_uploaded_bytes stays the forward bytes (and offsets) or the text bytes: the second strand never crosses the bus.
+ *   - Host memory only, the feed's three streams and no more; errors and capacity behaviour are those of the calls they extend, the strands checks behind `what`'s.
+ * Not built: `_v` and `_q4` forms of the strands calls, `_q4` forms of the pair ladder, strands over replicas, strands for fmgpu_search_hamming_sm. */
+typedef struct fmgpu_strands {
+    const uint8_t* complement;   /* host memory, n entries */
+    int32_t n;                   /* 1 .. 256 */
+    int32_t pair;                /* 0: the strands are independent reads; 1: best stratum per read (the pair ladder) */
+} fmgpu_strands;                 /* 16 bytes */
+int fmgpu_queries_strands(const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, const uint8_t* complement, int32_t n,
+                          uint8_t* out_qbuf, uint64_t* out_qoff, void* stream);
+int fmgpu_search_best_pairs(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                            const fmgpu_scheme* schemes, int32_t n_schemes, uint64_t max_hits_per_query,
+                            fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, fmgpu_stats* stats, void* stream);
+int fmgpu_search_best_ng21_pairs(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                                 const fmgpu_expanded_scheme* schemes, int32_t n_schemes, uint64_t max_hits_per_query,
+                                 fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, uint8_t* out_stratum, fmgpu_stats* stats, void* stream);
+int fmgpu_map_strands(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                      const fmgpu_map_query* what, const fmgpu_strands* strands,
+                      fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                      fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                      uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats, void* stream);
+int fmgpu_feed_map_strands(fmgpu_feed_t f, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq,
+                           const fmgpu_map_query* what, const fmgpu_strands* strands,
+                           fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                           fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                           uint8_t* out_stratum, fmgpu_stats* search_stats, fmgpu_stats* locate_stats);
+int fmgpu_feed_map_text_strands(fmgpu_feed_t f, const uint8_t* text, uint64_t bytes, int32_t format, int32_t final,
+                                const uint8_t* symbol_of, uint64_t chunk_bytes, const fmgpu_map_query* what, const fmgpu_strands* strands,
+                                fmgpu_position* out, uint64_t capacity, uint64_t* out_count,
+                                fmgpu_hit* out_hits, uint64_t hits_capacity, uint64_t* out_hit_count,
+                                uint8_t* out_stratum, fmgpu_text_span* out_names, fmgpu_text_span* out_quals, uint64_t* out_lens,
+                                uint64_t read_capacity, fmgpu_parse_result* result,
+                                fmgpu_stats* search_stats, fmgpu_stats* locate_stats);
 
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
