@@ -20,7 +20,7 @@ from . import search_scheme  # noqa: F401
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer",
-           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
+           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
 
 
 class _Options:
@@ -1546,3 +1546,67 @@ def parse_stream(fileobj, format, table, chunk_bytes=64 << 20, max_chunk_bytes=1
     finally:
         buf = None
         pinned.free()
+
+
+# ---- positions to text lines on the device (fmgpu_positions_format)
+def pack_names(names):
+    """a list of bytes / str -> (data uint8[total], spans TEXT_SPAN_DTYPE[len(names)]): the names back to back, the shape of a name table of format_positions"""
+    raw = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in names]
+    spans = np.zeros(len(raw), dtype=TEXT_SPAN_DTYPE)
+    lens = np.fromiter((len(n) for n in raw), dtype=np.uint64, count=len(raw))
+    spans["len"] = lens
+    if len(raw):
+        spans["offset"][1:] = np.cumsum(lens)[:-1]
+    return np.frombuffer(b"".join(raw), dtype=np.uint8), spans
+
+
+def _name_table(names):
+    """(capi.NameTable, keep-alive) of a (data, spans) pair — data as parse_queries takes it, spans a TEXT_SPAN_DTYPE array or a device buffer — or of a list of names"""
+    if not (isinstance(names, tuple) and len(names) == 2):
+        names = pack_names(names)
+    data, spans = names
+    p, nbytes, alive = _text_buffer(data)
+    if isinstance(spans, np.ndarray):
+        spans = np.ascontiguousarray(spans, dtype=TEXT_SPAN_DTYPE)
+    sp, sbytes = _buffer(spans)
+    table = capi.NameTable(p.value if nbytes else None, nbytes, sp.value if sbytes else None, sbytes // TEXT_SPAN_DTYPE.itemsize)
+    return table, (alive, spans)
+
+
+def format_positions(positions, columns=("qidx", "seq_id", "pos", "errors"), sep=" ", strands=False, name_stop=False, pos_add=0, read_names=None, seq_names=None,
+                     device=False, want_line_offsets=False, stream=None):
+    """fmgpu_positions_format: one text line per located position, made on the device.  positions: a POSITION_DTYPE array, or a DeviceBuffer / torch tensor of such
+    records (used in place).  columns: names from capi.COLUMNS (or their codes), at most eight; a decimal column is written without padding, `sep` (one byte) stands
+    between two columns and a newline ends the line; the default is the `qidx seq_id pos errors` line of the example.  strands=True reads qidx as the both-strand calls
+    number it: "read" and "read_name" use qidx >> 1, "strand" is '-' for an odd qidx.  read_names / seq_names: a (data, spans) pair — what parse_queries and
+    Feed.map_text return with want_names=True, with the text as data — or a list of bytes / str; name_stop ends a name at its first blank.  pos_add is added to pos.
+    Returns the text as bytes, or with device=True (DeviceBuffer, bytes); with want_line_offsets also the uint64 offsets of the lines (count + 1 entries)."""
+    if isinstance(positions, np.ndarray):
+        positions = np.ascontiguousarray(positions, dtype=POSITION_DTYPE)
+    pp, pbytes = _buffer(positions)
+    count = pbytes // POSITION_DTYPE.itemsize
+    cols = [capi.COLUMNS[c] if isinstance(c, str) else int(c) for c in columns]
+    if not 1 <= len(cols) <= 8:
+        raise ValueError("a line has 1 .. 8 columns")
+    sep = sep.encode("latin-1") if isinstance(sep, str) else bytes(sep)
+    if len(sep) != 1:
+        raise ValueError("sep is one byte")
+    spec = capi.FormatSpec(len(cols), (C.c_uint8 * 8)(*cols), sep[0], 1 if strands else 0, 1 if name_stop else 0, 0, int(pos_add) & UINT64_MAX, None, None)
+    keep = []
+    for field, names, code in (("read_names", read_names, capi.COL_READ_NAME), ("seq_names", seq_names, capi.COL_SEQ_NAME)):
+        if code in cols:
+            if names is None:
+                raise ValueError(f"a {field[:-1]} column needs {field}")
+            table, alive = _name_table(names)
+            keep.append((table, alive))
+            setattr(spec, field, C.pointer(table))
+    sp = None if stream is None else C.c_void_p(stream if isinstance(stream, int) else getattr(stream, "cuda_stream", 0))
+    L, nbytes = capi.lib(), C.c_uint64()
+    off = np.zeros(count + 1, dtype=np.uint64) if want_line_offsets else None
+    capi.check(L.fmgpu_positions_format(pp, count, C.byref(spec), None, 0, C.byref(nbytes), None, sp))       # the counting call sizes the text exactly
+    total = int(nbytes.value)
+    out = DeviceBuffer(max(total, 8)) if device else np.zeros(max(total, 1), dtype=np.uint8)
+    capi.check(L.fmgpu_positions_format(pp, count, C.byref(spec), capi.ptr(out), total, C.byref(nbytes), capi.ptr(off), sp))
+    del keep
+    res = (out, total) if device else out[:total].tobytes()
+    return (res, off) if want_line_offsets else res

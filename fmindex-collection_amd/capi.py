@@ -163,6 +163,23 @@ TEXT_LINES, TEXT_FASTA, TEXT_FASTQ = 0, 1, 2
 SYM_DROP, SYM_FOREIGN = 254, 255
 
 
+class NameTable(C.Structure):
+    """fmgpu_name_table: the names a READ_NAME / SEQ_NAME column of fmgpu_positions_format copies: bytes, and one span per row (each host or device memory)"""
+    _fields_ = [("bytes", C.c_void_p), ("n_bytes", C.c_uint64), ("spans", C.c_void_p), ("count", C.c_uint64)]
+
+
+class FormatSpec(C.Structure):
+    """fmgpu_format_spec: the columns of a line of fmgpu_positions_format and how they are written (host memory)"""
+    _fields_ = [("n_cols", C.c_int32), ("cols", C.c_uint8 * 8), ("sep", C.c_uint8), ("strand_shift", C.c_uint8), ("name_stop", C.c_uint8), ("reserved", C.c_uint8),
+                ("pos_add", C.c_uint64), ("read_names", C.POINTER(NameTable)), ("seq_names", C.POINTER(NameTable))]
+
+
+assert C.sizeof(NameTable) == 32 and C.sizeof(FormatSpec) == 40
+COL_QIDX, COL_SEQ_ID, COL_POS, COL_ERRORS, COL_HIT, COL_READ, COL_STRAND, COL_READ_NAME, COL_SEQ_NAME = range(9)
+COLUMNS = {"qidx": COL_QIDX, "seq_id": COL_SEQ_ID, "pos": COL_POS, "errors": COL_ERRORS, "hit": COL_HIT, "read": COL_READ, "strand": COL_STRAND,
+           "read_name": COL_READ_NAME, "seq_name": COL_SEQ_NAME}
+
+
 # every symbol include/fmgpu.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "fmgpu_abi_version", "fmgpu_last_error", "fmgpu_device_count", "fmgpu_set_device",
@@ -185,6 +202,7 @@ EXPORTS = [
     "fmgpu_map", "fmgpu_map_q4", "fmgpu_hits_from_intervals", "fmgpu_feed_map", "fmgpu_feed_map_v",
     "fmgpu_queries_parse", "fmgpu_feed_map_text",
     "fmgpu_queries_strands", "fmgpu_search_best_pairs", "fmgpu_search_best_ng21_pairs", "fmgpu_map_strands", "fmgpu_feed_map_strands", "fmgpu_feed_map_text_strands",
+    "fmgpu_positions_format",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -343,6 +361,8 @@ def lib():
         L.fmgpu_map_strands.argtypes = L.fmgpu_map.argtypes[:5] + [C.POINTER(Strands)] + L.fmgpu_map.argtypes[5:]
         L.fmgpu_feed_map_strands.argtypes = L.fmgpu_map_strands.argtypes[:-1]
         L.fmgpu_feed_map_text_strands.argtypes = L.fmgpu_feed_map_text.argtypes[:8] + [C.POINTER(Strands)] + L.fmgpu_feed_map_text.argtypes[8:]
+    if hasattr(L, "fmgpu_positions_format"):                  # (FMGPU_LIBRARY may name an older build of the same ABI)
+        L.fmgpu_positions_format.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(FormatSpec), C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

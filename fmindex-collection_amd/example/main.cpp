@@ -23,6 +23,9 @@
 //     strands is found (fmgpu_map_strands with pair = 1 through fmc::map / fmc::Feed::map with an fmc::Strands).  queryId in --save_output then counts read by read,
 //     2 * read + strand, instead of the forward reads followed by the reverse complements.  With --feed --device-parse (no trimming, no read limit, not ng21) the
 //     bytes of the query file go through fmgpu_feed_map_text_strands.
+//   * --device-format (not in the reference; --mode map): the --save_output file is formatted on the device (fmgpu_positions_format through fmc::formatPositions) instead
+//     of by the fprintf loop.  The file is the same, byte for byte.  fmc::map returns host vectors, so the records are staged up again for it: this flag proves that
+//     the two writers agree, not that one is faster (tools/format_probe.py measures that on records that are resident on the device).
 //   * --device-parse (not in the reference): the --query file is read as bytes and parsed on the device (fmgpu_queries_parse through fmc::parseQueries); its first byte
 //     chooses FASTA ('>') or FASTQ ('@', read only this way).  On a well-formed FASTA — ends in a newline, no '>' inside sequence lines, no '\r' — the output is the
 //     same, byte for byte.  Elsewhere the device rules differ from the reader below: a '\r' in front of a newline belongs to the line end (the reader takes it for
@@ -58,7 +61,7 @@ struct Options {
     bool schemeDyn = false;
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false;
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -102,6 +105,7 @@ FlagRule const kFlags[] = {
     {"--feed", false, [](Options& o, char const*) { o.feed = true; }},
     {"--device-parse", false, [](Options& o, char const*) { o.deviceParse = true; }},
     {"--pair-strands", false, [](Options& o, char const*) { o.pairStrands = true; }},
+    {"--device-format", false, [](Options& o, char const*) { o.deviceFormat = true; }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
     {"--ext", true, [](Options&, char const*) {}},
     {"--threads", true, [](Options&, char const*) {}},
@@ -385,8 +389,15 @@ struct Run {
         if (config.outputFile.empty()) return;
         auto* out = std::fopen(config.outputFile.c_str(), "w");
         if (!out) throw std::runtime_error("cannot write " + config.outputFile);
-        for (auto const& p : mapped.positions)
-            std::fprintf(out, "%zu %zu %zu %zu\n", static_cast<size_t>(p.qidx), static_cast<size_t>(static_cast<uint32_t>(p.seq_id)), static_cast<size_t>(p.pos), static_cast<size_t>(p.errors));
+        if (config.deviceFormat) {                                      // the same lines made on the device (the default FormatSpec: qidx seq_id pos errors)
+            auto records = mapped.positions;
+            for (auto& p : records) p.seq_id = static_cast<uint32_t>(p.seq_id);       // (what the loop below prints of it)
+            auto const text = fmc::formatPositions(records);
+            if (std::fwrite(text.data(), 1, text.size(), out) != text.size()) { std::fclose(out); throw std::runtime_error("cannot write " + config.outputFile); }
+        } else {
+            for (auto const& p : mapped.positions)
+                std::fprintf(out, "%zu %zu %zu %zu\n", static_cast<size_t>(p.qidx), static_cast<size_t>(static_cast<uint32_t>(p.seq_id)), static_cast<size_t>(p.pos), static_cast<size_t>(p.errors));
+        }
         std::fclose(out);
     }
 
@@ -443,11 +454,13 @@ int main(int argc, char const* const* argv) try {
                     "                 a last line without a newline keeps its last base, a name line at the end of the file is an empty read)\\\n"
                     "          --pair-strands (--mode map: reverse complements made on the device, best stratum per read: once either strand of a\\\n"
                     "                 read is found, neither is searched with more errors; queryId = 2 * read + strand)\\\n"
+                    "          --device-format (--mode map: the --save_output file is formatted on the device; the same file, byte for byte)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }
     bool const needsFirstLength = std::any_of(config.algorithms.begin(), config.algorithms.end(), [](auto const& a) { return algorithmByName(a) == Algorithm::ng21; });
     if (config.pairStrands && (config.hitMode != HitMode::map || config.packed)) throw std::runtime_error("--pair-strands needs --mode map and byte reads (no --packed)");
+    if (config.deviceFormat && config.hitMode != HitMode::map) throw std::runtime_error("--device-format needs --mode map");
     if (config.hitMode == HitMode::map && config.feed && config.deviceParse && (!config.withReverseComplement || config.pairStrands) && !config.packed && config.readLimit == 0 &&
         config.trimTo == 0 && !needsFirstLength && !config.readsFasta.empty() && std::filesystem::exists(config.readsFasta)) {
         std::ifstream in{config.readsFasta, std::ios::binary};

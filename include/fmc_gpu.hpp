@@ -1310,6 +1310,49 @@ auto map(Index const& index, PackedQueries const& queries, MapQuery const& query
     });
 }
 
+// Positions as text (include/fmgpu.h: fmgpu_positions_format): fmc::formatPositions(positions, spec[, readNames, seqNames]) is one line per located position, formatted
+// on the device.  The default FormatSpec writes `qidx seq_id pos errors`, the line the reference's example prints per hit.  strands = true reads qidx as fmc::map with
+// Strands numbers it (Column::Read and Column::ReadName use qidx >> 1, Column::Strand is '-' for an odd qidx); nameStop ends a name in front of its first blank; posAdd
+// is added to pos.  A NameTable is the names back to back plus one span per row: built from strings, or from the bytes and spans a parse returned.
+struct FormatSpec {
+    enum class Column : uint8_t { Qidx = FMGPU_COL_QIDX, SeqId = FMGPU_COL_SEQ_ID, Pos = FMGPU_COL_POS, Errors = FMGPU_COL_ERRORS, Hit = FMGPU_COL_HIT,
+                                  Read = FMGPU_COL_READ, Strand = FMGPU_COL_STRAND, ReadName = FMGPU_COL_READ_NAME, SeqName = FMGPU_COL_SEQ_NAME };
+    std::vector<Column> columns{Column::Qidx, Column::SeqId, Column::Pos, Column::Errors};
+    char     sep{' '};
+    bool     strands{false};
+    bool     nameStop{false};
+    uint64_t posAdd{0};
+};
+struct NameTable {
+    std::vector<uint8_t>         bytes;
+    std::vector<fmgpu_text_span> spans;
+    NameTable() = default;
+    explicit NameTable(std::vector<std::string> const& names) {
+        for (auto const& n : names) {
+            spans.push_back(fmgpu_text_span{bytes.size(), n.size()});
+            bytes.insert(bytes.end(), n.begin(), n.end());
+        }
+    }
+    NameTable(std::string_view text, std::vector<fmgpu_text_span> spans_) : bytes(text.begin(), text.end()), spans(std::move(spans_)) {}
+    auto c() const -> fmgpu_name_table { return fmgpu_name_table{bytes.empty() ? nullptr : bytes.data(), bytes.size(), spans.empty() ? nullptr : spans.data(), spans.size()}; }
+};
+inline auto formatPositions(std::vector<fmgpu_position> const& positions, FormatSpec const& spec = {}, NameTable const* readNames = nullptr,
+                            NameTable const* seqNames = nullptr) -> std::string {
+    if (spec.columns.empty() || spec.columns.size() > 8) throw std::runtime_error("fmindex-collection (gpu): a line has 1 .. 8 columns");
+    fmgpu_format_spec s{};
+    s.n_cols = static_cast<int32_t>(spec.columns.size());
+    for (size_t c = 0; c < spec.columns.size(); ++c) s.cols[c] = static_cast<uint8_t>(spec.columns[c]);
+    s.sep = static_cast<uint8_t>(spec.sep); s.strand_shift = spec.strands ? 1 : 0; s.name_stop = spec.nameStop ? 1 : 0; s.pos_add = spec.posAdd;
+    fmgpu_name_table rt{}, qt{};
+    if (readNames) { rt = readNames->c(); s.read_names = &rt; }
+    if (seqNames) { qt = seqNames->c(); s.seq_names = &qt; }
+    uint64_t bytes = 0;
+    detail::check(fmgpu_positions_format(positions.data(), positions.size(), &s, nullptr, 0, &bytes, nullptr, nullptr));      // the counting call sizes the text exactly
+    std::string text(bytes, '\0');
+    if (bytes) detail::check(fmgpu_positions_format(positions.data(), positions.size(), &s, reinterpret_cast<uint8_t*>(text.data()), bytes, &bytes, nullptr, nullptr));
+    return text;
+}
+
 // A feed (include/fmgpu.h: fmgpu_feed_*): host batches searched chunk by chunk on one index, upload, search and download overlapped.  What a caller that holds its
 // queries in host memory — the reference's Sequences — should search through: `fmc::Feed feed{index}; feed.search_no_errors(queries, delegate);`.  A Sequences object
 // (reads of one-byte symbols, each contiguous) goes down through the `_v` calls without being flattened, a PackedQueries through `_q4`.  The delegates are called as by

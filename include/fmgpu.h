@@ -923,6 +923,59 @@ int fmgpu_feed_map_text_strands(fmgpu_feed_t f, const uint8_t* text, uint64_t by
                                 uint64_t read_capacity, fmgpu_parse_result* result,
                                 fmgpu_stats* search_stats, fmgpu_stats* locate_stats);
 
+/* ---- positions to text: located hits formatted as lines on the device ---------------------------------------------------------------------------
+ * fmgpu_positions_format is the mirror image of fmgpu_queries_parse: fmgpu_position records in, text lines out, so that a run which writes a file moves the text
+ * (about 20 bytes per record, fewer than the record's 32) over the bus instead of the records, and no host loop formats them.
+ *   - Lines: record i becomes line i: its columns in the order of spec->cols, spec->sep between two columns, '\n' behind the last; the lines are concatenated in record
+ *     order.  Decimal columns have no sign, no padding and no leading zero; the value 0 is "0".  A column may appear more than once.  With cols = {0, 1, 2, 3}, sep = ' '
+ *     and pos_add = 0 the output is byte for byte what `fprintf(out, "%zu %zu %zu %zu\n", qidx, seq_id, pos, errors)` writes per record.
+ *   - Names: FMGPU_COL_READ_NAME copies the bytes of row (qidx >> strand_shift) of spec->read_names, FMGPU_COL_SEQ_NAME those of row seq_id of spec->seq_names (what
+ *     fmgpu_queries_parse / fmgpu_feed_map_text return as out_names, with the text as `bytes`).  name_stop = 1 ends a name in front of its first ' ' or '\t'.
+ *   - out_line_off: NULL, or count + 1 entries in host or device memory: out_line_off[i] = the byte offset of line i, out_line_off[count] = *out_bytes.  It is written
+ *     whenever the call gets past its checks, also on FMGPU_ERR_CAPACITY (the rule of out_match_len).
+ *   - *out_bytes = the exact size of the text, on success and on FMGPU_ERR_CAPACITY alike; if it exceeds `capacity` the call returns FMGPU_ERR_CAPACITY and writes nothing
+ *     to `out`.  out == NULL with capacity == 0 is the counting call: it returns 0 with *out_bytes (and out_line_off) and writes no text.
+ *   - count == 0 returns 0 with *out_bytes = 0 before anything else is looked at; a host out_line_off[0] is set to 0 (a device one by a memset).
+ *   - Before the first use of the device, FMGPU_ERR_INVALID, each with a message of its own, for: a null spec, positions or out_bytes; a null out while capacity > 0;
+ *     n_cols outside 1 .. 8; an unknown column code; strand_shift or name_stop outside 0 .. 1; reserved != 0; a name column whose table pointer is null, or whose table
+ *     has a null bytes with n_bytes > 0 or a null spans with count > 0.  2^32 - 256 records and more: FMGPU_ERR_UNSUPPORTED.
+ *   - On the device, in the pass that measures the lines: a name column whose row (read or seq_id) is >= its table's count, or a span with offset + len > n_bytes, returns
+ *     FMGPU_ERR_INVALID; nothing is written (out_line_off neither) and the message names the lowest offending record index.  A name span of 2^31 bytes or more, or a line
+ *     of 2^32 bytes or more, returns FMGPU_ERR_UNSUPPORTED in the same way (an FMGPU_ERR_INVALID record anywhere in the batch goes first).
+ *   - Every buffer (positions, out, out_line_off, and the bytes and spans of each table) may be host or device memory; host buffers are staged.  A device `out` needs no
+ *     alignment: the text leaves in 16-byte stores aligned to the output address, and only the first and last bytes of a workgroup's range are stored byte by byte.
+ *   - Three passes (measure, hipcub exclusive scan, write) and one read-back: the size of the text and the error words together.  The call returns after completion and
+ *     frees its scratch of 12 bytes per record (a 4-byte length, an 8-byte offset) plus the scan's own.
+ * Not built: SAM / PAF records as such, text per chunk inside fmgpu_map or the feeds, fmgpu_hit records or seed spans as text, compressed output, columns from a caller's arrays. */
+#define FMGPU_COL_QIDX      0   /* qidx, decimal */
+#define FMGPU_COL_SEQ_ID    1   /* seq_id, decimal */
+#define FMGPU_COL_POS       2   /* pos + spec->pos_add, decimal (wraps mod 2^64) */
+#define FMGPU_COL_ERRORS    3   /* errors, decimal */
+#define FMGPU_COL_HIT       4   /* hit, decimal */
+#define FMGPU_COL_READ      5   /* qidx >> strand_shift, decimal */
+#define FMGPU_COL_STRAND    6   /* one byte: '-' if strand_shift == 1 and (qidx & 1), else '+' */
+#define FMGPU_COL_READ_NAME 7   /* bytes of read_names row (qidx >> strand_shift) */
+#define FMGPU_COL_SEQ_NAME  8   /* bytes of seq_names row seq_id */
+typedef struct fmgpu_name_table {          /* 32 bytes; bytes and spans may each be host or device memory */
+    const uint8_t* bytes;
+    uint64_t n_bytes;
+    const fmgpu_text_span* spans;          /* span offsets are relative to `bytes` */
+    uint64_t count;
+} fmgpu_name_table;
+typedef struct fmgpu_format_spec {         /* 40 bytes, host memory */
+    int32_t n_cols;                        /* 1 .. 8 */
+    uint8_t cols[8];                       /* FMGPU_COL_*; a column may appear more than once */
+    uint8_t sep;                           /* the byte between two columns */
+    uint8_t strand_shift;                  /* 0: read = qidx; 1: read = qidx >> 1, strand = qidx & 1 (the numbering of the *_strands calls) */
+    uint8_t name_stop;                     /* 0: a name is its whole span; 1: it ends in front of its first ' ' or '\t' */
+    uint8_t reserved;                      /* 0 */
+    uint64_t pos_add;                      /* added to pos (1 = SAM's one-based positions) */
+    const fmgpu_name_table* read_names;    /* NULL unless a READ_NAME column is asked for */
+    const fmgpu_name_table* seq_names;     /* NULL unless a SEQ_NAME column is asked for */
+} fmgpu_format_spec;
+int fmgpu_positions_format(const fmgpu_position* positions, uint64_t count, const fmgpu_format_spec* spec,
+                           uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* out_line_off, void* stream);
+
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
 int fmgpu_free(void* ptr);
