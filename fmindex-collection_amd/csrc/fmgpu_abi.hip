@@ -237,10 +237,18 @@ int fmgpu_built_get(fmgpu_built_t b_, int32_t part, const void** ptr, uint64_t* 
     return 0;
 }
 
-int fmgpu_index_save(fmgpu_index_t h, const char* path, int32_t include_tables) { ROUTE(h, fmgpu_index_save(h, path, include_tables)); }
+static const char* const kNoFilesMsg = "index files: this development build keeps other super-blocks than the shipped library (SUPER_SHIFT), it neither writes nor reads index files";
+#ifdef FMGPU_DEV
+int fmgpu_dev_super_shift(void) { return (int)fmgpu32::kSuperShift; }      // (development builds only: log2 of the rows of a wide super-block, so that a test sees which library it holds)
+#endif
+int fmgpu_index_save(fmgpu_index_t h, const char* path, int32_t include_tables) {
+    if (fmgpu32::kDevSuperShift) return fail(FMGPU_ERR_UNSUPPORTED, kNoFilesMsg);
+    ROUTE(h, fmgpu_index_save(h, path, include_tables));
+}
 int fmgpu_index_load(const char* path, fmgpu_index_t* out) {
     if (!path || !out) return fail(FMGPU_ERR_INVALID, "path / out is null");
     *out = nullptr;
+    if (fmgpu32::kDevSuperShift) return fail(FMGPU_ERR_UNSUPPORTED, kNoFilesMsg);
     FILE* f = fopen(path, "rb");
     if (!f) return fail(FMGPU_ERR_INVALID, std::string("index file: cannot open ") + path);
     struct { char magic[8]; uint32_t version, abi, wide, endian_probe; uint64_t meta_bytes, meta_sum, reserved[3]; } fh;

@@ -305,7 +305,19 @@ constexpr bool kWide = FMGPU_WIDE != 0;
 // double walk {LF^2J row, code, code} 12 bytes.  64-bit rows: 16 bytes each — {lb, len} as two u64; {row lo, row hi, code, 0}; {row lo, row hi, code, code};
 // a walk that meets a delimiter has row = all ones.
 constexpr size_t kSlutEntryBytes = kWide ? 16 : 8, kWalkEntryBytes = kWide ? 16 : 8, kWalk2EntryBytes = kWide ? 16 : 12;
-constexpr uint32_t kSuperShift = 30;          // wide rows: counts are kept relative to super-blocks of 2^30 rows / node positions
+// wide rows: counts are kept relative to super-blocks of 2^kSuperShift rows / node positions — 2^30 in every shipped build.  A development build made with
+// SUPER_SHIFT=k (make DEV=1 SUPER_SHIFT=16: ../libfmgpu_dev_ss16.so) takes smaller ones, so that an index of 10^5 rows has several and the tests can stand on
+// their boundaries; it neither writes nor reads index files (its tables are not the shipped build's).
+#if defined(FMGPU_DEV) && defined(FMGPU_DEV_SUPER_SHIFT)
+constexpr uint32_t kSuperShift = FMGPU_DEV_SUPER_SHIFT;
+constexpr bool kDevSuperShift = true;
+#else
+constexpr uint32_t kSuperShift = 30;
+constexpr bool kDevSuperShift = false;
+#endif
+// lines of 128 rows (Format P) must not straddle a super-block and `kSuperShift - 7` is used as a shift; a block's count within its super-block is a u32 and
+// k_pair_counts_seg runs one through a whole super-block in 32 bits
+static_assert(kSuperShift >= 8 && kSuperShift <= 30, "wide super-blocks hold 2^8 .. 2^30 rows");
 constexpr idx_t kNoRow = ~(idx_t)0;
 
 enum Family : int { FAM_A = 0, FAM_EPR = 1, FAM_EPRV2 = 2, FAM_WAVELET = 3 };

@@ -701,6 +701,12 @@ void ora_all_ranks_and_prefix_ranks(const ora_string* s, uint64_t idx, uint64_t*
     }
 }
 
+/* the same for a list of rows: rs / prs are [nrows][sigma] (the edge tests probe 10^5 rows of a string) */
+void ora_all_ranks_rows(const ora_string* s, const uint64_t* rows, uint64_t nrows, uint64_t* rs, uint64_t* prs) {
+    for (uint64_t k = 0; k < nrows; ++k)
+        ora_all_ranks_and_prefix_ranks(s, rows[k], rs + k * (uint64_t)s->sigma, prs + k * (uint64_t)s->sigma);
+}
+
 /* =====================================================================================
  * sampled suffix array: SparseArray<tuple<u32,u32>, Bitvector2L<512,65536>>
  * ===================================================================================== */

@@ -58,6 +58,7 @@ uint64_t    ora_prefix_rank(const ora_string* s, uint64_t idx, uint64_t symb);
 uint64_t    ora_symbol(const ora_string* s, uint64_t idx);
 /* mathematically correct all_ranks_and_prefix_ranks (string/concepts.h:50-64), rs/prs hold sigma entries */
 void        ora_all_ranks_and_prefix_ranks(const ora_string* s, uint64_t idx, uint64_t* rs, uint64_t* prs);
+void        ora_all_ranks_rows(const ora_string* s, const uint64_t* rows, uint64_t nrows, uint64_t* rs, uint64_t* prs);
 /* raw arrays in the reference's in-memory layout.
  * blocked layouts: part 0 = blocks, part 1 = superBlocks ([k][sigma] u64)
  * wavelet:         part node*4 + {0: superblocks u64, 1: blocks u8, 2: bits u64, 3: totalLength u64}

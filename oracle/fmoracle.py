@@ -94,6 +94,7 @@ def lib():
         L.ora_symbol.restype = C.c_uint64
         L.ora_symbol.argtypes = [C.c_void_p, C.c_uint64]
         L.ora_all_ranks_and_prefix_ranks.argtypes = [C.c_void_p, C.c_uint64, u64p, u64p]
+        L.ora_all_ranks_rows.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p]
         L.ora_string_raw.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), u64p]
         L.ora_sparse_build.restype = C.POINTER(Sparse)
         L.ora_sparse_build.argtypes = [C.c_uint64, u8p, u64p, u64p]
@@ -251,6 +252,14 @@ class OraString(_StringBase):
         rs = np.zeros(self.sigma, dtype=np.uint64)
         prs = np.zeros(self.sigma, dtype=np.uint64)
         lib().ora_all_ranks_and_prefix_ranks(self.h, i, _p64(rs), _p64(prs))
+        return rs, prs
+
+    def all_ranks_rows(self, rows):
+        """all_ranks_and_prefix_ranks of every row of a list: two [len(rows), sigma] arrays"""
+        rows = as_u64(rows)
+        rs = np.zeros((len(rows), self.sigma), dtype=np.uint64)
+        prs = np.zeros((len(rows), self.sigma), dtype=np.uint64)
+        lib().ora_all_ranks_rows(self.h, _p64(rows), len(rows), _p64(rs), _p64(prs))
         return rs, prs
 
     def rank_table(self):
@@ -672,6 +681,12 @@ class RefString(_StringBase):
 
     def block_stride(self):
         return ref().fmref_string_block_stride(self.h)
+
+    def all_ranks_and_prefix_ranks(self, i):
+        rs = np.zeros(self.sigma, dtype=np.uint64)
+        prs = np.zeros(self.sigma, dtype=np.uint64)
+        ref().fmref_string_all_ranks_and_prefix_ranks(self.h, i, _p64(rs), _p64(prs))
+        return rs, prs
 
     def rank_table(self):
         n = self.size()

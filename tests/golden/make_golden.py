@@ -12,8 +12,10 @@
                          limitToHamming, isValid, isComplete, nodeCount, createUniformPartition).
   ref_strings_live.json  digests of what the real reference's occurrence-table types answer (block arrays, rank, prefix_rank,
                          symbol) on the seeded texts of test_strings_live_against_real_reference, every layout it builds.
+  ref_strings_live_edges.json  the same for the texts of test_strings_live_edges_against_real_reference: sizes around every layout's
+                         super-block period, alphabets of 4, 6, 21, 28 and 255 symbols, rows beside the boundaries and row n.
 
-    python tests/golden/make_golden.py [--tests-only | --live-strings]
+    python tests/golden/make_golden.py [--tests-only | --live-strings | --live-edges]
 """
 import json
 import os
@@ -357,6 +359,96 @@ def live_string_vectors():
     return out
 
 
+# ----------------------------------------------------------------------------------------------- super-block edges
+EDGE_SIGMAS = (4, 5, 6, 21, 28, 255)
+EDGE_WINDOW = 130
+
+
+def super_period(layout, sigma):
+    """rows after which the layout starts a new super-block (its counters of w bytes count inside one), or None where that is beyond 65 536 rows:
+    2^(8w) for the InterleavedBitvector / EPRV2 / EPRV3 families, whole blocks of 64 / bitct rows for InterleavedEPR, 65 536 for the top level of
+    EPRV4 / EPRV5 / InterleavedEPRV7 and the l0 rows of FlattenedBitvectors2L"""
+    if layout in ("EPRV4", "EPRV5", "IEPRV7") or layout.startswith("FBV_"):
+        return 65536
+    if layout == "WAVELET":
+        return None
+    w = int(re.search(r"(8|16|32)A?$", layout).group(1)) // 8      # bytes of a block counter
+    if w > 2:
+        return None
+    if layout in ("EPR8", "EPR16"):
+        rows = 64 // max(1, (sigma - 1).bit_length())
+        return (1 << (8 * w)) // rows * rows
+    return 1 << (8 * w)
+
+
+def inner_periods(layout):
+    """the rows at which a counter level below the super-block starts anew (EPRV4 / EPRV5 / InterleavedEPRV7: 256; FlattenedBitvectors2L: l1_bits)"""
+    if layout in ("EPRV4", "EPRV5", "IEPRV7"):
+        return (256,)
+    if layout.startswith("FBV_"):
+        return (int(layout.split("_")[1]),)
+    return ()
+
+
+def edge_sizes(layout, sigma):
+    """P - 1, P, P + 1 and 2 P + 300 rows around the layout's super-block period P; 8-bit counters also 65 536 + 300 rows (many super-blocks and the
+    65 536 rows of the device's own tables).  A layout without a period up to 65 536 rows (32-bit counters, Wavelet) takes P = 65 536"""
+    P = super_period(layout, sigma) or 65536
+    return [P - 1, P, P + 1, 2 * P + 300] + ([65536 + 300] if P <= 256 else [])
+
+
+def edge_text(sigma, n):
+    from tests.util import make_text
+    return make_text(n, sigma, seed=n + sigma, lo=0)
+
+
+def edge_rows(layout, sigma, n, window=EDGE_WINDOW):
+    """(rows, boundary): the probed rows of a string of n rows, ascending, and which of them lie within `window` of a multiple of the super-block period,
+    of 65 536 or of an inner level size, or are n - 1 or n (probed with every symbol); the others are every 509th row"""
+    i = np.arange(n + 1, dtype=np.int64)
+    near = i >= n - 1
+    for m in {super_period(layout, sigma) or 65536, 65536, *inner_periods(layout)}:
+        d = i % m
+        near |= (d <= window) | (d >= m - window)
+    keep = near | (i % 509 == 0)
+    return i[keep].astype(np.uint64), near[keep]
+
+
+def edge_string_cases(layout):
+    """the texts of test_strings_live_edges_against_real_reference, in its order: (sigma, n, text, rows probed, symbols probed one by one)"""
+    for sigma in EDGE_SIGMAS:
+        if sigma == 5:
+            continue                                             # (sigma = 5 has its boundary sizes in live_string_cases)
+        for n in edge_sizes(layout, sigma):
+            rows, _ = edge_rows(layout, sigma, n, window=3)
+            yield sigma, n, edge_text(sigma, n), [int(r) for r in rows], list(range(0, sigma, 1 if sigma <= 28 else 17)) + [sigma - 1] * (sigma > 28)
+
+
+def edge_digests(s, sigma, n, rows, symbols):
+    """rank and prefix_rank symbol by symbol, the ranks of all_ranks_and_prefix_ranks and symbol at the probed rows, as digests.  (The prefix ranks of the
+    reference's all_ranks_and_prefix_ranks are not its prefix_rank in the EPR and EPRV3 .. 7 families — InterleavedEPR leaves the super-block counts out of
+    them — so they are not pinned: the oracle returns prefix_rank there, test_long_text_crossing_255)"""
+    return {"rank": _digest(np.array([[s.rank(i, c) for c in symbols] for i in rows], dtype=np.uint64)),
+            "prefix_rank": _digest(np.array([[s.prefix_rank(i, c) for c in symbols] for i in rows], dtype=np.uint64)),
+            "all_ranks": _digest(np.array([s.all_ranks_and_prefix_ranks(i)[0] for i in rows], dtype=np.uint64)),
+            "symbol": _digest(np.array([s.symbol(i) for i in rows if i < n], dtype=np.uint64))}
+
+
+def live_edge_vectors():
+    """the answers of the reference headers compiled in place (oracle/_ref/libfmref.so) on the texts of edge_string_cases, for every layout it builds"""
+    import fmoracle as fo
+    if not fo.ref_available():
+        raise SystemExit("oracle/_ref/libfmref.so missing: run `make -C oracle ref` first")
+    out = {}
+    for layout in (l for l in fo.LAYOUTS if l not in fo.REF_UNBUILDABLE):
+        out[layout] = [{"sigma": sigma, "n": n, **edge_digests(fo.RefString(layout, sigma, text), sigma, n, rows, symbols)}
+                       for sigma, n, text, rows, symbols in edge_string_cases(layout)]
+    with open(os.path.join(HERE, "ref_strings_live_edges.json"), "w") as f:
+        json.dump({"_provenance": "produced by the real reference headers via oracle/_ref/libfmref.so (tests/golden/make_golden.py live_edge_vectors): "
+                                  "sha-256 (first 24 hex digits) of each answer array on the texts of edge_string_cases", "layouts": out}, f, separators=(",", ":"))
+    return out
+
+
 REF_SEARCH_CASES = {    # name: (layout, sigma, text symbols, text seed, reads, read length)
     "config0_ib16": ("IB16", 5, 1_000_000, 42, 10_000, 31),          # BASELINE.json configs[0]
     "protein_wavelet": ("WAVELET", 28, 300_000, 7, 3_000, 40),        # configs[4] in small: FMIndex<28, Wavelet>, 40 aa
@@ -406,8 +498,12 @@ def main():
     if "--live-strings" in sys.argv:                             # only ref_strings_live.json (needs oracle/_ref)
         live_string_vectors()
         return
+    if "--live-edges" in sys.argv:                               # only ref_strings_live_edges.json (needs oracle/_ref)
+        live_edge_vectors()
+        return
     ref_search_intervals()
     live_string_vectors()
+    live_edge_vectors()
     with open(os.path.join(HERE, "reference_tests.json"), "w") as f:
         json.dump(reference_tests(), f, separators=(",", ":"))
     strings, schemes = ref_vectors()

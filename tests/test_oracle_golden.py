@@ -9,13 +9,14 @@ import pytest
 
 import fmoracle as fo
 from tests.util import make_text, occurrences, sample_reads
-from tests.golden.make_golden import live_string_cases, string_digests
+from tests.golden.make_golden import live_string_cases, string_digests, edge_string_cases, edge_digests
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 REF = json.load(open(os.path.join(GOLD, "reference_tests.json")))
 REFSTR = json.load(open(os.path.join(GOLD, "ref_strings.json")))
 REFSCH = json.load(open(os.path.join(GOLD, "ref_schemes.json")))
 REFLIVE = json.load(open(os.path.join(GOLD, "ref_strings_live.json")))["layouts"]
+REFEDGES = json.load(open(os.path.join(GOLD, "ref_strings_live_edges.json")))["layouts"]
 
 ALL_LAYOUTS = list(fo.LAYOUTS)
 
@@ -99,7 +100,7 @@ def test_flattened_bitvectors_against_text_counts(layout):
     reference's String unit-test vectors above (hallo welt, 310 symbols) and by counting in the text, around the 512 / 2048 / 65 536
     block edges; its array layout is restated from the source text only (parity of the BYTES unpinned)."""
     rng = np.random.default_rng(7)
-    for sigma, n in ((5, 0), (5, 1), (5, 513), (5, 2048), (5, 66000), (28, 2100), (256, 700), (2, 130)):
+    for sigma, n in ((5, 0), (5, 1), (5, 513), (5, 2048), (5, 66000), (28, 2100), (256, 700), (2, 130), (28, 2 * 65536 + 300)):
         text = rng.integers(0, sigma, size=n, dtype=np.uint8)
         s = fo.OraString(layout, sigma, text)
         l1_bits = int(layout.split("_")[1]); bitct = max(1, (sigma - 1).bit_length())
@@ -107,7 +108,7 @@ def test_flattened_bitvectors_against_text_counts(layout):
         nsuper = n // 65536 + 1
         assert l0.size == nsuper * (sigma + 1) * 8 and l1.size == nsuper * (65536 // l1_bits) * (sigma + 1) * 2
         assert bits.size == nsuper * (65536 // l1_bits) * bitct * l1_bits // 8
-        for i in (list(range(n + 1)) if n <= 2100 else list(range(0, n + 1, 1021)) + [n, 65535, 65536, 65537]):
+        for i in (list(range(n + 1)) if n <= 2100 else list(range(0, n + 1, 1021)) + [n, 65535, 65536, 65537] + [131071, 131072, 131073] * (n > 131073)):
             for c in range(0, sigma, 1 if sigma <= 28 else 51):
                 assert s.rank(i, c) == naive_rank(text, i, c) and s.prefix_rank(i, c) == naive_prefix(text, i, c)
 
@@ -122,6 +123,19 @@ def test_strings_live_against_real_reference(layout):
     for w, (sigma, n, d) in zip(want, got):
         for k in ("blocks", "rank", "prefix_rank", "symbol"):
             assert d.get(k) == w.get(k), (layout, sigma, n, k)
+
+
+@pytest.mark.parametrize("layout", [l for l in ALL_LAYOUTS if l not in fo.REF_UNBUILDABLE])
+def test_strings_live_edges_against_real_reference(layout):
+    """the same comparison at the super-block boundaries of every layout and alphabets of 4, 6, 21, 28 and 255 symbols (ref_strings_live_edges.json): sizes P - 1,
+    P, P + 1 and 2 P + 300 around the layout's super-block period P, rows beside every boundary and row n — rank and prefix_rank symbol by symbol,
+    the ranks of all_ranks_and_prefix_ranks and symbol.  At n = k P the reference's own rank(n, .) counts the closed super-block twice: pinned as it is"""
+    want = REFEDGES[layout]
+    got = [(sigma, n, edge_digests(fo.OraString(layout, sigma, text), sigma, n, rows, symbols)) for sigma, n, text, rows, symbols in edge_string_cases(layout)]
+    assert [(w["sigma"], w["n"]) for w in want] == [(sigma, n) for sigma, n, _ in got]
+    for w, (sigma, n, d) in zip(want, got):
+        for k in ("rank", "prefix_rank", "all_ranks", "symbol"):
+            assert d[k] == w[k], (layout, sigma, n, k)
 
 
 # ------------------------------------------------------------------------------------------------ search schemes
