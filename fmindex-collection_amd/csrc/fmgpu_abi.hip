@@ -179,6 +179,14 @@ int handle_device(fmgpu_index_t h, int32_t* device) {
     *device = hd->device;
     return 0;
 }
+#if defined(FMGPU_DEV) && defined(FMGPU_DEV_SUPER_SHIFT)
+static std::atomic<uint64_t> g_flat_launch{0};
+static std::atomic<uint32_t> g_flat_launches{0};
+void dev_note_flat_launch(uint32_t lanes, uint32_t super_lds, uint32_t count_bits) {
+    g_flat_launch.store((uint64_t)lanes | ((uint64_t)count_bits << 16) | ((uint64_t)super_lds << 32));
+    ++g_flat_launches;
+}
+#endif
 }  // namespace fmgpu
 
 extern "C" {
@@ -240,6 +248,17 @@ int fmgpu_built_get(fmgpu_built_t b_, int32_t part, const void** ptr, uint64_t* 
 static const char* const kNoFilesMsg = "index files: this development build keeps other super-blocks than the shipped library (SUPER_SHIFT), it neither writes nor reads index files";
 #ifdef FMGPU_DEV
 int fmgpu_dev_super_shift(void) { return (int)fmgpu32::kSuperShift; }      // (development builds only: log2 of the rows of a wide super-block, so that a test sees which library it holds)
+#endif
+#if defined(FMGPU_DEV) && defined(FMGPU_DEV_SUPER_SHIFT)
+// (the development build with small super-blocks only) the last k_exact_s launch of the process: 0 where there was none; else *lanes = the lanes of its workgroups,
+// *super_lds = the entries of the super table it staged in LDS (0: read through L2), *count_bits = the width of the count fields it read; returns the launches so far
+int fmgpu_dev_flat_launch(uint32_t* lanes, uint32_t* super_lds, uint32_t* count_bits) {
+    const uint64_t v = g_flat_launch.load();
+    if (lanes) *lanes = (uint32_t)(v & 0xffffu);
+    if (count_bits) *count_bits = (uint32_t)(v >> 16) & 0xffffu;
+    if (super_lds) *super_lds = (uint32_t)(v >> 32);
+    return (int)g_flat_launches.load();
+}
 #endif
 int fmgpu_index_save(fmgpu_index_t h, const char* path, int32_t include_tables) {
     if (fmgpu32::kDevSuperShift) return fail(FMGPU_ERR_UNSUPPORTED, kNoFilesMsg);

@@ -147,6 +147,12 @@ inline const char* dev_env(const char* name) {
     (void)name; return nullptr;
 #endif
 }
+#if defined(FMGPU_DEV) && defined(FMGPU_DEV_SUPER_SHIFT)
+// (the development build with small super-blocks) what the last k_exact_s launch of the process took: the lanes of a workgroup and the entries of the super table
+// staged in LDS (0: read through L2).  The two instantiations and the two homes of the table compute the same intervals, so a test that forces one with
+// FMGPU_DEV_FLAT_LANES / FMGPU_DEV_FLAT_SUPER_MAX cannot see from the result that it ran: fmgpu_dev_flat_launch() (fmgpu_abi.hip) hands this out.
+void dev_note_flat_launch(uint32_t lanes, uint32_t super_lds, uint32_t count_bits);
+#endif
 // bits of FMGPU_OPT_KERNEL_SELECT (FMGPU_SEL_* in include/fmgpu.h); a DEV build ORs the non-selection bits of FMGPU_DEV_FLAGS in (kDevCountOnly, ...).
 // A search call reads them once, at its entry point, and passes the value down: a concurrent fmgpu_set_option cannot hand one call two configurations.
 constexpr int kDevCountOnly = 1 << 0;         // the one bit outside FMGPU_SEL_ALL that the launchers' word carries by name: the kernels count hits and write no records
@@ -776,7 +782,7 @@ struct DevString {
     // Format P (see the head of this file): pair lines of the bwt + the ascending list of the rows left out of them (u32, `pairs_nex` of them)
     uint8_t* pairs = nullptr; size_t pairs_bytes = 0; idx_t* pairs_ex = nullptr; uint32_t pairs_nex = 0;
     idx_t* pairs_super = nullptr; uint32_t pairs_nsb = 0;     // 64-bit rows: the line counts are relative to super-blocks of 2^30 rows, [pairs_nsb][16] holds the rest
-    // Format S (see the head of this file): one line per 64 rows of a Wavelet bwt with 6 <= sigma <= 29 + the counts at the start of every 2^24 rows ([flat_nsb][sigma], C folded in)
+    // Format S (see the head of this file): one line per 64 rows of a Wavelet bwt with 6 <= sigma <= 29 + the counts at the start of every 2^flat_count_bits(sigma) rows ([flat_nsb][sigma], C folded in)
     uint8_t* flat = nullptr; size_t flat_bytes = 0; idx_t* flat_super = nullptr; uint32_t flat_nsb = 0;
     void* shadow = nullptr; size_t shadow_bytes = 0;   // (shadow_bytes = blocks + super table)
     void* shadow_sup = nullptr; size_t shadow_sup_bytes = 0;
@@ -816,7 +822,17 @@ void drop_sample_chain(Index* x);
 // device_bytes itself; defined in fmgpu_index.hip
 int auto_shadow(Index* x, hipStream_t stream);
 // Format S: bits of a count inside a line (= log2 of the rows per super-block); 28 at most, so that a super-block's scan stays short
+#if defined(FMGPU_DEV) && defined(FMGPU_DEV_SUPER_SHIFT)
+// (the development build with small super-blocks takes Format S along: fields of min(shipped, SUPER_SHIFT) bits, so that 10^5 rows use a field to its top bit and
+// stand in several super-blocks.  The builder and k_exact_s take the width as an argument; both row widths' fmgpu_index / fmgpu_exact objects see this.)
+constexpr uint32_t flat_count_bits_shipped(uint32_t sigma) { return sigma == 0u ? 28u : ((704u / sigma) < 28u ? (704u / sigma) : 28u); }
+constexpr uint32_t flat_count_bits(uint32_t sigma) { return flat_count_bits_shipped(sigma) < kSuperShift ? flat_count_bits_shipped(sigma) : kSuperShift; }
+#else
 constexpr uint32_t flat_count_bits(uint32_t sigma) { return sigma == 0u ? 28u : ((704u / sigma) < 28u ? (704u / sigma) : 28u); }
+#endif
+// a line has 88 bytes = 704 bits behind its planes for sigma fields; a super-block holds at least 4 lines (k_flat_counts shifts by cbits - 6)
+constexpr bool flat_count_bits_fit() { for (uint32_t s = 6; s <= 29; ++s) if (flat_count_bits(s) < 8u || s * flat_count_bits(s) > 704u) return false; return true; }
+static_assert(flat_count_bits_fit(), "Format S: sigma fields of at least 8 bits in the 704 bits behind the planes, 6 <= sigma <= 29");
 // builds Format S beside the Wavelet bwt of an index with 6 <= sigma <= 29 (no-op where it does not apply; adds its bytes to device_bytes); defined in fmgpu_index.hip
 int build_flat_table(Index* x, hipStream_t stream);
 void free_string(DevString& s);

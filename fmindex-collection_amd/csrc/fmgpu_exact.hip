@@ -455,7 +455,7 @@ __global__ __launch_bounds__(256) void k_exact_chain(OccA<5> occ, ViewSA sa, con
 }
 
 // ---- exact search on Format S (fmgpu_common.h): ONE 128-byte line per LF step and interval end where the multi-ary wavelet tree of sigma = 28 takes two —
-// the five symbol planes of the line's 64 rows, the symbol's 24-bit count before the line and the super-block's count (a small table, LDS or L2).
+// the five symbol planes of the line's 64 rows, the symbol's count before the line (cbits = flat_count_bits(sigma) bits: 24 .. 28) and the super-block's count (a small table, LDS or L2).
 // The lines are fetched by the lanes of an OCTET together: a lane that reads 44 bytes of its own random line with four load instructions pays four address
 // translations and four passes through the texture path per line, and that — not the line fills — bounds the kernel (tools/membench.hip modes 8 / 9 / 4:
 // 33 / 47 / 44 G lines/s on a 3.1 GB table, 24 / 22 / 25 on a 4.2 GB one, where one load per line keeps 51).  Here instruction k of a round has the eight lanes of
@@ -1004,6 +1004,9 @@ static int search_exact(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qo
             return 0;
         };
         if ((rc = lanes == 256 ? launch(k_exact_s<256>) : launch(k_exact_s<512>))) return rc;
+#if defined(FMGPU_DEV) && defined(FMGPU_DEV_SUPER_SHIFT)
+        dev_note_flat_launch(lanes, super_lds, flat_count_bits((uint32_t)x->bwt.sigma));
+#endif
     } else if (x->bwt.search_family() == FAM_WAVELET) {
         uint32_t mx = shape_max, mn = 0;
         if (!have_shape && (rc = query_len_range((const uint64_t*)soff.dev, nq, stream, &mx, &mn))) return rc;

@@ -9,6 +9,9 @@
      steps, locate, locate_hits and extract, per layout, alphabet and row width, against the CPU walk of the oracle.
   3. The same check list with 64-bit rows on super-blocks of 2^16 rows (three of them), so that the super tables of Formats A / P / M, the builder's, the
      locate kernels' and the lean kernel's LDS copy are read beyond their first entry.
+  4. The symbol-plane table (Format S, k_exact_s) in that build: count fields of 16 bits in both row widths, three super-blocks — exact search by every selection
+     and with interval tables at sigma = 6, 21, 25, 26, 28, 29, the super table in LDS and through L2, workgroups of 256 and 512 lanes, and skewed collections that
+     set a field's top bit before each boundary.  (The shipped field widths at their real boundaries: tests/test_gpu_symbol_planes.py.)
 
 The reference's own rank(n, .) at n = k P counts the closed super-block twice: pinned in QUIRK_ROW."""
 import functools
@@ -133,12 +136,27 @@ BOUNDARIES = (65_520, 65_532, 65_536, 131_040, 131_064, 131_072)     # two super
 AIM_OFFSETS = (-65, -64, -63, -2, -1, 0, 1, 2, 63, 64, 65)
 AIM_LENGTHS = (1, 2, 3, 5, 8, 12, 20, 40)
 SCHEMES = {"h2": lambda: fm.search_scheme.h2(3, 0, 1), "pigeon": lambda: fm.search_scheme.pigeon_opt(0, 1)}
+PLANES_EXTRA_SIGMAS = (25, 26, 29)                                   # alphabets of part 4 (exact search on the symbol-plane table) beyond EDGE_SIGMAS
+SKEWED = ((29, 1), (29, 28))                                         # (sigma, dominant symbol) of part 4's skewed collections: the first symbol and the last
+
+
+def skewed_text(n, sigma, dominant, seed):
+    """n symbols: `dominant` at 90 % of the positions, placed at random (no runs beyond chance), the other symbols of 1 .. sigma - 1 uniform over the rest"""
+    rng = np.random.default_rng(seed)
+    other = rng.integers(1, sigma - 1, size=n, dtype=np.uint8)
+    other += other >= dominant
+    return np.where(rng.random(n) < 0.9, np.uint8(dominant), other).astype(np.uint8)
+
+
+def collection(sigma, dominant=0):
+    return _collection(sigma, dominant)
 
 
 @functools.lru_cache(maxsize=None)
-def collection(sigma):
-    """two sequences of 100 000 and 31 369 symbols, sorted once: the oracle index (IB16, rate 4, bidirectional) and what OraIndex.from_bwt needs for another layout"""
-    seqs = [make_text(100_000, sigma, seed=3), make_text(31_369, sigma, seed=4)]
+def _collection(sigma, dominant):
+    """two sequences of 100 000 and 31 369 symbols, sorted once: the oracle index (IB16, rate 4, bidirectional) and what OraIndex.from_bwt needs for another layout
+    (dominant = d: the skewed collection of part 4, symbol d at 90 % of the positions)"""
+    seqs = [make_text(100_000, sigma, seed=3), make_text(31_369, sigma, seed=4)] if not dominant else [skewed_text(100_000, sigma, dominant, 3), skewed_text(31_369, sigma, dominant, 4)]
     ox = fo.OraIndex.build("IB16", sigma, seqs, 4, True)
     n = ox.n
     assert n == N_ROWS
@@ -160,11 +178,15 @@ def text_position(ox, row):
     return int(seq), int(pos + steps)
 
 
+def batch(sigma, dominant=0):
+    return _batch(sigma, dominant)
+
+
 @functools.lru_cache(maxsize=None)
-def batch(sigma):
+def _batch(sigma, dominant):
     """(reads, rows of the aimed reads): per row beside a boundary the first L symbols of its suffix, the same with one substitution and with a delimiter,
     and 500 reads from random places"""
-    seqs, ox, _ = collection(sigma)
+    seqs, ox, _ = collection(sigma, dominant)
     rng = np.random.default_rng(1000 + sigma)
     aimed, rows = [], []
     for b in BOUNDARIES:
@@ -281,17 +303,17 @@ def expected(sigma):
 
 def test_the_batch_is_what_it_claims():
     """CPU only: every aimed read's interval contains its row; at least 100 intervals straddle a boundary (lb < b < lb + len), at least 20 begin or end exactly
-    on one, at least 100 are a single row — for each of the six alphabets"""
-    for sigma in EDGE_SIGMAS:
-        seqs, ox, _ = collection(sigma)
-        reads, rows = batch(sigma)
+    on one, at least 100 are a single row — for each of the six alphabets and for the three that only the symbol-plane checks of part 4 add (its skewed collections: see there)"""
+    for sigma, dominant in [(s, 0) for s in EDGE_SIGMAS + PLANES_EXTRA_SIGMAS]:
+        seqs, ox, _ = collection(sigma, dominant)
+        reads, rows = batch(sigma, dominant)
         lb, ln = ox.search_exact(*fm.flatten(reads[: len(rows)]))
         assert ((lb <= rows) & (rows < lb + ln)).all(), sigma
         straddle = sum(int(((lb < b) & (b < lb + ln)).sum()) for b in BOUNDARIES)
         on_edge = sum(int(((lb == b) | (lb + ln == b)).sum()) for b in BOUNDARIES)
         one_row = int((ln == 1).sum())
-        print("sigma %d: %d aimed reads, %d straddle a boundary, %d begin or end on one, %d are one row" % (sigma, len(rows), straddle, on_edge, one_row))
-        assert straddle >= 100 and on_edge >= 20 and one_row >= 100, (sigma, straddle, on_edge, one_row)
+        print("sigma %d%s: %d aimed reads, %d straddle a boundary, %d begin or end on one, %d are one row" % (sigma, ", symbol %d dominant" % dominant if dominant else "", len(rows), straddle, on_edge, one_row))
+        assert straddle >= 100 and on_edge >= 20 and one_row >= 100, (sigma, dominant, straddle, on_edge, one_row)
 
 
 def exact_selections(sigma, wide):
@@ -434,8 +456,8 @@ def variant_options(layout, sigma):
     return out
 
 
-def layout_oracle(layout, sigma):
-    seqs, ox, arrays = collection(sigma)
+def layout_oracle(layout, sigma, dominant=0):
+    seqs, ox, arrays = collection(sigma, dominant)
     return ox if layout == "IB16" else fo.OraIndex.from_bwt(layout, sigma, *arrays)
 
 
@@ -533,3 +555,134 @@ def test_wide_super_blocks_of_2_16_rows(layout, sigma, tmp_path):
     assert compare(got, sigma, (layout, sigma, "64-bit rows, super-blocks of 2^16 rows")) > 40
     if layout in ("IB16", "WAVELET"):
         assert any(k.endswith("built2/default") for k in got) and any(k.endswith("built1/default") for k in got)
+
+
+# ------------------------------------------------------------------------------------------------ 4. the symbol-plane table on super-blocks of 2^16 rows
+# In the development build with SUPER_SHIFT = 16 the count fields of Format S are min(shipped width, 16) = 16 bits wide in both row widths (fmgpu_common.h,
+# flat_count_bits): 131 371 rows are three of its super-blocks, a count reaches 2^16 - 64, and the aimed reads stand on both boundaries — against the oracle.
+# (A 16-bit field never lies in two 32-bit words: the straddling store and load are what tests/test_gpu_symbol_planes.py reaches at the shipped widths.)
+PLANES_CASES = {6: ("WAVELET", "EPR16", "EPRV2_16"), 21: ("WAVELET",), 25: ("WAVELET",), 26: ("WAVELET",), 28: ("WAVELET", "EPR16", "EPRV2_16"), 29: ("WAVELET",)}
+# the development knobs that choose among result-identical paths of k_exact_s: (environment, lanes of a workgroup, the super table staged in LDS)
+PLANES_KNOBS = {"default": ({}, 512, True), "super_through_l2": ({"FMGPU_DEV_FLAT_SUPER_MAX": "0"}, 512, False),
+                "lanes_256": ({"FMGPU_DEV_FLAT_LANES": "256"}, 256, True), "lanes_512": ({"FMGPU_DEV_FLAT_LANES": "512"}, 512, True)}
+
+
+@functools.lru_cache(maxsize=None)
+def expected_exact(sigma, dominant=0):
+    """the oracle's intervals and step count of the batch: what every path of part 4 must return"""
+    _, ox, _ = collection(sigma, dominant)
+    lb, ln, st = ox.search_exact(*fm.flatten(batch(sigma, dominant)[0]), want_steps=True)
+    return {"exact": np.stack([lb, ln]), "exact_steps": np.array([int(st.sum())], dtype=np.uint64)}
+
+
+def planes_tables(sigma, wide):
+    """an interval table alone in front of the symbol planes (k_exact_s starts from its entry), then the combinations of exact_tables (a k-step table puts Format A under
+    the search: the planes must hand over and take back)"""
+    return [(0, 1, 0), (0, 2, 0), (0, 3, 0)] + exact_tables(sigma, wide)[:3]
+
+
+PLANES_PATHS = 2 * 2 + 3 * 2 * 2 + 3 * 2 + 1                          # arrays per handle: (intervals, steps) by 2 selections, 3 x 2 + 3 table paths; tables dropped
+
+
+def collect_planes(gx, sigma, dominant, tag, R):
+    """exact search of the batch by every selection and with interval tables, on a handle that holds the symbol-plane table"""
+    assert gx.formats & capi.FMT_PLANES and gx.n == N_ROWS, tag
+    queries = fm.flatten(batch(sigma, dominant)[0])
+    for name, sel in exact_selections(sigma, gx.row_bits == 64):
+        with fm.options(kernel_select=sel):
+            R["exact@%s/%s" % (tag, name)], R["exact_steps@%s/%s" % (tag, name)] = exact_of(gx, queries)
+    for ks, lut, walk in planes_tables(sigma, gx.row_bits == 64):
+        gx.accelerate(ks, lut_len=lut, walk=walk)
+        for name, sel in (("", 0), ("_off", capi.SEL_NO_EXACT_LUT)) if ks == 0 else (("", 0),):
+            with fm.options(kernel_select=sel):
+                path = "%s/kstep%d_lut%d_walk%d%s" % (tag, ks, lut, walk, name)
+                R["exact@" + path], R["exact_steps@" + path] = exact_of(gx, queries)
+    gx.accelerate(0)
+    R["exact@%s/tables_dropped" % tag], _ = exact_of(gx, queries)
+
+
+def check_planes(sigma, dominant=0):
+    """every layout of PLANES_CASES[sigma] in both row widths, from the oracle's arrays and (Wavelet) built on the device by two suffix sorters"""
+    R = {}
+    seqs, _, _ = collection(sigma, dominant)
+    for layout in PLANES_CASES[sigma] if not dominant else ("WAVELET",):
+        lx = layout_oracle(layout, sigma, dominant)
+        for wide in (0, 1):
+            with fm.options(force_wide=wide):
+                gx = fm.FMIndex.from_reference_arrays(bwt=oracle_arrays(lx)["bwt"], C_array=oracle_arrays(lx)["C_array"])
+                assert gx.row_bits == (64 if wide else 32)
+                collect_planes(gx, sigma, dominant, "%s/rows%d/arrays" % (layout, gx.row_bits), R)
+                for sorter in (1, 2) if layout == "WAVELET" else ():
+                    with fm.options(suffix_sorter=sorter, bucket_rows=0 if sorter < 2 else 40_000):
+                        bx = fm.FMIndex.from_sequences(seqs, sigma, layout, 4)
+                    collect_planes(bx, sigma, dominant, "%s/rows%d/built%d" % (layout, bx.row_bits, sorter), R)
+    return R
+
+
+_CHILD_PLANES = r"""
+import os, sys
+sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, "oracle"))
+import ctypes as C
+import numpy as np
+from fmindex_collection_amd import capi
+from tests import test_gpu_superblocks as t
+sigma, dominant, knob, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
+L = capi.lib()
+assert L.fmgpu_dev_super_shift() == t.DEV_SHIFT and t.N_ROWS >> t.DEV_SHIFT == 2
+R = t.check_planes(sigma, dominant)
+lanes, super_lds, bits = C.c_uint32(), C.c_uint32(), C.c_uint32()
+launches = L.fmgpu_dev_flat_launch(C.byref(lanes), C.byref(super_lds), C.byref(bits))
+R["launch"] = np.array([launches, lanes.value, super_lds.value, bits.value])
+np.savez(out, **R)
+print("PLANES_DONE", len(R))
+"""
+
+
+def run_planes_child(sigma, dominant, knob, tmp_path):
+    """check_planes in a child process that holds the development build with super-blocks of 2^16 rows and the knob's environment; what the child's last k_exact_s
+    launch took (fmgpu_dev_flat_launch) is asserted here: the paths a knob chooses among return the same intervals"""
+    lib = os.path.join(ROOT, "fmindex-collection_amd", "libfmgpu_dev_ss%d.so" % DEV_SHIFT)
+    assert os.path.exists(lib), "libfmgpu_dev_ss16.so is not built (make -C fmindex-collection_amd/csrc DEV=1 SUPER_SHIFT=16)"
+    extra, lanes, in_lds = PLANES_KNOBS[knob]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("FMGPU_")}
+    env.update(extra, FMGPU_LIBRARY=lib)
+    path = str(tmp_path / "planes.npz")
+    r = subprocess.run([sys.executable, "-c", _CHILD_PLANES % (ROOT, ROOT), str(sigma), str(dominant), knob, path], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "PLANES_DONE" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+    got = dict(np.load(path))
+    launches, got_lanes, got_super, got_bits = (int(v) for v in got.pop("launch"))
+    nsb = (N_ROWS >> DEV_SHIFT) + 1
+    assert launches > 0 and got_lanes == lanes and got_bits == DEV_SHIFT and got_super == (nsb * sigma if in_lds else 0), (knob, launches, got_lanes, got_super, got_bits)
+    E = expected_exact(sigma, dominant)
+    bad = [(name, np.argwhere(got[name] != E[name.split("@")[0]])[:3].tolist()) for name in sorted(got) if not np.array_equal(got[name], E[name.split("@")[0]])]
+    assert not bad, (sigma, dominant, knob, bad[:12])
+    return got
+
+
+@gpu
+@pytest.mark.parametrize("knob", list(PLANES_KNOBS))
+@pytest.mark.parametrize("sigma", list(PLANES_CASES))
+def test_symbol_planes_on_super_blocks_of_2_16_rows(sigma, knob, tmp_path):
+    """exact search on Format S with 16-bit count fields and three super-blocks, 32- and 64-bit rows: a Wavelet at sigma = 6, 21, 25, 26, 28, 29 (from the oracle's arrays
+    and built on the device), EPR16 and EPRV2_16 blocks at sigma = 6 and 28 — every kernel selection, interval tables in front, against the oracle; then the same list
+    with the super table read through L2 and with workgroups of 256 and of 512 lanes forced, one child process each"""
+    got = run_planes_child(sigma, 0, knob, tmp_path)
+    handles = 2 * (3 + (len(PLANES_CASES[sigma]) - 1))                # per row width: the Wavelet from arrays and built twice, the EPR layouts from arrays
+    assert len(got) == handles * PLANES_PATHS, (len(got), handles)
+    assert any("rows32/built2/default" in k for k in got) and any("rows64/arrays/on_tree" in k for k in got)
+
+
+@gpu
+@pytest.mark.parametrize("sigma,dominant", SKEWED)
+def test_symbol_planes_with_full_count_fields(sigma, dominant, tmp_path):
+    """the skewed collection: one symbol holds 90 % of the 131 371 rows, so that its 16-bit count has the top bit set before each of the two boundaries (asserted on
+    the oracle's BWT) — the first symbol (its field in the upper half of a word) and the last one (in the lower half); exact search only, both row widths"""
+    _, _, arrays = collection(sigma, dominant)
+    bwt = arrays[0]
+    for b in (1 << DEV_SHIFT, 2 << DEV_SHIFT):
+        inside = int(np.count_nonzero(bwt[b - (1 << DEV_SHIFT): b - 64] == dominant))
+        assert inside >= 1 << (DEV_SHIFT - 1), (b, inside)
+    E = expected_exact(sigma, dominant)["exact"]                     # the batch on the oracle: wide intervals over the boundaries, and single rows
+    straddle = sum(int(((E[0] < b) & (b < E[0] + E[1])).sum()) for b in (1 << DEV_SHIFT, 2 << DEV_SHIFT))
+    assert straddle >= 100 and int((E[1] == 1).sum()) >= 100, (straddle, int((E[1] == 1).sum()))
+    assert len(run_planes_child(sigma, dominant, "default", tmp_path)) == 6 * PLANES_PATHS
