@@ -11,7 +11,7 @@ import pytest
 import fmoracle as fo
 import fmindex_collection_amd as fm
 from fmindex_collection_amd import capi
-from tests.util import make_text, sample_reads, oracle_arrays, string_arrays
+from tests.util import HIT_KEYS, make_text, same_hits, sample_reads, oracle_arrays, string_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -19,19 +19,11 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 REF = json.load(open(os.path.join(GOLD, "reference_tests.json")))
 LAYOUTS = ["IB8", "IB16", "IB32", "IB16A", "IBP16", "EPR8", "EPR16", "EPR32", "EPRV2_8", "EPRV2_16", "EPRV2_32", "WAVELET",
            "EPRV3_8", "EPRV3_16", "EPRV3_32", "EPRV4", "EPRV5", "IEPRV7", "FBV_64_64K", "FBV_512_64K", "FBV_2048_64K"]
-HIT_KEYS = ("qidx", "lb", "lb_rev", "len", "errors")
 
 
 def gpu_index(ox):
     cls = fm.BiFMIndex if ox.bidirectional else fm.FMIndex
     return cls.from_reference_arrays(**oracle_arrays(ox))
-
-
-def same_hits(g, o, unidirectional=False):
-    if len(g) != len(o):
-        return False
-    keys = [k for k in HIT_KEYS if not (unidirectional and k == "lb_rev")]
-    return all(np.array_equal(g[k].astype(np.uint64), o[k].astype(np.uint64)) for k in keys)
 
 
 def repeat_text(seed, n=3000):

@@ -2,6 +2,7 @@
 import numpy as np
 
 MASK64 = (1 << 64) - 1
+HIT_KEYS = ("qidx", "lb", "lb_rev", "len", "errors")
 
 
 def splitmix64(x):
@@ -83,3 +84,11 @@ def occurrences(text_with_delims, pattern, max_mismatch=0):
         mism += t[j: len(t) - m + 1 + j] != pattern[j]
     pos = np.nonzero(mism <= max_mismatch)[0]
     return pos, mism[pos]
+
+
+def same_hits(g, o, unidirectional=False):
+    """two arrays of hit records: the same records in the same order (lb_rev is not compared on a unidirectional index)"""
+    if len(g) != len(o):
+        return False
+    keys = [k for k in HIT_KEYS if not (unidirectional and k == "lb_rev")]
+    return all(np.array_equal(g[k].astype(np.uint64), o[k].astype(np.uint64)) for k in keys)
