@@ -20,7 +20,7 @@ from . import search_scheme  # noqa: F401
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer",
-           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
+           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
 
 
 class _Options:
@@ -1610,3 +1610,74 @@ def format_positions(positions, columns=("qidx", "seq_id", "pos", "errors"), sep
     del keep
     res = (out, total) if device else out[:total].tobytes()
     return (res, off) if want_line_offsets else res
+
+
+# ---- positions to SAM records on the device (fmgpu_positions_sam, fmgpu_sam_header)
+def char_table(letters="ACGT", first_rank=1, other="N", extra=None):
+    """the inverse of symbol_table: the 256-entry uint8 table a SEQ byte is read from: value first_rank + i -> letters[i], `extra` = {value: byte or one-character
+    string} on top, every other value (255, the FOREIGN symbol, among them) -> `other`.  char_table("dna5") is the inverse of symbol_table.dna5(): $ A C G T = 0 .. 4."""
+    if letters == "dna5":
+        return char_table("ACGT", 1, "N", {0: "$"})
+    t = np.full(256, ord(other) if isinstance(other, str) else int(other), dtype=np.uint8)
+    for i, ch in enumerate(letters):
+        t[first_rank + i] = ord(ch)
+    for k, v in (extra or {}).items():
+        t[int(k)] = ord(v) if isinstance(v, str) else int(v)
+    return t
+
+
+def format_sam(positions, queries, char_of="dna5", strands=None, read_names=None, quals=None, seq_names=None, cigar=True, emit_unmapped=True, secondary_seq=False,
+               mapq=(60, 0), device=False, want_line_offsets=False, stream=None):
+    """fmgpu_positions_sam: the positions of map_reads / Feed.map as SAM alignment lines, made on the device.  positions: a POSITION_DTYPE array, or a DeviceBuffer /
+    torch tensor of such records; queries: the FORWARD batch they were mapped from ((qbuf, qoff) of numpy arrays or DeviceBuffers, or a list of sequences); char_of: a
+    char_table (or "dna5").  strands: the complement table the reads were mapped with (or "dna5"): qidx counts both strands, an odd one is written reversed and
+    complemented with flag 16.  read_names / quals / seq_names: a (data, spans) pair — what parse_queries returns with want_names / want_quals, with the text as data —
+    or a list of bytes / str; without them QNAME and RNAME are numbers and QUAL is '*'.  cigar=True states that the search was ungapped ("<m>M"); mapq = (unique, multi).
+    Returns the text as bytes, or with device=True (DeviceBuffer, bytes); with want_line_offsets also the uint64 offsets of the lines (lines + 1 entries)."""
+    if isinstance(positions, np.ndarray):
+        positions = np.ascontiguousarray(positions, dtype=POSITION_DTYPE)
+    pp, pbytes = _buffer(positions)
+    count = pbytes // POSITION_DTYPE.itemsize
+    if isinstance(queries, PackedQueries):
+        raise ValueError("format_sam takes the byte form of the batch")
+    qbuf, qoff, nq = _queries(queries)
+    if isinstance(qoff, np.ndarray):
+        qoff = _u64(qoff)
+    if isinstance(qbuf, np.ndarray):
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+    table = char_table("dna5") if isinstance(char_of, str) and char_of == "dna5" else np.ascontiguousarray(np.asarray(char_of, dtype=np.uint8))
+    if table.size != 256:
+        raise ValueError("a character table has 256 entries")
+    st, comp = _strands(strands, False)
+    spec = capi.SamSpec(_buffer(qbuf)[0] if nq > 0 else None, _buffer(qoff)[0] if nq > 0 else None, max(nq, 0), table.ctypes.data, C.pointer(st) if st is not None else None,
+                        None, None, None, 1 if cigar else 0, 1 if emit_unmapped else 0, 1 if secondary_seq else 0, int(mapq[0]), int(mapq[1]), (C.c_uint8 * 3)(0, 0, 0))
+    keep = [comp, table, qbuf, qoff]
+    for field, names in (("read_names", read_names), ("quals", quals), ("seq_names", seq_names)):
+        if names is not None:
+            t, alive = _name_table(names)
+            keep.append((t, alive))
+            setattr(spec, field, C.pointer(t))
+    sp = None if stream is None else C.c_void_p(stream if isinstance(stream, int) else getattr(stream, "cuda_stream", 0))
+    L, nbytes, nlines = capi.lib(), C.c_uint64(), C.c_uint64()
+    capi.check(L.fmgpu_positions_sam(pp, count, C.byref(spec), None, 0, C.byref(nbytes), None, C.byref(nlines), sp))       # the counting call sizes the text exactly
+    total, lines = int(nbytes.value), int(nlines.value)
+    off = np.zeros(lines + 1, dtype=np.uint64) if want_line_offsets else None
+    out = DeviceBuffer(max(total, 8)) if device else np.zeros(max(total, 1), dtype=np.uint8)
+    capi.check(L.fmgpu_positions_sam(pp, count, C.byref(spec), capi.ptr(out), total, C.byref(nbytes), capi.ptr(off), C.byref(nlines), sp))
+    del keep
+    res = (out, total) if device else out[:total].tobytes()
+    return (res, off) if want_line_offsets else res
+
+
+def sam_header(seq_names, lengths, program=None):
+    """fmgpu_sam_header: the @HD line, one @SQ line per sequence (its name up to the first blank, its length) and, with `program`, a @PG line, as bytes.  seq_names: a
+    list of bytes / str or a host (data, spans) pair."""
+    lengths = _u64(lengths).reshape(-1)
+    table, alive = _name_table(seq_names)
+    prog = None if program is None else (program.encode("utf-8") if isinstance(program, str) else bytes(program))
+    L, nbytes = capi.lib(), C.c_uint64()
+    capi.check(L.fmgpu_sam_header(C.byref(table), capi.ptr(lengths), lengths.size, prog, None, 0, C.byref(nbytes)))
+    out = np.zeros(max(int(nbytes.value), 1), dtype=np.uint8)
+    capi.check(L.fmgpu_sam_header(C.byref(table), capi.ptr(lengths), lengths.size, prog, capi.ptr(out), int(nbytes.value), C.byref(nbytes)))
+    del alive
+    return out[:int(nbytes.value)].tobytes()

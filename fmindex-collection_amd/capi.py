@@ -175,6 +175,17 @@ class FormatSpec(C.Structure):
 
 
 assert C.sizeof(NameTable) == 32 and C.sizeof(FormatSpec) == 40
+
+
+class SamSpec(C.Structure):
+    """fmgpu_sam_spec: the batch, the tables and the switches of fmgpu_positions_sam (host memory)"""
+    _fields_ = [("qbuf", C.c_void_p), ("qoff", C.c_void_p), ("nq", C.c_uint64), ("char_of", C.c_void_p), ("strands", C.POINTER(Strands)),
+                ("read_names", C.POINTER(NameTable)), ("quals", C.POINTER(NameTable)), ("seq_names", C.POINTER(NameTable)),
+                ("cigar", C.c_uint8), ("emit_unmapped", C.c_uint8), ("secondary_seq", C.c_uint8), ("mapq_unique", C.c_uint8), ("mapq_multi", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
+assert C.sizeof(SamSpec) == 72
 COL_QIDX, COL_SEQ_ID, COL_POS, COL_ERRORS, COL_HIT, COL_READ, COL_STRAND, COL_READ_NAME, COL_SEQ_NAME = range(9)
 COLUMNS = {"qidx": COL_QIDX, "seq_id": COL_SEQ_ID, "pos": COL_POS, "errors": COL_ERRORS, "hit": COL_HIT, "read": COL_READ, "strand": COL_STRAND,
            "read_name": COL_READ_NAME, "seq_name": COL_SEQ_NAME}
@@ -203,6 +214,7 @@ EXPORTS = [
     "fmgpu_queries_parse", "fmgpu_feed_map_text",
     "fmgpu_queries_strands", "fmgpu_search_best_pairs", "fmgpu_search_best_ng21_pairs", "fmgpu_map_strands", "fmgpu_feed_map_strands", "fmgpu_feed_map_text_strands",
     "fmgpu_positions_format",
+    "fmgpu_positions_sam", "fmgpu_sam_header",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -363,6 +375,9 @@ def lib():
         L.fmgpu_feed_map_text_strands.argtypes = L.fmgpu_feed_map_text.argtypes[:8] + [C.POINTER(Strands)] + L.fmgpu_feed_map_text.argtypes[8:]
     if hasattr(L, "fmgpu_positions_format"):                  # (FMGPU_LIBRARY may name an older build of the same ABI)
         L.fmgpu_positions_format.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(FormatSpec), C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "fmgpu_positions_sam"):                     # (FMGPU_LIBRARY may name an older build of the same ABI)
+        L.fmgpu_positions_sam.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(SamSpec), C.c_void_p, C.c_uint64, u64p, C.c_void_p, u64p, C.c_void_p]
+        L.fmgpu_sam_header.argtypes = [C.POINTER(NameTable), C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_uint64, u64p]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

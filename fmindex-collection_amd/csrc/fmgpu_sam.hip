@@ -1,0 +1,548 @@
+// fmgpu_sam.hip — fmgpu_positions_sam and fmgpu_sam_header (include/fmgpu.h): located hits to SAM records on the device.  Nothing here depends on the row width or
+// on an index.  A line is about 220 bytes for 101 bp reads, most of them copied read and quality bytes, so the path is a stream whose stores dominate.  The passes:
+//  k_sam_records  one lane per record: read number in range and not below its predecessor's (an offending record atomicMin's its index into an error word), the first
+//                 and the last record of each read from the boundaries between neighbours, atomicMin of (errors, index) per read = its primary record
+//  k_sam_count    one lane per record: how many records of the read carry its minimal errors (MAPQ)
+//  k_sam_reads    one lane per read: the offsets of the batch do not decrease; the lines of the read (its records, or one unmapped line)
+//  (hipcub exclusive scan of the line counts: each read's first line)
+//  k_sam_measure  one lane per line of the bound count + nq (the number of lines is known on the device only): the line's length as one 32-bit word, names, quality
+//                 spans and lengths checked; a line behind the last one measures 0
+//  (hipcub exclusive scan of the lengths to 64-bit offsets; the size of the text, the number of lines and the error words are read back together, once)
+//  k_sam_write    the OUTPUT is cut into windows of 16 KiB aligned to 16 bytes of the output address, one per workgroup: each wave finds the lines that touch
+//                 the window and their reads by searches of 64 probes per step, a lane per line formats the short fields of its part inside the window into LDS, the
+//                 waves copy SEQ and QUAL, eight lanes to a field (aligned 16-byte loads, strand 1 reversed in registers, the symbol-to-character tables in LDS), and the
+//                 window leaves as aligned 16-byte stores: only the first and last bytes of the text leave byte by byte.  Equal windows balance a heavy-tailed batch by construction.
+// Every pass behind the first reads the error words and does nothing once one is set: a batch that is out of order indexes nothing.
+// Scratch: 32 bytes per read and 12 bytes per line of the bound, plus the scans' own, freed on return.
+#include "fmgpu_common.h"
+#include "fmgpu_pieces.h"
+
+#include <hipcub/hipcub.hpp>
+
+namespace fmgpu {
+namespace {
+
+constexpr uint32_t kSamWindow = 16384;                      // bytes of LDS a workgroup formats into (a multiple of 16)
+constexpr uint64_t kNone = ~0ull;
+constexpr uint32_t kNoRecord32 = 0xffffffffu;
+constexpr uint64_t kMaxSamLines = (1ull << 32) - 256;
+constexpr uint64_t kMaxSamBytes = 1ull << 31;               // a read or a name of this many bytes is refused
+
+// the error words behind the offsets: the lowest record whose read is >= nq; whose read lies below its predecessor's; the lowest read whose offsets decrease; the lowest
+// (line << 8 | code) the measure pass refuses as invalid; ... as unsupported; and (no error) the number of lines
+enum : int { E_RANGE = 0, E_ORDER = 1, E_QOFF = 2, E_LINE = 3, E_LONG = 4, E_LINES = 5, E_WORDS = 6 };
+enum : uint32_t { BAD_NONE = 0, BAD_RNAME_ROW = 1, BAD_RNAME_SPAN = 2, BAD_QUAL_ROW = 3, BAD_QUAL_SPAN = 4, BAD_QUAL_LEN = 5, BAD_SNAME_ROW = 6, BAD_SNAME_SPAN = 7 };
+enum : uint32_t { LONG_NONE = 0, LONG_READ = 1, LONG_NAME = 2, LONG_LINE = 3 };
+
+struct SamTable { const uint8_t* bytes; uint64_t n_bytes; const fmgpu_text_span* spans; uint64_t count; };
+struct SamArgs {
+    const fmgpu_position* pos; uint64_t count;
+    const uint8_t* qbuf; const uint64_t* qoff; uint64_t nq;
+    SamTable read_names, quals, seq_names;
+    uint8_t shift, use_read_names, use_quals, use_seq_names, cigar, emit_unmapped, secondary_seq, mapq_unique, mapq_multi;
+    int aligned16;                                          // the records may be loaded as 16-byte pieces
+    unsigned long long* key;                                // per read: (errors << 32 | record) of its primary record
+    uint32_t *first, *end, *nmin;                           // per read: its first record, one behind its last, its records with the minimal errors
+    uint32_t* lcount;                                       // nq + 1: the lines of each read
+    uint64_t* lstart;                                       // nq + 1: each read's first line; [nq] = the number of lines
+    unsigned long long* err;                                // E_WORDS words
+    uint64_t bound;                                         // count + (emit_unmapped ? nq : 0) >= the number of lines
+};
+
+__device__ const uint64_t kPow10[20] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull, 1000000000ull, 10000000000ull,
+                                        100000000000ull, 1000000000000ull, 10000000000000ull, 100000000000000ull, 1000000000000000ull, 10000000000000000ull,
+                                        100000000000000000ull, 1000000000000000000ull, 10000000000000000000ull};
+
+// decimal digits of v (0 has one): floor(log10) estimated from the bit length (1233 / 4096 ~ log10 2), corrected by one compare
+__device__ __forceinline__ uint32_t digits10(uint64_t v) {
+    v |= 1ull;
+    const uint32_t t = ((64u - (uint32_t)__clzll((long long)v)) * 1233u) >> 12;
+    return t + 1u - (v < kPow10[t] ? 1u : 0u);
+}
+
+__device__ __forceinline__ fmgpu_position load_record(const fmgpu_position* __restrict__ p, uint64_t i, int aligned16) {
+    fmgpu_position r;
+    if (aligned16) {
+        const ulonglong2 a = reinterpret_cast<const ulonglong2*>(p)[2 * i], b = reinterpret_cast<const ulonglong2*>(p)[2 * i + 1];
+        r.qidx = a.x; r.seq_id = a.y; r.pos = b.x; r.errors = (uint32_t)b.y; r.hit = (uint32_t)(b.y >> 32);
+    } else r = p[i];
+    return r;
+}
+
+__device__ __forceinline__ bool failed(const SamArgs& a) { return (a.err[E_RANGE] & a.err[E_ORDER] & a.err[E_QOFF]) != kNone; }
+
+__global__ __launch_bounds__(256) void k_sam_records(SamArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    const uint64_t read = a.pos[i].qidx >> a.shift;
+    if (read >= a.nq) { atomicMin(&a.err[E_RANGE], (unsigned long long)i); return; }
+    const uint64_t before = i ? a.pos[i - 1].qidx >> a.shift : kNone, behind = i + 1 < a.count ? a.pos[i + 1].qidx >> a.shift : kNone;
+    if (i && before > read) atomicMin(&a.err[E_ORDER], (unsigned long long)i);
+    if (before != read) a.first[read] = (uint32_t)i;
+    if (behind != read) a.end[read] = (uint32_t)i + 1u;
+    atomicMin(&a.key[read], ((unsigned long long)a.pos[i].errors << 32) | (unsigned long long)i);
+}
+
+__global__ __launch_bounds__(256) void k_sam_count(SamArgs a) {
+    if (failed(a)) return;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    const uint64_t read = a.pos[i].qidx >> a.shift;
+    if ((uint32_t)(a.key[read] >> 32) == a.pos[i].errors) atomicAdd(&a.nmin[read], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_sam_reads(SamArgs a) {
+    if ((a.err[E_RANGE] & a.err[E_ORDER]) != kNone) return;
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > a.nq) return;
+    if (r == a.nq) { a.lcount[r] = 0; return; }
+    if (a.qoff[r + 1] < a.qoff[r]) atomicMin(&a.err[E_QOFF], (unsigned long long)r);
+    const uint32_t f = a.first[r];
+    a.lcount[r] = f != kNoRecord32 ? a.end[r] - f : (uint32_t)a.emit_unmapped;
+}
+
+// one line of the output: where it comes from and how long its fields are
+struct Line {
+    uint32_t bad, toolong;
+    bool mapped, star_seq, star_qual, star_cigar;
+    uint64_t read;
+    fmgpu_position rec;                                     // (mapped)
+    uint32_t m, flag, mapq, nh;
+    const uint8_t *q, *qual, *rname, *sname;                // the read's symbols, its qualities, its name (nullptr: the number), the sequence's name
+    uint32_t rn, sn;                                        // bytes of QNAME and of RNAME as written
+    uint64_t length;
+};
+
+// row `row` of a table; stop: the name ends in front of its first ' ' or '\t'
+__device__ __forceinline__ uint32_t row_of(const SamTable& t, uint64_t row, bool stop, const uint8_t** src, uint64_t* len, uint32_t* toolong) {
+    *src = t.bytes; *len = 0;
+    if (row >= t.count) return 1;
+    const uint64_t o = t.spans[row].offset, n = t.spans[row].len;
+    if (n > t.n_bytes || o > t.n_bytes - n) return 2;
+    if (n >= kMaxSamBytes) { if (!*toolong) *toolong = LONG_NAME; return 0; }
+    const uint8_t* s = t.bytes + o;
+    uint64_t m = n;
+    if (stop) for (uint64_t j = 0; j < n; ++j) { const uint8_t b = s[j]; if (b == ' ' || b == '\t') { m = j; break; } }
+    *src = s; *len = m;
+    return 0;
+}
+
+// [lo, hi): reads known to hold the line's (lstart[lo] <= line < lstart[hi])
+__device__ __forceinline__ Line describe(const SamArgs& a, uint64_t line, uint64_t lo, uint64_t hi) {
+    Line d;                                                 // the last read r with lstart[r] <= line: the one that has lines (lstart increases strictly over such reads)
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (a.lstart[mid] <= line) lo = mid; else hi = mid; }
+    d.read = lo;
+    d.bad = BAD_NONE; d.toolong = LONG_NONE;
+    const uint32_t first = a.first[lo];
+    d.mapped = first != kNoRecord32;
+    const uint64_t q0 = a.qoff[lo], m64 = a.qoff[lo + 1] - q0;
+    if (m64 >= kMaxSamBytes) d.toolong = LONG_READ;
+    d.m = d.toolong ? 0u : (uint32_t)m64;
+    d.q = a.qbuf + q0;
+    uint32_t strand = 0;
+    bool secondary = false;
+    d.flag = 4; d.mapq = 0; d.nh = 0;
+    d.rec = fmgpu_position{0, 0, 0, 0, 0};
+    if (d.mapped) {
+        const uint64_t i = first + (line - a.lstart[lo]);
+        d.rec = load_record(a.pos, i, a.aligned16);
+        strand = a.shift ? (uint32_t)(d.rec.qidx & 1u) : 0u;
+        const unsigned long long key = a.key[lo];
+        secondary = (uint32_t)key != (uint32_t)i;
+        d.flag = (strand ? 16u : 0u) | (secondary ? 256u : 0u);
+        d.mapq = !secondary && a.nmin[lo] == 1u ? a.mapq_unique : a.mapq_multi;
+        d.nh = a.end[lo] - first;
+    }
+    uint32_t b;
+    uint64_t n = 0;
+    d.rname = nullptr; d.rn = digits10(d.read);
+    if (a.use_read_names) {
+        if ((b = row_of(a.read_names, d.read, true, &d.rname, &n, &d.toolong))) d.bad = BAD_RNAME_ROW + b - 1;
+        d.rn = n ? (uint32_t)n : 1u;
+        if (!n) d.rname = nullptr;
+    }
+    d.qual = nullptr;
+    uint64_t qn = 0;
+    if (a.use_quals) {
+        if ((b = row_of(a.quals, d.read, false, &d.qual, &qn, &d.toolong)) && !d.bad) d.bad = BAD_QUAL_ROW + b - 1;
+        else if (!b && !d.toolong && qn != 0 && qn != d.m && !d.bad) d.bad = BAD_QUAL_LEN;
+    }
+    d.sname = nullptr; d.sn = 1;
+    if (d.mapped) {
+        d.sn = digits10(d.rec.seq_id);
+        if (a.use_seq_names) {
+            if ((b = row_of(a.seq_names, d.rec.seq_id, true, &d.sname, &n, &d.toolong)) && !d.bad) d.bad = BAD_SNAME_ROW + b - 1;
+            d.sn = n ? (uint32_t)n : 1u;
+            if (!n) d.sname = nullptr;
+        }
+    }
+    d.star_seq = d.m == 0 || (secondary && !a.secondary_seq);
+    d.star_qual = d.star_seq || !a.use_quals || qn == 0;
+    d.star_cigar = !d.mapped || !a.cigar || d.m == 0;
+    // QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL [NM:i: NH:i:] and eleven or thirteen separators
+    uint64_t len = (uint64_t)d.rn + digits10(d.flag) + d.sn + (d.mapped ? digits10(d.rec.pos + 1) : 1u) + digits10(d.mapq) + (d.star_cigar ? 1u : digits10(d.m) + 1u) + 3u +
+                   (d.star_seq ? 1u : d.m) + (d.star_qual ? 1u : d.m) + 11u;
+    if (d.mapped) len += 5u + digits10(d.rec.errors) + 5u + digits10(d.nh) + 2u;
+    if (!d.toolong && (len >> 32)) d.toolong = LONG_LINE;
+    d.length = len;
+    return d;
+}
+
+__global__ __launch_bounds__(256) void k_sam_measure(SamArgs a, uint32_t* __restrict__ lens) {
+    const uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (l > a.bound) return;
+    const bool dead = failed(a);
+    const uint64_t lines = dead ? 0 : a.lstart[a.nq];
+    if (l == a.bound) a.err[E_LINES] = lines;
+    if (l >= lines) { lens[l] = 0; return; }
+    const Line d = describe(a, l, 0, a.nq);
+    if (d.bad) atomicMin(&a.err[E_LINE], (unsigned long long)((l << 8) | d.bad));
+    if (d.toolong) atomicMin(&a.err[E_LONG], (unsigned long long)((l << 8) | d.toolong));
+    lens[l] = d.bad || d.toolong ? 0u : (uint32_t)d.length;
+}
+
+// what a refused line was: out[0] = its read, out[1] = its record (kNone: the read has none)
+__global__ void k_sam_explain(SamArgs a, uint64_t line, uint64_t* out) {
+    uint64_t lo = 0, hi = a.nq;
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (a.lstart[mid] <= line) lo = mid; else hi = mid; }
+    out[0] = lo;
+    out[1] = a.first[lo] != kNoRecord32 ? a.first[lo] + (line - a.lstart[lo]) : kNone;
+}
+
+// the last index i of a[0 .. n - 1] with a[i] <= key (strict: a[i] < key), a non-decreasing and a[0] passing; by the whole wave, 64 probes per step
+__device__ __forceinline__ uint64_t wave_search(const uint64_t* __restrict__ a, uint64_t n, uint64_t key, bool strict) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint64_t step = (hi - lo + 63u) / 64u, at = lo + lane * step;
+        bool pass = false;
+        if (at < hi) { const uint64_t v = a[at]; pass = strict ? v < key : v <= key; }
+        const uint64_t passing = (uint64_t)__popcll(__ballot(pass));          // (a prefix of the lanes, lane 0 among them)
+        lo += (passing - 1) * step;
+        hi = lo + step < hi ? lo + step : hi;
+    }
+    return lo;
+}
+
+struct Window {                                             // positions count from the 16-byte piece of the output address that holds the text's first byte
+    uint8_t* lds; uint64_t lo;
+    __device__ __forceinline__ void put(uint64_t at, uint32_t b) const { const uint64_t k = at - lo; if (k < kSamWindow) lds[k] = (uint8_t)b; }
+};
+
+__device__ __forceinline__ void put_decimal(const Window& w, uint64_t v, uint64_t end) {       // its last digit at end - 1
+    while (v >> 32) {
+        const uint64_t q = v / 1000000000ull;
+        uint32_t r = (uint32_t)(v - q * 1000000000ull);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { w.put(--end, '0' + r % 10u); r /= 10u; }
+        v = q;
+    }
+    uint32_t x = (uint32_t)v;
+    do { w.put(--end, '0' + x % 10u); x /= 10u; } while (x);
+}
+__device__ __forceinline__ uint64_t field_decimal(const Window& w, uint64_t at, uint64_t v, uint32_t sep) {
+    const uint32_t d = digits10(v);
+    put_decimal(w, v, at + d);
+    w.put(at + d, sep);
+    return at + d + 1;
+}
+__device__ __forceinline__ uint64_t field_text(const Window& w, uint64_t at, const char* s, uint32_t n) {
+    for (uint32_t k = 0; k < n; ++k) w.put(at + k, (uint32_t)(uint8_t)s[k]);
+    return at + n;
+}
+// a name by its lane, the part inside the window: without a table the number in decimal, '*' for an empty name (src == nullptr)
+__device__ __forceinline__ uint64_t field_name(const Window& w, uint64_t hi, uint64_t at, const uint8_t* src, uint32_t n, bool numbered, uint64_t number) {
+    if (!src && numbered) return field_decimal(w, at, number, '\t');
+    if (!src) { w.put(at, '*'); w.put(at + 1, '\t'); return at + 2; }
+    if (at < hi && at + n > w.lo) {
+        const uint32_t j0 = at < w.lo ? (uint32_t)(w.lo - at) : 0u, j1 = at + n > hi ? (uint32_t)(hi - at) : n;
+        for (uint32_t j = j0; j < j1; ++j) w.lds[at + j - w.lo] = src[j];
+    }
+    w.put(at + n, '\t');
+    return at + n + 1;
+}
+
+// `len` bytes at position `at`, the part inside the window, copied by the wave, eight lanes to a field: a lane makes up to 16 bytes of the line from the aligned
+// 16-byte pieces that hold their source, reversed in registers where `rev` (byte j of the line is byte len - 1 - j of src), each sent through the strand's 256 entries
+// of tab (nullptr: as it is).  Every lane of the wave calls it; a lane without such a field passes len = 0.
+__device__ __forceinline__ void put_run(const Window& w, uint64_t hi, const uint8_t* src, uint32_t len, uint64_t at, uint32_t rev, const uint8_t* tab) {
+    uint32_t j0 = 0, j1 = 0;                                // bytes j0 .. j1 - 1 of the field lie in the window
+    if (len && at < hi && at + len > w.lo) { j0 = at < w.lo ? (uint32_t)(w.lo - at) : 0u; j1 = at + len > hi ? (uint32_t)(hi - at) : len; }
+    unsigned long long todo = __ballot(j1 > j0);
+    const uint32_t lane = threadIdx.x & 63u, slot = lane >> 3, sub = lane & 7u;
+    while (todo) {                                          // eight fields per round, eight lanes (128 bytes a step) each
+        unsigned long long mine = todo;
+        for (uint32_t k = 0; k < slot; ++k) mine &= mine - 1;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) todo &= todo - 1;
+        const int l = mine ? __ffsll((long long)mine) - 1 : 0;
+        const unsigned long long s = __shfl((unsigned long long)reinterpret_cast<uintptr_t>(src), l), p = __shfl((unsigned long long)at, l);
+        const uint32_t b = (uint32_t)__shfl((int)j0, l), e = (uint32_t)__shfl((int)j1, l), n = (uint32_t)__shfl((int)len, l), r = (uint32_t)__shfl((int)rev, l);
+        const uint8_t* from = reinterpret_cast<const uint8_t*>((uintptr_t)s);
+        const uint8_t* tr = tab ? tab + 256u * r : nullptr;
+        for (uint32_t c = b + 16u * sub; mine && c < e; c += 128u) {
+            const uint32_t k = e - c < 16u ? e - c : 16u;
+            Piece v;
+            if (!r) v = load_bytes(from + c, k);
+            else {
+                const Piece f = load_bytes(from + (n - c - k), k);
+                v = piece_shr(Piece{__builtin_bswap64(f.hi), __builtin_bswap64(f.lo)}, 16u - k);
+            }
+            for (uint32_t x = 0; x < k; ++x) {
+                uint32_t byte = (uint32_t)((x < 8u ? v.lo >> (8u * x) : v.hi >> (8u * (x - 8u))) & 255u);
+                if (tr) byte = tr[byte];
+                w.lds[p + c + x - w.lo] = (uint8_t)byte;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sam_write(SamArgs a, const uint8_t* __restrict__ tables, const uint64_t* __restrict__ off, uint64_t lines, uint64_t total,
+                                                   uint8_t* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kSamWindow];
+    __shared__ uint8_t tab[512];                            // the SEQ byte of a symbol: [0, 256) strand 0, [256, 512) strand 1 (complemented)
+    tab[threadIdx.x] = tables[threadIdx.x];
+    tab[256u + threadIdx.x] = tables[256u + threadIdx.x];
+    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
+    uint8_t* const gbase = out - shift;                     // position 0: 16-byte aligned, never stored to below position `shift`
+    const uint64_t lo = (uint64_t)blockIdx.x * kSamWindow, extent = shift + total;
+    const uint64_t hi = lo + kSamWindow < extent ? lo + kSamWindow : extent;
+    const uint64_t from = lo > shift ? lo : shift;          // the window holds positions [from, hi) of the text = bytes [from - shift, hi - shift)
+    if (from >= hi) return;                                 // (uniform)
+    const uint64_t o0 = from - shift, o1 = hi - shift;
+    // l0: the last line that starts at or before o0; l1: the first line that starts at or behind o1 (off[0] = 0 < o1; a line has at least its '\n': the offsets
+    // increase strictly); r0, r1: the reads of lines l0 and l1 - 1 (lstart[0] = 0): every wave finds the four by itself, 64 probes per step
+    const uint64_t l0 = wave_search(off, lines, o0, false), l1 = wave_search(off, lines, o1, true) + 1;
+    const uint64_t r0 = wave_search(a.lstart, a.nq, l0, false), r1 = wave_search(a.lstart, a.nq, l1 - 1, false);
+    __syncthreads();
+    const Window w{lds, lo};
+    const uint64_t n = l1 - l0;
+    for (uint64_t base = 0; base < n; base += 256u) {
+        const uint64_t j = base + 4u * (threadIdx.x & 63u) + (threadIdx.x >> 6);      // consecutive lines go to the four waves in turn
+        const bool mine = j < n;
+        const uint8_t *seq = nullptr, *qual = nullptr;
+        uint32_t seq_len = 0, qual_len = 0, rev = 0;
+        uint64_t seq_at = 0, qual_at = 0;
+        if (mine) {
+            const uint64_t l = l0 + j;
+            const Line d = describe(a, l, r0, r1 + 1);
+            uint64_t at = off[l] + shift;
+            at = field_name(w, hi, at, d.rname, d.rn, !a.use_read_names, d.read);
+            at = field_decimal(w, at, d.flag, '\t');
+            if (d.mapped) { at = field_name(w, hi, at, d.sname, d.sn, !a.use_seq_names, d.rec.seq_id); at = field_decimal(w, at, d.rec.pos + 1, '\t'); }
+            else at = field_text(w, at, "*\t0\t", 4);
+            at = field_decimal(w, at, d.mapq, '\t');
+            if (d.star_cigar) at = field_text(w, at, "*\t", 2);
+            else { at = field_decimal(w, at, d.m, 'M'); w.put(at, '\t'); ++at; }
+            at = field_text(w, at, "*\t0\t0\t", 6);
+            rev = d.mapped && a.shift && (d.rec.qidx & 1u) ? 1u : 0u;
+            if (d.star_seq) { w.put(at, '*'); at += 1; } else { seq = d.q; seq_len = d.m; seq_at = at; at += d.m; }
+            w.put(at, '\t'); ++at;
+            if (d.star_qual) { w.put(at, '*'); at += 1; } else { qual = d.qual; qual_len = d.m; qual_at = at; at += d.m; }
+            if (d.mapped) {
+                at = field_text(w, at, "\tNM:i:", 6);
+                at = field_decimal(w, at, d.rec.errors, '\t');
+                at = field_text(w, at, "NH:i:", 5);
+                at = field_decimal(w, at, d.nh, '\n');
+            } else w.put(at, '\n');
+        }
+        put_run(w, hi, seq, seq_len, seq_at, rev, tab);
+        put_run(w, hi, qual, qual_len, qual_at, rev, nullptr);
+    }
+    __syncthreads();
+    const uint32_t pieces = (uint32_t)((hi - lo + 15u) / 16u);
+    for (uint32_t j = threadIdx.x; j < pieces; j += 256u) {
+        const uint64_t p0 = lo + 16u * j;
+        if (p0 >= from && p0 + 16u <= hi) *reinterpret_cast<uint4*>(gbase + p0) = *reinterpret_cast<const uint4*>(lds + 16u * j);
+        else for (uint32_t k = 0; k < 16u; ++k) if (p0 + k >= from && p0 + k < hi) gbase[p0 + k] = lds[16u * j + k];
+    }
+}
+
+struct Widen { __host__ __device__ uint64_t operator()(uint32_t v) const { return v; } };
+using Widened = hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*>;
+
+int check_table(const fmgpu_name_table* t, const char* which) {
+    if (!t) return 0;
+    if (!t->bytes && t->n_bytes) return fail(FMGPU_ERR_INVALID, std::string("fmgpu_sam_spec: the ") + which + " table has no bytes but n_bytes > 0");
+    if (!t->spans && t->count) return fail(FMGPU_ERR_INVALID, std::string("fmgpu_sam_spec: the ") + which + " table has no spans but count > 0");
+    return 0;
+}
+
+const char* const kBadText[] = {"", "names a row beyond the read_names table", "has a read name span that leaves the table's bytes", "names a row beyond the quals table",
+                                "has a quality span that leaves the table's bytes", "has a quality span whose len is neither 0 nor the read's length",
+                                "names a row beyond the seq_names table", "has a sequence name span that leaves the table's bytes"};
+const char* const kLongText[] = {"", "is a read of 2^31 symbols or more", "has a name or quality span of 2^31 bytes or more", "makes a line of 2^32 bytes or more"};
+
+}  // namespace
+}  // namespace fmgpu
+
+using namespace fmgpu;
+
+extern "C" {
+
+int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const fmgpu_sam_spec* spec, uint8_t* out, uint64_t capacity, uint64_t* out_bytes,
+                        uint64_t* out_line_off, uint64_t* out_lines, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!spec) return fail(FMGPU_ERR_INVALID, "fmgpu_positions_sam: spec is null");
+    if (!spec->char_of) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: char_of is null");
+    if (!out_bytes) return fail(FMGPU_ERR_INVALID, "fmgpu_positions_sam: out_bytes is null");
+    const uint64_t nq = spec->nq;
+    if (nq && !spec->qbuf) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: qbuf is null while nq > 0");
+    if (nq && !spec->qoff) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: qoff is null while nq > 0");
+    if (count && !positions) return fail(FMGPU_ERR_INVALID, "fmgpu_positions_sam: positions is null while count > 0");
+    if (!out && capacity) return fail(FMGPU_ERR_INVALID, "fmgpu_positions_sam: out is null while capacity > 0");
+    if (spec->cigar > 1) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: cigar must be 0 or 1");
+    if (spec->emit_unmapped > 1) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: emit_unmapped must be 0 or 1");
+    if (spec->secondary_seq > 1) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: secondary_seq must be 0 or 1");
+    if (spec->reserved[0] || spec->reserved[1] || spec->reserved[2]) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: reserved must be 0");
+    if (spec->strands && !spec->strands->complement) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: strands has a null complement");
+    if (spec->strands && (spec->strands->n < 1 || spec->strands->n > 256)) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: strands->n must be in [1, 256]");
+    int rc;
+    if ((rc = check_table(spec->read_names, "read_names")) || (rc = check_table(spec->quals, "quals")) || (rc = check_table(spec->seq_names, "seq_names"))) return rc;
+    *out_bytes = 0;
+    if (out_lines) *out_lines = 0;
+    const uint64_t bound = count + (spec->emit_unmapped ? nq : 0);
+    if (count >= kMaxSamLines || nq >= kMaxSamLines || bound >= kMaxSamLines)
+        return fail(FMGPU_ERR_UNSUPPORTED, "fmgpu_positions_sam: count, nq and count + (emit_unmapped ? nq : 0), the bound on the lines, must each stay below 2^32 - 256");
+    if (bound == 0) {                                               // no line
+        if (!out_line_off) return 0;
+        if (!is_device_pointer(out_line_off)) { out_line_off[0] = 0; return 0; }
+        FM_HIP(hipMemsetAsync(out_line_off, 0, 8, stream));
+        FM_HIP(hipStreamSynchronize(stream));
+        return 0;
+    }
+
+    SamArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.count = count; a.nq = nq; a.bound = bound;
+    a.shift = spec->strands ? 1 : 0;
+    a.cigar = spec->cigar; a.emit_unmapped = spec->emit_unmapped; a.secondary_seq = spec->secondary_seq;
+    a.mapq_unique = spec->mapq_unique; a.mapq_multi = spec->mapq_multi;
+    uint8_t tables[512], comp[256];
+    for (int c = 0; c < 256; ++c) comp[c] = (uint8_t)c;
+    if (spec->strands) strands_table(spec->strands->complement, spec->strands->n, comp);
+    for (int c = 0; c < 256; ++c) { tables[c] = spec->char_of[c]; tables[256 + c] = spec->char_of[comp[c]]; }
+
+    Staged spos, soff, sq, sbytes[3], sspans[3], sout;
+    if ((rc = spos.in(positions, count * sizeof(fmgpu_position), stream))) return rc;
+    if (nq && (rc = soff.in(spec->qoff, (nq + 1) * 8, stream))) return rc;
+    const fmgpu_name_table* tabs[3] = {spec->read_names, spec->quals, spec->seq_names};
+    SamTable* dst[3] = {&a.read_names, &a.quals, &a.seq_names};
+    for (int k = 0; k < 3; ++k) {
+        if (!tabs[k]) continue;
+        if ((rc = sbytes[k].in(tabs[k]->bytes, tabs[k]->n_bytes, stream)) || (rc = sspans[k].in(tabs[k]->spans, tabs[k]->count * sizeof(fmgpu_text_span), stream))) return rc;
+        *dst[k] = SamTable{(const uint8_t*)sbytes[k].dev, tabs[k]->n_bytes, (const fmgpu_text_span*)sspans[k].dev, tabs[k]->count};
+    }
+    a.use_read_names = spec->read_names != nullptr; a.use_quals = spec->quals != nullptr; a.use_seq_names = spec->seq_names != nullptr;
+    a.pos = (const fmgpu_position*)spos.dev;
+    a.aligned16 = (reinterpret_cast<uintptr_t>(a.pos) & 15u) == 0;
+    a.qoff = (const uint64_t*)soff.dev;
+
+    // per read: key, lstart (8 bytes each), first, end, nmin, lcount (4 bytes each), one entry more than reads; per line of the bound: the offset and the length
+    DBuf reads, lens, off, tmp, small;
+    if ((rc = reads.alloc((nq + 1) * 32)) || (rc = lens.alloc((bound + 1) * 4)) || (rc = off.alloc((bound + 1 + E_WORDS) * 8)) || (rc = small.alloc(512 + 16))) return rc;
+    a.key = reads.as<unsigned long long>();
+    a.lstart = reads.as<uint64_t>() + (nq + 1);
+    a.first = reinterpret_cast<uint32_t*>(a.lstart + (nq + 1));
+    a.end = a.first + (nq + 1); a.nmin = a.end + (nq + 1); a.lcount = a.nmin + (nq + 1);
+    uint64_t* const doff = off.as<uint64_t>();
+    a.err = reinterpret_cast<unsigned long long*>(doff + bound + 1);
+    FM_HIP(hipMemcpyAsync(small.p, tables, 512, hipMemcpyHostToDevice, stream));
+    FM_HIP(hipMemsetAsync(a.key, 0xff, (nq + 1) * 8, stream));
+    FM_HIP(hipMemsetAsync(a.first, 0xff, (nq + 1) * 4, stream));
+    FM_HIP(hipMemsetAsync(a.nmin, 0, (nq + 1) * 4, stream));
+    FM_HIP(hipMemsetAsync(a.err, 0xff, E_WORDS * 8, stream));
+
+    Widened lcounts(a.lcount, Widen{}), lengths(lens.as<uint32_t>(), Widen{});
+    size_t tb1 = 0, tb2 = 0;
+    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, lcounts, a.lstart, (size_t)(nq + 1), stream));
+    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, lengths, doff, (size_t)(bound + 1), stream));
+    if ((rc = tmp.alloc(tb1 > tb2 ? tb1 : tb2))) return rc;
+    if (count) {
+        FM_GRID(rgrid, count);
+        k_sam_records<<<rgrid, dim3(256), 0, stream>>>(a);
+        FM_LAUNCHED("k_sam_records");
+        k_sam_count<<<rgrid, dim3(256), 0, stream>>>(a);
+        FM_LAUNCHED("k_sam_count");
+    }
+    FM_GRID(qgrid, nq + 1);
+    k_sam_reads<<<qgrid, dim3(256), 0, stream>>>(a);
+    FM_LAUNCHED("k_sam_reads");
+    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb1, lcounts, a.lstart, (size_t)(nq + 1), stream));
+    FM_GRID(mgrid, bound + 1);
+    k_sam_measure<<<mgrid, dim3(256), 0, stream>>>(a, lens.as<uint32_t>());
+    FM_LAUNCHED("k_sam_measure");
+    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb2, lengths, doff, (size_t)(bound + 1), stream));
+    uint64_t back[1 + E_WORDS];                                     // the size of the text, the error words, the number of lines: the call's one read-back
+    FM_HIP(hipMemcpyAsync(back, doff + bound, sizeof back, hipMemcpyDeviceToHost, stream));
+    FM_HIP(hipStreamSynchronize(stream));
+    const uint64_t* err = back + 1;
+    if (err[E_RANGE] != kNone) return fail(FMGPU_ERR_INVALID, "fmgpu_positions_sam: record " + std::to_string(err[E_RANGE]) + " names a read >= nq");
+    if (err[E_ORDER] != kNone) return fail(FMGPU_ERR_INVALID, "fmgpu_positions_sam: record " + std::to_string(err[E_ORDER]) + " names a read below its predecessor's");
+    if (err[E_QOFF] != kNone) return fail(FMGPU_ERR_INVALID, "fmgpu_positions_sam: read " + std::to_string(err[E_QOFF]) + " has a qoff above its successor's");
+    if (err[E_LINE] != kNone || err[E_LONG] != kNone) {
+        const bool invalid = err[E_LINE] != kNone;
+        const uint64_t word = invalid ? err[E_LINE] : err[E_LONG];
+        uint64_t* const where = reinterpret_cast<uint64_t*>(small.as<uint8_t>() + 512);
+        uint64_t who[2] = {0, 0};
+        k_sam_explain<<<dim3(1), dim3(1), 0, stream>>>(a, word >> 8, where);
+        FM_LAUNCHED("k_sam_explain");
+        FM_HIP(hipMemcpyAsync(who, where, 16, hipMemcpyDeviceToHost, stream));
+        FM_HIP(hipStreamSynchronize(stream));
+        const std::string name = who[1] != kNone ? "record " + std::to_string(who[1]) : "unmapped read " + std::to_string(who[0]);
+        return fail(invalid ? FMGPU_ERR_INVALID : FMGPU_ERR_UNSUPPORTED, "fmgpu_positions_sam: " + name + " " + (invalid ? kBadText : kLongText)[word & 255u]);
+    }
+    const uint64_t total = back[0], lines = err[E_LINES];
+    *out_bytes = total;
+    if (out_lines) *out_lines = lines;
+    if (out_line_off) FM_HIP(hipMemcpyAsync(out_line_off, doff, (lines + 1) * 8, hipMemcpyDefault, stream));
+    if (!out && !capacity) { FM_HIP(hipStreamSynchronize(stream)); return 0; }
+    if (total > capacity) {
+        FM_HIP(hipStreamSynchronize(stream));
+        return fail(FMGPU_ERR_CAPACITY, "the text takes " + std::to_string(total) + " bytes: more than `capacity`");
+    }
+    if (!total) { FM_HIP(hipStreamSynchronize(stream)); return 0; }
+    uint64_t symbols = 0;                                           // the offsets do not decrease: the batch ends at qoff[nq]
+    FM_HIP(hipMemcpyAsync(&symbols, a.qoff + nq, 8, hipMemcpyDeviceToHost, stream));
+    FM_HIP(hipStreamSynchronize(stream));
+    if ((rc = sq.in(spec->qbuf, symbols, stream))) return rc;
+    a.qbuf = sq.dev ? (const uint8_t*)sq.dev : spec->qbuf;          // (a batch without a symbol: the pointer is never read through)
+    if ((rc = sout.out(out, total, stream))) { (void)hipStreamSynchronize(stream); return rc; }
+    uint8_t* const dout = (uint8_t*)sout.dev;
+    const uint64_t windows = ((reinterpret_cast<uintptr_t>(dout) & 15u) + total + kSamWindow - 1) / kSamWindow;
+    FM_GRID(wgrid, windows * 256);
+    k_sam_write<<<wgrid, dim3(256), 0, stream>>>(a, small.as<uint8_t>(), doff, lines, total, dout);
+    FM_LAUNCHED("k_sam_write");
+    if ((rc = sout.finish())) return rc;
+    FM_HIP(hipStreamSynchronize(stream));
+    return 0;
+}
+
+int fmgpu_sam_header(const fmgpu_name_table* seq_names, const uint64_t* seq_lengths, uint64_t nseq, const char* program_id, uint8_t* out, uint64_t capacity,
+                     uint64_t* out_bytes) {
+    if (!out_bytes) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_header: out_bytes is null");
+    if (!out && capacity) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_header: out is null while capacity > 0");
+    if (nseq && !seq_names) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_header: seq_names is null while nseq > 0");
+    if (nseq && !seq_lengths) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_header: seq_lengths is null while nseq > 0");
+    if (nseq && (seq_names->count < nseq || !seq_names->spans || (!seq_names->bytes && seq_names->n_bytes)))
+        return fail(FMGPU_ERR_INVALID, "fmgpu_sam_header: seq_names holds fewer than nseq rows");
+    std::string text = "@HD\tVN:1.6\tSO:unknown\n";
+    for (uint64_t s = 0; s < nseq; ++s) {
+        const uint64_t o = seq_names->spans[s].offset, n = seq_names->spans[s].len;
+        if (n > seq_names->n_bytes || o > seq_names->n_bytes - n) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_header: sequence " + std::to_string(s) + " has a name span that leaves the table's bytes");
+        uint64_t m = 0;
+        while (m < n && seq_names->bytes[o + m] != ' ' && seq_names->bytes[o + m] != '\t') ++m;
+        if (!m) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_header: sequence " + std::to_string(s) + " has an empty name");
+        text += "@SQ\tSN:";
+        text.append(reinterpret_cast<const char*>(seq_names->bytes + o), m);
+        text += "\tLN:" + std::to_string(seq_lengths[s]) + "\n";
+    }
+    if (program_id) text += std::string("@PG\tID:") + program_id + "\n";
+    *out_bytes = text.size();
+    if (!out && !capacity) return 0;
+    if (text.size() > capacity) return fail(FMGPU_ERR_CAPACITY, "the header takes " + std::to_string(text.size()) + " bytes: more than `capacity`");
+    std::memcpy(out, text.data(), text.size());
+    return 0;
+}
+
+}  // extern "C"

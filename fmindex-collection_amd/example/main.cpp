@@ -26,6 +26,11 @@
 //   * --device-format (not in the reference; --mode map): the --save_output file is formatted on the device (fmgpu_positions_format through fmc::formatPositions) instead
 //     of by the fprintf loop.  The file is the same, byte for byte.  fmc::map returns host vectors, so the records are staged up again for it: this flag proves that
 //     the two writers agree, not that one is faster (tools/format_probe.py measures that on records that are resident on the device).
+//   * --sam (not in the reference; --mode map, not --packed): the --save_output file is a SAM file: the header (fmgpu_sam_header through fmc::samHeader: one @SQ line
+//     per sequence of --index, named up to its first blank) followed by the records made on the device (fmgpu_positions_sam through fmc::formatSam) from the positions
+//     and the searched batch.  QNAME is the read's number in that batch and QUAL is '*' (the default reader keeps neither names nor qualities); CIGAR is "<m>M" for
+//     noerror and '*' otherwise (the ladders of this harness are edit-distance searches).  With --pair-strands a read and its reverse complement are one read (flag 16);
+//     without it every read of the searched batch, the reverse complements the harness appends included, is a read of its own.
 //   * --device-parse (not in the reference): the --query file is read as bytes and parsed on the device (fmgpu_queries_parse through fmc::parseQueries); its first byte
 //     chooses FASTA ('>') or FASTQ ('@', read only this way).  On a well-formed FASTA — ends in a newline, no '>' inside sequence lines, no '\r' — the output is the
 //     same, byte for byte.  Elsewhere the device rules differ from the reader below: a '\r' in front of a newline belongs to the line end (the reader takes it for
@@ -61,7 +66,7 @@ struct Options {
     bool schemeDyn = false;
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false;
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false, sam = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -106,6 +111,7 @@ FlagRule const kFlags[] = {
     {"--device-parse", false, [](Options& o, char const*) { o.deviceParse = true; }},
     {"--pair-strands", false, [](Options& o, char const*) { o.pairStrands = true; }},
     {"--device-format", false, [](Options& o, char const*) { o.deviceFormat = true; }},
+    {"--sam", false, [](Options& o, char const*) { o.sam = true; }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
     {"--ext", true, [](Options&, char const*) {}},
     {"--threads", true, [](Options&, char const*) {}},
@@ -189,6 +195,28 @@ std::vector<std::vector<uint8_t>> readQueriesOnDevice(std::string const& path, s
     return records;
 }
 
+// --sam: the names of the sequences of a FASTA file, by the reader's rules above (a name line starts a record only if a sequence part follows it), without the
+// blanks in front of them
+std::vector<std::string> readFastaNames(std::string const& path) {
+    std::vector<std::string> names;
+    std::ifstream in{path, std::ios::binary};
+    std::string const bytes{std::istreambuf_iterator<char>{in}, std::istreambuf_iterator<char>{}};
+    size_t const size = bytes.size();
+    size_t at = 0;
+    while (at < size) {
+        size_t const from = at + 1;
+        while (at < size && bytes[at] != '\n') ++at;
+        std::string name = bytes.substr(std::min(from, at), at - std::min(from, at));
+        name.erase(0, name.find_first_not_of(" \t"));
+        ++at;
+        if (at >= size) break;
+        names.push_back(name);
+        while (at + 1 < size && bytes[at] != '>') ++at;
+        if (at + 1 >= size) break;
+    }
+    return names;
+}
+
 // every read followed by its reverse complement (A <-> T, C <-> G; other ranks stay)
 std::vector<std::vector<uint8_t>> withReverseComplements(std::vector<std::vector<uint8_t>> const& reads) {
     static uint8_t const complement[6] = {0, 4, 3, 2, 1, 5};
@@ -266,6 +294,8 @@ struct Placement {
 struct Run {
     Options const& config;
     Index index;
+    fmc::NameTable referenceNames{};                             // --sam: the names and lengths of the sequences of --index
+    std::vector<uint64_t> referenceLengths{};
 
     // a scheme stretched to the read length: uniformly, or (--gen <name>_dyn) part by part where the weighted node count grows least — with the constants
     // the reference's example passes (src/example/main.cpp:116, :135: Edit = true, sigma 4, 3e9 rows)
@@ -354,7 +384,10 @@ struct Run {
             for (size_t j = 0; j <= k; ++j) query.expanded.push_back(stretch(schemeByName(config.schemeName, j, j), firstLength));
         }
         auto const mapped = config.feed ? mapThroughFeed(reads, query) : mapAtOnce(reads, query);
-        reportMapped(mapped, (config.pairStrands ? 2 : 1) * reads.size(), k, clock.reset());
+        double const tMap = clock.reset();
+        std::string sam;
+        if constexpr (!std::is_same_v<Queries, fmc::PackedQueries>) if (config.sam && !config.outputFile.empty()) sam = samFile(mapped, reads, kind == Algorithm::noerror);
+        reportMapped(mapped, (config.pairStrands ? 2 : 1) * reads.size(), k, tMap, sam);
     }
 
     // --mode map --feed --device-parse without reverse complements: the bytes of the query file go through the feed as they are (fmgpu_feed_map_text through
@@ -372,10 +405,26 @@ struct Run {
         auto const mapped = config.pairStrands ? fmc::Feed{index}.mapText(std::string_view{text}, format, table, query, pairStrands())
                                                : fmc::Feed{index}.mapText(std::string_view{text}, format, table, query);
         if (mapped.foreign > 0) throw std::runtime_error("unknown alphabet");
-        reportMapped(mapped, (config.pairStrands ? 2 : 1) * mapped.size(), k, clock.reset());
+        double const tMap = clock.reset();
+        std::string sam;                                                // (the records need the reads: the text is parsed once more)
+        if (config.sam && !config.outputFile.empty()) sam = samFile(mapped, fmc::parseQueries(text, format, table), kind == Algorithm::noerror);
+        reportMapped(mapped, (config.pairStrands ? 2 : 1) * mapped.size(), k, tMap, sam);
     }
 
-    void reportMapped(fmc::MapResult const& mapped, size_t nreads, size_t k, double tMap) const {
+    // --sam: the header and the records of the batch that was searched
+    template <typename Queries>
+    std::string samFile(fmc::MapResult const& mapped, Queries const& reads, bool ungapped) const {
+        auto const strands = pairStrands();
+        fmc::SamSpec spec;
+        if (config.pairStrands) spec.strands = &strands;
+        spec.seqNames = &referenceNames;
+        spec.cigar = ungapped;
+        auto records = mapped.positions;
+        for (auto& p : records) p.seq_id = static_cast<uint32_t>(p.seq_id);           // (what the other files print of it)
+        return fmc::samHeader(referenceNames, referenceLengths, "fmindex-collection-gpu-example") + fmc::formatSam(records, reads, spec).text;
+    }
+
+    void reportMapped(fmc::MapResult const& mapped, size_t nreads, size_t k, double tMap, std::string const& sam = {}) const {
         struct { size_t n; size_t size() const { return n; } } const reads{nreads};
         std::vector<Placement> distinct;
         distinct.reserve(mapped.positions.size());
@@ -389,7 +438,9 @@ struct Run {
         if (config.outputFile.empty()) return;
         auto* out = std::fopen(config.outputFile.c_str(), "w");
         if (!out) throw std::runtime_error("cannot write " + config.outputFile);
-        if (config.deviceFormat) {                                      // the same lines made on the device (the default FormatSpec: qidx seq_id pos errors)
+        if (config.sam) {
+            if (std::fwrite(sam.data(), 1, sam.size(), out) != sam.size()) { std::fclose(out); throw std::runtime_error("cannot write " + config.outputFile); }
+        } else if (config.deviceFormat) {                               // the same lines made on the device (the default FormatSpec: qidx seq_id pos errors)
             auto records = mapped.positions;
             for (auto& p : records) p.seq_id = static_cast<uint32_t>(p.seq_id);       // (what the loop below prints of it)
             auto const text = fmc::formatPositions(records);
@@ -455,12 +506,22 @@ int main(int argc, char const* const* argv) try {
                     "          --pair-strands (--mode map: reverse complements made on the device, best stratum per read: once either strand of a\\\n"
                     "                 read is found, neither is searched with more errors; queryId = 2 * read + strand)\\\n"
                     "          --device-format (--mode map: the --save_output file is formatted on the device; the same file, byte for byte)\\\n"
+                    "          --sam (--mode map, not --packed: the --save_output file is a SAM file, the header and the records made on the device;\\\n"
+                    "                 QNAME = the read's number in the searched batch, with --pair-strands one read for both strands)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }
     bool const needsFirstLength = std::any_of(config.algorithms.begin(), config.algorithms.end(), [](auto const& a) { return algorithmByName(a) == Algorithm::ng21; });
     if (config.pairStrands && (config.hitMode != HitMode::map || config.packed)) throw std::runtime_error("--pair-strands needs --mode map and byte reads (no --packed)");
     if (config.deviceFormat && config.hitMode != HitMode::map) throw std::runtime_error("--device-format needs --mode map");
+    if (config.sam && (config.hitMode != HitMode::map || config.packed || config.deviceFormat)) throw std::runtime_error("--sam needs --mode map, byte reads (no --packed) and no --device-format");
+    auto withReference = [&](Run& run) {                              // --sam: what the header and RNAME are made of
+        if (!config.sam) return;
+        auto const reference = readFasta(config.referenceFasta, Sigma, config.unknownToA);
+        run.referenceNames = fmc::NameTable{readFastaNames(config.referenceFasta)};
+        for (auto const& s : reference) run.referenceLengths.push_back(s.size());
+        if (run.referenceNames.spans.size() != run.referenceLengths.size()) throw std::runtime_error("--sam: the names and the sequences of --index do not pair up");
+    };
     if (config.hitMode == HitMode::map && config.feed && config.deviceParse && (!config.withReverseComplement || config.pairStrands) && !config.packed && config.readLimit == 0 &&
         config.trimTo == 0 && !needsFirstLength && !config.readsFasta.empty() && std::filesystem::exists(config.readsFasta)) {
         std::ifstream in{config.readsFasta, std::ios::binary};
@@ -468,6 +529,7 @@ int main(int argc, char const* const* argv) try {
         if (text.empty() || (text[0] != '>' && text[0] != '@')) throw std::runtime_error("can't read fasta file");
         std::printf("loaded %zu bytes of query text\n", text.size());
         Run run{config, openIndex(config)};
+        withReference(run);
         for (auto const& algorithm : config.algorithms) {
             std::printf("using algorithm %s\n", algorithm.c_str());
             for (size_t k = config.firstK; k <= config.lastK; k += config.stepK) run.oneErrorBudgetMappedText(algorithmByName(algorithm), k, text);
@@ -487,6 +549,7 @@ int main(int argc, char const* const* argv) try {
                     "time_locate", "(time_search+time_locate)/queries.size()", "resultCt", "results.size()", "uniqueResults.size()", "readIds.size()", "memory");
     }
     Run run{config, openIndex(config)};
+    withReference(run);
     size_t const limit = config.readLimit != 0 ? config.readLimit : std::numeric_limits<size_t>::max();     // (of the doubled batch)
     if (strands * reads.size() > limit) reads.resize((limit + strands - 1) / strands);
     if (config.trimTo != 0) for (auto& r : reads) if (r.size() > config.trimTo) r.resize(config.trimTo);

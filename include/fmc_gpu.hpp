@@ -1353,6 +1353,68 @@ inline auto formatPositions(std::vector<fmgpu_position> const& positions, Format
     return text;
 }
 
+// Positions as SAM (include/fmgpu.h: fmgpu_positions_sam, fmgpu_sam_header): fmc::formatSam(positions, reads, spec) is the alignment lines of the positions fmc::map
+// returned for `reads` (the FORWARD batch: any range of reads, a ParsedQueries among them), formatted on the device; fmc::samHeader(names, lengths, program) is the
+// header in front of them.  spec.strands = the Strands the reads were mapped with (qidx counts both strands; an odd one is written reversed and complemented with flag
+// 16).  Without a table QNAME and RNAME are numbers and QUAL is '*'.  cigar = true states that the search was ungapped: "<m>M".
+struct CharTable {
+    std::array<uint8_t, 256> map;
+    // value firstRank + i -> letters[i], every other value (255, the Foreign symbol, among them) -> other
+    explicit CharTable(std::string_view letters = "ACGT", uint8_t firstRank = 1, char other = 'N') {
+        map.fill(static_cast<uint8_t>(other));
+        for (size_t i = 0; i < letters.size(); ++i) map[firstRank + i] = static_cast<uint8_t>(letters[i]);
+    }
+    auto set(uint8_t value, char byte) -> CharTable& { map[value] = static_cast<uint8_t>(byte); return *this; }
+    static auto dna5() -> CharTable { return CharTable{}.set(0, '$'); }       // the inverse of SymbolTable::dna5()
+};
+struct SamSpec {
+    CharTable        charOf{CharTable::dna5()};
+    Strands const*   strands{nullptr};
+    NameTable const* readNames{nullptr};
+    NameTable const* quals{nullptr};
+    NameTable const* seqNames{nullptr};
+    bool    cigar{true};
+    bool    emitUnmapped{true};
+    bool    secondarySeq{false};
+    uint8_t mapqUnique{60}, mapqMulti{0};
+};
+struct SamText {
+    std::string           text;
+    std::vector<uint64_t> lineOffsets;                                       // lines + 1 entries where asked for, else empty
+};
+template <typename Queries>
+auto formatSam(std::vector<fmgpu_position> const& positions, Queries const& reads, SamSpec const& spec = {}, bool wantLineOffsets = false) -> SamText {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(reads, buf, off);
+    fmgpu_sam_spec s{};
+    s.qbuf = buf.data(); s.qoff = off.data(); s.nq = off.size() - 1; s.char_of = spec.charOf.map.data();
+    fmgpu_strands st{};
+    fmgpu_name_table rt{}, qt{}, nt{};
+    if (spec.strands) { st = spec.strands->c(); s.strands = &st; }
+    if (spec.readNames) { rt = spec.readNames->c(); s.read_names = &rt; }
+    if (spec.quals) { qt = spec.quals->c(); s.quals = &qt; }
+    if (spec.seqNames) { nt = spec.seqNames->c(); s.seq_names = &nt; }
+    s.cigar = spec.cigar ? 1 : 0; s.emit_unmapped = spec.emitUnmapped ? 1 : 0; s.secondary_seq = spec.secondarySeq ? 1 : 0;
+    s.mapq_unique = spec.mapqUnique; s.mapq_multi = spec.mapqMulti;
+    uint64_t bytes = 0, lines = 0;
+    detail::check(fmgpu_positions_sam(positions.data(), positions.size(), &s, nullptr, 0, &bytes, nullptr, &lines, nullptr));        // the counting call sizes the text exactly
+    SamText out;
+    out.text.assign(bytes, '\0');
+    if (wantLineOffsets) out.lineOffsets.assign(lines + 1, 0);
+    if (bytes) detail::check(fmgpu_positions_sam(positions.data(), positions.size(), &s, reinterpret_cast<uint8_t*>(out.text.data()), bytes, &bytes,
+                                                 wantLineOffsets ? out.lineOffsets.data() : nullptr, &lines, nullptr));
+    return out;
+}
+inline auto samHeader(NameTable const& seqNames, std::vector<uint64_t> const& lengths, char const* program = nullptr) -> std::string {
+    if (seqNames.spans.size() < lengths.size()) throw std::runtime_error("fmindex-collection (gpu): a name per sequence length");
+    fmgpu_name_table const t = seqNames.c();
+    uint64_t bytes = 0;
+    detail::check(fmgpu_sam_header(&t, lengths.data(), lengths.size(), program, nullptr, 0, &bytes));
+    std::string text(bytes, '\0');
+    detail::check(fmgpu_sam_header(&t, lengths.data(), lengths.size(), program, reinterpret_cast<uint8_t*>(text.data()), bytes, &bytes));
+    return text;
+}
+
 // A feed (include/fmgpu.h: fmgpu_feed_*): host batches searched chunk by chunk on one index, upload, search and download overlapped.  What a caller that holds its
 // queries in host memory — the reference's Sequences — should search through: `fmc::Feed feed{index}; feed.search_no_errors(queries, delegate);`.  A Sequences object
 // (reads of one-byte symbols, each contiguous) goes down through the `_v` calls without being flattened, a PackedQueries through `_q4`.  The delegates are called as by

@@ -946,7 +946,7 @@ int fmgpu_feed_map_text_strands(fmgpu_feed_t f, const uint8_t* text, uint64_t by
  *     alignment: the text leaves in 16-byte stores aligned to the output address, and only the first and last bytes of a workgroup's range are stored byte by byte.
  *   - Three passes (measure, hipcub exclusive scan, write) and one read-back: the size of the text and the error words together.  The call returns after completion and
  *     frees its scratch of 12 bytes per record (a 4-byte length, an 8-byte offset) plus the scan's own.
- * Not built: SAM / PAF records as such, text per chunk inside fmgpu_map or the feeds, fmgpu_hit records or seed spans as text, compressed output, columns from a caller's arrays. */
+ * Not built: PAF records (SAM records: fmgpu_positions_sam below), text per chunk inside fmgpu_map or the feeds, fmgpu_hit records or seed spans as text, compressed output, columns from a caller's arrays. */
 #define FMGPU_COL_QIDX      0   /* qidx, decimal */
 #define FMGPU_COL_SEQ_ID    1   /* seq_id, decimal */
 #define FMGPU_COL_POS       2   /* pos + spec->pos_add, decimal (wraps mod 2^64) */
@@ -975,6 +975,69 @@ typedef struct fmgpu_format_spec {         /* 40 bytes, host memory */
 } fmgpu_format_spec;
 int fmgpu_positions_format(const fmgpu_position* positions, uint64_t count, const fmgpu_format_spec* spec,
                            uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* out_line_off, void* stream);
+
+/* ---- positions to SAM: located hits as SAM records on the device -------------------------------------------------------------------------------
+ * fmgpu_positions_sam writes the positions of fmgpu_map* as SAM alignment lines; fmgpu_sam_header (host code) writes the header in front of them.  Nothing is aligned
+ * here: the searches most callers run are ungapped (exact search, Hamming schemes, fmgpu_search_hamming_sm), so their CIGAR is "<m>M"; for edit-distance hits SAM allows
+ * '*'.  SEQ comes from the query batch the caller holds, QUAL from the spans fmgpu_queries_parse returns, FLAG from the both-strand numbering, MAPQ and NH from counts.
+ *   - Input order: `positions` is what fmgpu_map* returns: the read number (qidx >> shift; shift = 1 with spec->strands, else 0) does not decrease over the records.
+ *     cnt[r] = the number of records of read r.
+ *   - Output order: reads ascending; a read with records gets one line per record, in record order; a read without records gets one unmapped line iff emit_unmapped.
+ *     *out_lines (may be NULL) = the number of lines.  out_line_off: NULL, or *out_lines + 1 entries (size it for the bound count + nq + 1): the byte offset of every
+ *     line, the last entry = *out_bytes; written whenever the call gets past its checks, also on FMGPU_ERR_CAPACITY.
+ *   - Mapped line, tabs between the fields and '\n' behind the last: QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL NM:i:<errors> NH:i:<cnt[r]>
+ *     Unmapped line: QNAME 4 * 0 0 * * 0 0 SEQ QUAL, with SEQ and QUAL of the forward read.
+ *   - The primary record of a read is the one with the fewest errors, the lowest record index among equals.  FLAG = (strand ? 16 : 0) | (not the primary ? 256 : 0).
+ *     MAPQ: the primary record gets mapq_unique if it is the read's only record with the minimal errors, else mapq_multi; every secondary record gets mapq_multi.
+ *   - POS = pos + 1 (mod 2^64).  CIGAR = m in decimal and 'M' if cigar == 1 and the read's length m > 0, else '*'.
+ *   - QNAME = row `read` of read_names, RNAME = row seq_id of seq_names: the name up to its first ' ' or '\t'; an empty result is written as '*'.  Without the table:
+ *     the read number, or seq_id, in decimal.
+ *   - SEQ: strand 0: byte j = char_of[q[j]]; strand 1: byte j = char_of[comp(q[m - 1 - j])] with comp(c) = complement[c] for c < n, c otherwise (the rule of
+ *     fmgpu_queries_strands).  m = 0 gives '*'; so does a secondary record unless secondary_seq.
+ *   - QUAL: '*' if quals is NULL, if the span's len is 0 or if SEQ is '*'; else the bytes of row `read` of quals, reversed for strand 1.
+ *   - *out_bytes and *out_lines are exact, on success and on FMGPU_ERR_CAPACITY alike (then nothing is written to `out`); out == NULL with capacity == 0 is the counting
+ *     call.  Without a line (count == 0 and either nq == 0 or emit_unmapped == 0) the call returns 0 behind its argument checks and size limits with zero counts and out_line_off[0] = 0;
+ *     count == 0 with emit_unmapped = 1 writes nq unmapped lines.
+ *   - Before the first use of the device, FMGPU_ERR_INVALID, each with a message of its own, for: a null spec, char_of or out_bytes; a null qbuf or qoff while nq > 0;
+ *     null positions while count > 0; a null out while capacity > 0; cigar, emit_unmapped or secondary_seq outside 0 .. 1; reserved != 0; a strands with a null complement
+ *     or n outside 1 .. 256; a table with a null bytes while n_bytes > 0 or a null spans while count > 0.  Then FMGPU_ERR_UNSUPPORTED where count, nq or
+ *     count + (emit_unmapped ? nq : 0), the bound on the lines, reaches 2^32 - 256 (records and reads are numbered in 32 bits; this comes before the call looks whether
+ *     there is a line at all).
+ *   - On the device, FMGPU_ERR_INVALID, looked for in this order; nothing is written (out_line_off neither) and the message names the lowest offender: a record whose
+ *     read number is >= nq; a record whose read number lies below its predecessor's; a read r with qoff[r + 1] < qoff[r] ("read r"); then, per line in line order and
+ *     inside a line in this order: a read_names row beyond its table or a span beyond its bytes, the same for quals, a quality span whose len is neither 0 nor m, the
+ *     same two for seq_names.  The line is named by its record ("record i"), an unmapped line by its read ("unmapped read r").  A read of 2^31 symbols or more, a name
+ *     or quality span of 2^31 bytes or more, or a line of 2^32 bytes or more returns FMGPU_ERR_UNSUPPORTED in the same way; an FMGPU_ERR_INVALID line anywhere goes first.
+ *   - Every buffer (positions, qbuf, qoff, out, out_line_off, the bytes and spans of each table) may be host or device memory; host buffers are staged (qbuf: its first
+ *     qoff[nq] bytes).  The spec, char_of and complement are host memory.  A device `out` needs no alignment: the text is cut into windows of 16 KiB aligned to 16 bytes
+ *     of the output address, one per workgroup, which leave as aligned 16-byte stores; only the first and last bytes of the text are stored byte by byte.
+ *   - Passes: per record (order, range, each read's records and primary), per record (records at the minimum), per read (offsets, lines), a scan to each read's first
+ *     line, per line (length, names and spans), a scan to 64-bit offsets, ONE read-back (size, lines, error words), the write pass.  The call returns after completion and
+ *     frees its scratch: 32 bytes per read and 12 bytes per line of the bound count + (emit_unmapped ? nq : 0), plus the scans' own.
+ * fmgpu_sam_header: "@HD\tVN:1.6\tSO:unknown\n", one "@SQ\tSN:<name up to its first blank>\tLN:<length>\n" per sequence, and "@PG\tID:<program_id>\n" if program_id
+ * is not NULL.  Host memory only, no device.  The counting and capacity rule above.  FMGPU_ERR_INVALID for a null out_bytes, a null out while capacity > 0, a null
+ * seq_names or seq_lengths while nseq > 0, a table of fewer than nseq rows, a span beyond the table's bytes, an empty SN.
+ * Not built: PAF, CIGAR for edit-distance hits, mate fields (RNEXT, PNEXT, TLEN stay * 0 0), SAM text per chunk inside fmgpu_map or the feeds, BAM or compression. */
+typedef struct fmgpu_sam_spec {            /* 72 bytes, host memory */
+    const uint8_t*  qbuf;                  /* the FORWARD batch the positions were mapped from; host or device */
+    const uint64_t* qoff;                  /* nq + 1 entries, qoff[0] need not be 0 */
+    uint64_t        nq;
+    const uint8_t*  char_of;               /* host, 256 entries: the SEQ byte of symbol value c (255 -> 'N' is the caller's choice) */
+    const fmgpu_strands* strands;          /* NULL: read = qidx.  Else read = qidx >> 1, strand = qidx & 1; `pair` is ignored */
+    const fmgpu_name_table* read_names;    /* NULL: QNAME = the read number in decimal */
+    const fmgpu_name_table* quals;         /* NULL: QUAL = '*' */
+    const fmgpu_name_table* seq_names;     /* NULL: RNAME = seq_id in decimal */
+    uint8_t cigar;                         /* 0: '*';  1: "<m>M" (the caller states the search was ungapped) */
+    uint8_t emit_unmapped;                 /* 1: a read without records gets one flag-4 line at its place */
+    uint8_t secondary_seq;                 /* 0: SEQ and QUAL of secondary records are '*' */
+    uint8_t mapq_unique, mapq_multi;
+    uint8_t reserved[3];                   /* 0 */
+} fmgpu_sam_spec;
+int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const fmgpu_sam_spec* spec,
+                        uint8_t* out, uint64_t capacity, uint64_t* out_bytes,
+                        uint64_t* out_line_off, uint64_t* out_lines, void* stream);
+int fmgpu_sam_header(const fmgpu_name_table* seq_names, const uint64_t* seq_lengths, uint64_t nseq,
+                     const char* program_id, uint8_t* out, uint64_t capacity, uint64_t* out_bytes);   /* host memory only, no device */
 
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
