@@ -14,13 +14,13 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import FmgpuError, DeviceBuffer, PinnedBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE, TEXT_SPAN_DTYPE
+from .capi import FmgpuError, DeviceBuffer, PinnedBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE, TEXT_SPAN_DTYPE, MATE_PAIR_DTYPE
 from . import search_scheme  # noqa: F401
 
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer",
-           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
+           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "join_mates", "MatePairs", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
 
 
 class _Options:
@@ -1681,3 +1681,67 @@ def sam_header(seq_names, lengths, program=None):
     capi.check(L.fmgpu_sam_header(C.byref(table), capi.ptr(lengths), lengths.size, prog, capi.ptr(out), int(nbytes.value), C.byref(nbytes)))
     del alive
     return out[:int(nbytes.value)].tobytes()
+
+
+# ---- positions of paired-end mates joined to concordant pairs on the device (fmgpu_positions_mates)
+class MatePairs:
+    """what join_mates returns: pairs (a MATE_PAIR_DTYPE array: fragment, tlen, a, b, errors, flags), off (uint64, fragments + 1 entries: each fragment's first pair
+    record) and cls (uint8 per fragment, an index into capi.MATE_CLASSES)"""
+
+    def __init__(self, pairs, off, cls):
+        self.pairs, self.off, self.cls = pairs, off, cls
+
+    def __len__(self):
+        return len(self.pairs)
+
+
+def _records(positions):
+    """(void*, count, keep-alive) of a POSITION_DTYPE array, or of a DeviceBuffer / torch tensor of such records (used in place)"""
+    if positions is None:
+        return None, 0, None
+    if isinstance(positions, np.ndarray):
+        positions = np.ascontiguousarray(positions, dtype=POSITION_DTYPE)
+    p, nbytes = _buffer(positions)
+    count = nbytes // POSITION_DTYPE.itemsize
+    return (p if count else None), count, positions
+
+
+def join_mates(positions_a, qoff_a, positions_b=None, qoff_b=None, strands=True, interleaved=False, orientation="fr", min_tlen=0, max_tlen=1000, best=False,
+               max_records=0, stream=None):
+    """fmgpu_positions_mates: the positions map_reads returned for the two mates of every fragment joined to concordant pairs, on the device.  positions_a / positions_b:
+    POSITION_DTYPE arrays, or DeviceBuffers / torch tensors of such records; qoff_a / qoff_b: the read offsets of the two batches (arrays or DeviceBuffers; only the read
+    lengths are used).  interleaved=True: one batch (positions_b and qoff_b stay None) whose reads 2f and 2f + 1 are the mates of fragment f.  strands=True reads qidx
+    as the both-strand calls number it (read = qidx >> 1, strand = qidx & 1).  orientation: "fr" (opposite strands, the forward mate upstream, no dovetail) or "any".
+    min_tlen <= template length <= max_tlen.  best=True keeps only a fragment's pairs with the fewest errors; max_records > 0 leaves a fragment unjoined (class 5) if one
+    of its mates has more records.  Returns a MatePairs (pairs, off, cls); the counting call sizes `pairs` exactly."""
+    pa, count_a, keep_a = _records(positions_a)
+    pb, count_b, keep_b = _records(positions_b)
+    if interleaved and (positions_b is not None or qoff_b is not None):
+        raise ValueError("an interleaved batch has no positions_b and no qoff_b")
+    if not interleaved and (positions_b is None or qoff_b is None):
+        raise ValueError("separate batches need positions_b and qoff_b")
+    offs = []
+    for q in (qoff_a, qoff_b):
+        if q is not None and not (hasattr(q, "ptr") and not hasattr(q, "ctypes")) and not hasattr(q, "data_ptr"):
+            q = _u64(q).reshape(-1)
+        offs.append(q)
+    reads_a = _buffer(offs[0])[1] // 8 - 1
+    if reads_a < 0 or (interleaved and reads_a % 2):
+        raise ValueError("qoff_a holds reads + 1 offsets, an even number of reads in an interleaved batch")
+    n = reads_a // 2 if interleaved else reads_a
+    if not interleaved and _buffer(offs[1])[1] // 8 - 1 != n:
+        raise ValueError("both batches have one read per fragment")
+    kinds = {"fr": capi.MATES_FR, "any": capi.MATES_ANY}
+    if orientation not in kinds:
+        raise ValueError('orientation is "fr" or "any"')
+    spec = capi.MatesSpec(_buffer(offs[0])[0], None if interleaved else _buffer(offs[1])[0], n, int(min_tlen), int(max_tlen), int(max_records), 1 if strands else 0,
+                          1 if interleaved else 0, kinds[orientation], 1 if best else 0, (C.c_uint8 * 4)(0, 0, 0, 0))
+    sp = None if stream is None else C.c_void_p(stream if isinstance(stream, int) else getattr(stream, "cuda_stream", 0))
+    L, total = capi.lib(), C.c_uint64()
+    off, cls = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8)
+    capi.check(L.fmgpu_positions_mates(pa, count_a, pb, count_b, C.byref(spec), None, 0, C.byref(total), None, None, sp))       # the counting call sizes the pairs exactly
+    pairs = np.zeros(int(total.value), dtype=capi.MATE_PAIR_DTYPE)
+    capi.check(L.fmgpu_positions_mates(pa, count_a, pb, count_b, C.byref(spec), capi.ptr(pairs) if pairs.size else None, pairs.size, C.byref(total), capi.ptr(off),
+                                       capi.ptr(cls), sp))
+    del keep_a, keep_b, offs
+    return MatePairs(pairs[:int(total.value)], off, cls[:n])

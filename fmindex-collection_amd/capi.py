@@ -186,6 +186,27 @@ class SamSpec(C.Structure):
 
 
 assert C.sizeof(SamSpec) == 72
+
+
+class MatePair(C.Structure):
+    """fmgpu_mate_pair: one concordant pair of records of the two mates of a fragment (fmgpu_positions_mates)"""
+    _fields_ = [("fragment", C.c_uint64), ("tlen", C.c_uint64), ("a", C.c_uint32), ("b", C.c_uint32), ("errors", C.c_uint32), ("flags", C.c_uint32)]
+
+
+MATE_PAIR_DTYPE = np.dtype([("fragment", "<u8"), ("tlen", "<u8"), ("a", "<u4"), ("b", "<u4"), ("errors", "<u4"), ("flags", "<u4")])
+assert MATE_PAIR_DTYPE.itemsize == C.sizeof(MatePair) == 32
+
+
+class MatesSpec(C.Structure):
+    """fmgpu_mates_spec: the read offsets, the fragment count, the template length bounds and the switches of fmgpu_positions_mates (host memory)"""
+    _fields_ = [("qoff_a", C.c_void_p), ("qoff_b", C.c_void_p), ("n_fragments", C.c_uint64), ("min_tlen", C.c_uint64), ("max_tlen", C.c_uint64),
+                ("max_records", C.c_uint64), ("strand_shift", C.c_uint8), ("interleaved", C.c_uint8), ("orientation", C.c_uint8), ("best", C.c_uint8),
+                ("reserved", C.c_uint8 * 4)]
+
+
+assert C.sizeof(MatesSpec) == 56
+MATES_FR, MATES_ANY = 0, 1
+MATE_CLASSES = ("none", "only_a", "only_b", "discordant", "paired", "skipped")
 COL_QIDX, COL_SEQ_ID, COL_POS, COL_ERRORS, COL_HIT, COL_READ, COL_STRAND, COL_READ_NAME, COL_SEQ_NAME = range(9)
 COLUMNS = {"qidx": COL_QIDX, "seq_id": COL_SEQ_ID, "pos": COL_POS, "errors": COL_ERRORS, "hit": COL_HIT, "read": COL_READ, "strand": COL_STRAND,
            "read_name": COL_READ_NAME, "seq_name": COL_SEQ_NAME}
@@ -215,6 +236,7 @@ EXPORTS = [
     "fmgpu_queries_strands", "fmgpu_search_best_pairs", "fmgpu_search_best_ng21_pairs", "fmgpu_map_strands", "fmgpu_feed_map_strands", "fmgpu_feed_map_text_strands",
     "fmgpu_positions_format",
     "fmgpu_positions_sam", "fmgpu_sam_header",
+    "fmgpu_positions_mates",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -378,6 +400,8 @@ def lib():
     if hasattr(L, "fmgpu_positions_sam"):                     # (FMGPU_LIBRARY may name an older build of the same ABI)
         L.fmgpu_positions_sam.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(SamSpec), C.c_void_p, C.c_uint64, u64p, C.c_void_p, u64p, C.c_void_p]
         L.fmgpu_sam_header.argtypes = [C.POINTER(NameTable), C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_uint64, u64p]
+    if hasattr(L, "fmgpu_positions_mates"):
+        L.fmgpu_positions_mates.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(MatesSpec), C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

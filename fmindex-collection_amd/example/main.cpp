@@ -31,6 +31,10 @@
 //     and the searched batch.  QNAME is the read's number in that batch and QUAL is '*' (the default reader keeps neither names nor qualities); CIGAR is "<m>M" for
 //     noerror and '*' otherwise (the ladders of this harness are edit-distance searches).  With --pair-strands a read and its reverse complement are one read (flag 16);
 //     without it every read of the searched batch, the reverse complements the harness appends included, is a read of its own.
+//   * --mates <second query file> (not in the reference; --mode map, not --sam, --feed, --packed, --device-format or --queries): read i of --query and read i of
+//     --mates are the two mates of fragment i.  Both files are mapped as --mode map maps one, and the positions are joined on the device (fmgpu_positions_mates
+//     through fmc::joinMates) with --min_tlen / --max_tlen (0 / 1000): with both strands a pair is concordant in FR orientation, with --no-reverse in any.
+//     --save_output gets "fragment seqId posA strandA posB strandB tlen errors" per pair, strands as + / -.
 //   * --device-parse (not in the reference): the --query file is read as bytes and parsed on the device (fmgpu_queries_parse through fmc::parseQueries); its first byte
 //     chooses FASTA ('>') or FASTQ ('@', read only this way).  On a well-formed FASTA — ends in a newline, no '>' inside sequence lines, no '\r' — the output is the
 //     same, byte for byte.  Elsewhere the device rules differ from the reader below: a '\r' in front of a newline belongs to the line end (the reader takes it for
@@ -60,12 +64,13 @@ namespace {
 // token that is no flag, is reported as "unknown commandline <token>".
 enum class HitMode { all, besthits, map };
 struct Options {
-    std::string referenceFasta, readsFasta, outputFile;
+    std::string referenceFasta, readsFasta, outputFile, matesFasta;
     std::vector<std::string> algorithms;
     std::string schemeName = "h2-k2";
     bool schemeDyn = false;
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
+    size_t minTlen = 0, maxTlen = 1000;                          // --mates: the template lengths of a concordant pair, inclusive
     bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false, sam = false;
     HitMode hitMode = HitMode::all;
 };
@@ -112,6 +117,9 @@ FlagRule const kFlags[] = {
     {"--pair-strands", false, [](Options& o, char const*) { o.pairStrands = true; }},
     {"--device-format", false, [](Options& o, char const*) { o.deviceFormat = true; }},
     {"--sam", false, [](Options& o, char const*) { o.sam = true; }},
+    {"--mates", true, [](Options& o, char const* v) { o.matesFasta = v; }},
+    {"--min_tlen", true, [](Options& o, char const* v) { o.minTlen = asCount(v); }},
+    {"--max_tlen", true, [](Options& o, char const* v) { o.maxTlen = asCount(v); }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
     {"--ext", true, [](Options&, char const*) {}},
     {"--threads", true, [](Options&, char const*) {}},
@@ -296,6 +304,7 @@ struct Run {
     Index index;
     fmc::NameTable referenceNames{};                             // --sam: the names and lengths of the sequences of --index
     std::vector<uint64_t> referenceLengths{};
+    std::vector<std::vector<uint8_t>> const* mateReads{nullptr};  // --mates: the reads of the second file, loaded, doubled and trimmed as the first's
 
     // a scheme stretched to the read length: uniformly, or (--gen <name>_dyn) part by part where the weighted node count grows least — with the constants
     // the reference's example passes (src/example/main.cpp:116, :135: Edit = true, sigma 4, 3e9 rows)
@@ -383,11 +392,51 @@ struct Run {
             query.kind = fmc::MapQuery::Kind::Ng21;
             for (size_t j = 0; j <= k; ++j) query.expanded.push_back(stretch(schemeByName(config.schemeName, j, j), firstLength));
         }
+        if constexpr (!std::is_same_v<Queries, fmc::PackedQueries>) if (mateReads) return matesMapped(reads, query, k, clock);
         auto const mapped = config.feed ? mapThroughFeed(reads, query) : mapAtOnce(reads, query);
         double const tMap = clock.reset();
         std::string sam;
         if constexpr (!std::is_same_v<Queries, fmc::PackedQueries>) if (config.sam && !config.outputFile.empty()) sam = samFile(mapped, reads, kind == Algorithm::noerror);
         reportMapped(mapped, (config.pairStrands ? 2 : 1) * reads.size(), k, tMap, sam);
+    }
+
+    // --mates: both files mapped as --mode map maps one, then the positions of the two mates of every fragment (read i of either file) joined on the device
+    // (fmgpu_positions_mates through fmc::joinMates).  A batch with both strands counts 2 * read + strand, whether the reverse complements were made here (every read
+    // followed by its reverse complement) or on the device (--pair-strands): concordant is FR then; with --no-reverse every strand is 0 and any order counts.
+    // --save_output gets "fragment seqId posA strandA posB strandB tlen errors" per pair, written by a loop here.
+    void matesMapped(std::vector<std::vector<uint8_t>> const& reads, fmc::MapQuery const& query, size_t k, StopWatch& clock) const {
+        auto const first = mapAtOnce(reads, query);
+        auto const second = mapAtOnce(*mateReads, query);
+        double const tMap = clock.reset();
+        bool const bothStrands = config.pairStrands || config.withReverseComplement, doubled = bothStrands && !config.pairStrands;
+        auto forward = [&](std::vector<std::vector<uint8_t>> const& batch) {
+            if (!doubled) return batch;
+            std::vector<std::vector<uint8_t>> every;
+            for (size_t i = 0; i < batch.size(); i += 2) every.push_back(batch[i]);
+            return every;
+        };
+        fmc::MatesSpec spec;
+        spec.strands = bothStrands;
+        spec.orientation = bothStrands ? fmc::MatesSpec::Orientation::FR : fmc::MatesSpec::Orientation::Any;
+        spec.minTlen = config.minTlen; spec.maxTlen = config.maxTlen;
+        auto const joined = fmc::joinMates(first.positions, forward(reads), second.positions, forward(*mateReads), spec);
+        double const tJoin = clock.reset();
+        size_t const factor = config.pairStrands ? 2 : 1;
+        printMapped(first, factor * reads.size(), k, tMap / 2);
+        printMapped(second, factor * mateReads->size(), k, tMap / 2);
+        size_t const paired = static_cast<size_t>(std::count(joined.classes.begin(), joined.classes.end(), uint8_t{4}));
+        std::printf("%-15s %3zu: %10.3gs - pairs: %10zu in %10zu of %10zu fragments\n", "mates", k, tJoin, joined.pairs.size(), paired, joined.classes.size());
+        if (config.outputFile.empty()) return;
+        auto* out = std::fopen(config.outputFile.c_str(), "w");
+        if (!out) throw std::runtime_error("cannot write " + config.outputFile);
+        for (auto const& p : joined.pairs) {
+            auto const& a = first.positions[p.a];
+            auto const& b = second.positions[p.b];
+            std::fprintf(out, "%zu %zu %zu %c %zu %c %zu %zu\n", static_cast<size_t>(p.fragment), static_cast<size_t>(static_cast<uint32_t>(a.seq_id)), static_cast<size_t>(a.pos),
+                         bothStrands && (a.qidx & 1) ? '-' : '+', static_cast<size_t>(b.pos), bothStrands && (b.qidx & 1) ? '-' : '+', static_cast<size_t>(p.tlen),
+                         static_cast<size_t>(p.errors));
+        }
+        std::fclose(out);
     }
 
     // --mode map --feed --device-parse without reverse complements: the bytes of the query file go through the feed as they are (fmgpu_feed_map_text through
@@ -424,7 +473,7 @@ struct Run {
         return fmc::samHeader(referenceNames, referenceLengths, "fmindex-collection-gpu-example") + fmc::formatSam(records, reads, spec).text;
     }
 
-    void reportMapped(fmc::MapResult const& mapped, size_t nreads, size_t k, double tMap, std::string const& sam = {}) const {
+    void printMapped(fmc::MapResult const& mapped, size_t nreads, size_t k, double tMap) const {
         struct { size_t n; size_t size() const { return n; } } const reads{nreads};
         std::vector<Placement> distinct;
         distinct.reserve(mapped.positions.size());
@@ -435,6 +484,10 @@ struct Run {
         for (auto const& h : mapped.hits) readsWithHits.insert(config.pairStrands ? h.qidx / 2 : h.qidx > reads.size() / 2 ? h.qidx - reads.size() / 2 : h.qidx);
         std::printf("%-15s %3zu: %10.3gs (%10.3gs+%10.3gs) %10.3gq/s - results: %10zu/%10zu/%10zu/%10zu - mem: %13zu\n", "str", k, tMap, tMap, 0.0,
                     reads.size() / tMap, mapped.positions.size(), mapped.positions.size(), distinct.size(), readsWithHits.size(), size_t{0});
+    }
+
+    void reportMapped(fmc::MapResult const& mapped, size_t nreads, size_t k, double tMap, std::string const& sam = {}) const {
+        printMapped(mapped, nreads, k, tMap);
         if (config.outputFile.empty()) return;
         auto* out = std::fopen(config.outputFile.c_str(), "w");
         if (!out) throw std::runtime_error("cannot write " + config.outputFile);
@@ -508,6 +561,11 @@ int main(int argc, char const* const* argv) try {
                     "          --device-format (--mode map: the --save_output file is formatted on the device; the same file, byte for byte)\\\n"
                     "          --sam (--mode map, not --packed: the --save_output file is a SAM file, the header and the records made on the device;\\\n"
                     "                 QNAME = the read's number in the searched batch, with --pair-strands one read for both strands)\\\n"
+                    "          --mates <second queryfile> (--mode map, not --sam, --feed, --packed, --device-format or --queries: read i of the two files are\\\n"
+                    "                 the mates of fragment i; both files are mapped and their positions joined on the device: --save_output gets\\\n"
+                    "                 \"fragment seqId posA strandA posB strandB tlen errors\" per concordant pair (opposite strands, the forward mate\\\n"
+                    "                 upstream; with --no-reverse any order))\\\n"
+                    "          --min_tlen <int> --max_tlen <int> (--mates: the template lengths of a concordant pair, inclusive; 0 and 1000)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }
@@ -515,6 +573,10 @@ int main(int argc, char const* const* argv) try {
     if (config.pairStrands && (config.hitMode != HitMode::map || config.packed)) throw std::runtime_error("--pair-strands needs --mode map and byte reads (no --packed)");
     if (config.deviceFormat && config.hitMode != HitMode::map) throw std::runtime_error("--device-format needs --mode map");
     if (config.sam && (config.hitMode != HitMode::map || config.packed || config.deviceFormat)) throw std::runtime_error("--sam needs --mode map, byte reads (no --packed) and no --device-format");
+    if (!config.matesFasta.empty() && config.hitMode != HitMode::map) throw std::runtime_error("--mates needs --mode map");
+    if (!config.matesFasta.empty() && (config.sam || config.feed)) throw std::runtime_error("--mates does not go with --sam or --feed: pairs are joined from the positions of two whole batches");
+    if (!config.matesFasta.empty() && (config.packed || config.deviceFormat || config.readLimit != 0)) throw std::runtime_error("--mates needs byte reads (no --packed), no --device-format and no --queries");
+    if (config.minTlen > config.maxTlen) throw std::runtime_error("--min_tlen lies above --max_tlen");
     auto withReference = [&](Run& run) {                              // --sam: what the header and RNAME are made of
         if (!config.sam) return;
         auto const reference = readFasta(config.referenceFasta, Sigma, config.unknownToA);
@@ -553,6 +615,16 @@ int main(int argc, char const* const* argv) try {
     size_t const limit = config.readLimit != 0 ? config.readLimit : std::numeric_limits<size_t>::max();     // (of the doubled batch)
     if (strands * reads.size() > limit) reads.resize((limit + strands - 1) / strands);
     if (config.trimTo != 0) for (auto& r : reads) if (r.size() > config.trimTo) r.resize(config.trimTo);
+    std::vector<std::vector<uint8_t>> mates;
+    if (!config.matesFasta.empty()) {
+        if (!std::filesystem::exists(config.matesFasta)) throw std::runtime_error("--mates: no file " + config.matesFasta);
+        mates = config.deviceParse ? readQueriesOnDevice(config.matesFasta, Sigma, config.unknownToA) : readFasta(config.matesFasta, Sigma, config.unknownToA);
+        if (config.withReverseComplement && !strandsOnDevice) mates = withReverseComplements(mates);
+        if (config.trimTo != 0) for (auto& r : mates) if (r.size() > config.trimTo) r.resize(config.trimTo);
+        if (mates.size() != reads.size()) throw std::runtime_error("--mates: the two files do not hold the same number of reads");
+        std::printf("loaded %zu mates (incl reverse complements)\n", strands * mates.size());
+        run.mateReads = &mates;
+    }
     fmc::PackedQueries packed;
     if (config.packed) {
         packed = strandsOnDevice ? fmc::PackedQueries::packOnDevice(reads, Sigma, {0, 4, 3, 2, 1}) : fmc::PackedQueries::pack(reads, Sigma);

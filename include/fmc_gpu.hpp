@@ -1415,6 +1415,58 @@ inline auto samHeader(NameTable const& seqNames, std::vector<uint64_t> const& le
     return text;
 }
 
+// Paired-end mates (include/fmgpu.h: fmgpu_positions_mates): fmc::joinMates(positionsA, readsA, positionsB, readsB, spec) joins the positions fmc::map returned for
+// the two mates of every fragment — mate A of fragment f is read f of readsA, mate B read f of readsB — to concordant pairs, on the device; the overload without a
+// second batch takes one interleaved batch whose reads 2f and 2f + 1 are the mates.  Only the lengths of the reads are used.  spec.strands = the positions come from a
+// both-strand call (qidx counts both strands); without strands every strand is 0 and Orientation::FR finds nothing.
+struct MatesSpec {
+    enum class Orientation : uint8_t { FR = FMGPU_MATES_FR, Any = FMGPU_MATES_ANY };
+    bool        strands{true};
+    Orientation orientation{Orientation::FR};
+    uint64_t    minTlen{0}, maxTlen{1000};                                   // inclusive
+    bool        best{false};                                                 // only a fragment's pairs with the fewest errors
+    uint64_t    maxRecords{0};                                               // > 0: a fragment one of whose mates has more records is not joined (class 5)
+};
+struct MatePairs {
+    std::vector<fmgpu_mate_pair> pairs;                                      // fragments ascending, inside a fragment by a, then by (pos of b, b)
+    std::vector<uint64_t>        offsets;                                    // fragments + 1 entries: each fragment's first pair
+    std::vector<uint8_t>         classes;                                    // per fragment: 0 no record, 1 only A, 2 only B, 3 no concordant pair, 4 paired, 5 not joined
+};
+namespace detail {
+inline auto joinMates(std::vector<fmgpu_position> const& a, std::vector<uint64_t> const& offA, std::vector<fmgpu_position> const* b, std::vector<uint64_t> const* offB,
+                      MatesSpec const& spec) -> MatePairs {
+    size_t const reads = offA.size() - 1;
+    if (b ? offB->size() != offA.size() : reads % 2 != 0) throw std::runtime_error("fmindex-collection (gpu): one read of each batch per fragment");
+    fmgpu_mates_spec s{};
+    s.qoff_a = offA.data(); s.qoff_b = b ? offB->data() : nullptr; s.n_fragments = b ? reads : reads / 2;
+    s.min_tlen = spec.minTlen; s.max_tlen = spec.maxTlen; s.max_records = spec.maxRecords;
+    s.strand_shift = spec.strands ? 1 : 0; s.interleaved = b ? 0 : 1; s.orientation = static_cast<uint8_t>(spec.orientation); s.best = spec.best ? 1 : 0;
+    fmgpu_position const* pb = b && !b->empty() ? b->data() : nullptr;
+    fmgpu_position const* pa = a.empty() ? nullptr : a.data();
+    uint64_t count = 0;
+    detail::check(fmgpu_positions_mates(pa, a.size(), pb, b ? b->size() : 0, &s, nullptr, 0, &count, nullptr, nullptr, nullptr));     // the counting call sizes the pairs exactly
+    MatePairs out;
+    out.pairs.resize(count); out.offsets.assign(s.n_fragments + 1, 0); out.classes.assign(s.n_fragments, 0);
+    detail::check(fmgpu_positions_mates(pa, a.size(), pb, b ? b->size() : 0, &s, count ? out.pairs.data() : nullptr, count, &count, out.offsets.data(),
+                                        out.classes.empty() ? nullptr : out.classes.data(), nullptr));
+    return out;
+}
+}  // namespace detail
+template <typename QueriesA, typename QueriesB>
+auto joinMates(std::vector<fmgpu_position> const& positionsA, QueriesA const& readsA, std::vector<fmgpu_position> const& positionsB, QueriesB const& readsB,
+               MatesSpec const& spec = {}) -> MatePairs {
+    std::vector<uint8_t> bufA, bufB; std::vector<uint64_t> offA, offB;
+    detail::flatten(readsA, bufA, offA);
+    detail::flatten(readsB, bufB, offB);
+    return detail::joinMates(positionsA, offA, &positionsB, &offB, spec);
+}
+template <typename Queries>
+auto joinMates(std::vector<fmgpu_position> const& positions, Queries const& interleavedReads, MatesSpec const& spec = {}) -> MatePairs {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(interleavedReads, buf, off);
+    return detail::joinMates(positions, off, nullptr, nullptr, spec);
+}
+
 // A feed (include/fmgpu.h: fmgpu_feed_*): host batches searched chunk by chunk on one index, upload, search and download overlapped.  What a caller that holds its
 // queries in host memory — the reference's Sequences — should search through: `fmc::Feed feed{index}; feed.search_no_errors(queries, delegate);`.  A Sequences object
 // (reads of one-byte symbols, each contiguous) goes down through the `_v` calls without being flattened, a PackedQueries through `_q4`.  The delegates are called as by

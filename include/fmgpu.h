@@ -1017,7 +1017,7 @@ int fmgpu_positions_format(const fmgpu_position* positions, uint64_t count, cons
  * fmgpu_sam_header: "@HD\tVN:1.6\tSO:unknown\n", one "@SQ\tSN:<name up to its first blank>\tLN:<length>\n" per sequence, and "@PG\tID:<program_id>\n" if program_id
  * is not NULL.  Host memory only, no device.  The counting and capacity rule above.  FMGPU_ERR_INVALID for a null out_bytes, a null out while capacity > 0, a null
  * seq_names or seq_lengths while nseq > 0, a table of fewer than nseq rows, a span beyond the table's bytes, an empty SN.
- * Not built: PAF, CIGAR for edit-distance hits, mate fields (RNEXT, PNEXT, TLEN stay * 0 0), SAM text per chunk inside fmgpu_map or the feeds, BAM or compression. */
+ * Not built: PAF, CIGAR for edit-distance hits, mate fields (RNEXT, PNEXT, TLEN stay * 0 0; the join of two mates' positions itself: fmgpu_positions_mates below), SAM text per chunk inside fmgpu_map or the feeds, BAM or compression. */
 typedef struct fmgpu_sam_spec {            /* 72 bytes, host memory */
     const uint8_t*  qbuf;                  /* the FORWARD batch the positions were mapped from; host or device */
     const uint64_t* qoff;                  /* nq + 1 entries, qoff[0] need not be 0 */
@@ -1038,6 +1038,69 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
                         uint64_t* out_line_off, uint64_t* out_lines, void* stream);
 int fmgpu_sam_header(const fmgpu_name_table* seq_names, const uint64_t* seq_lengths, uint64_t nseq,
                      const char* program_id, uint8_t* out, uint64_t capacity, uint64_t* out_bytes);   /* host memory only, no device */
+
+/* ---- positions to mate pairs: the located hits of paired-end mates joined on the device -------------------------------------------------------
+ * fmgpu_positions_mates takes the positions fmgpu_map* returned for the two mates of every fragment and writes one fmgpu_mate_pair per concordant pair of records.
+ * It needs no index handle: it reads position records and read offsets only.  Mapping, the feeds and fmgpu_positions_sam are as they were.
+ *   - Input order: both arrays are what fmgpu_map* returns: the read number (qidx >> strand_shift) does not decrease over the records (fmgpu_positions_sam's rule).
+ *     Separate mode (interleaved = 0): batch A holds mate A of every fragment and batch B mate B, both have n_fragments reads, fragment = read.  Interleaved mode:
+ *     positions_b is NULL with count_b = 0 and qoff_b is NULL; the one batch has 2 n_fragments reads, and reads 2f and 2f + 1 are mates A and B of fragment f.
+ *   - Geometry of a record x: s(x) its strand (qidx & 1 with strand_shift = 1, else 0), p(x) = pos, m(x) the length of its read (qoff[read + 1] - qoff[read]: only the
+ *     lengths of the offsets are used), e(x) = p(x) + m(x).  The read's length stands in for the length of the matched text, also for edit-distance hits: the
+ *     convention of fmgpu_positions_sam's "<m>M".
+ *   - Record a of mate A and record b of mate B of one fragment are a concordant pair iff a.seq_id == b.seq_id, min_tlen <= tlen <= max_tlen with
+ *     tlen = max(e(a), e(b)) - min(p(a), p(b)), and under FMGPU_MATES_FR also s(a) != s(b) and, with f the strand-0 and r the strand-1 record of the two,
+ *     p(f) <= p(r) and e(f) <= e(r): the forward mate lies upstream and there is no dovetail.  FMGPU_MATES_ANY drops the strand and order conditions.  With
+ *     strand_shift = 0 every strand is 0 and FR finds nothing: that is the rule, not an error.
+ *   - Output: one fmgpu_mate_pair per concordant pair; with best = 1 only a fragment's pairs with its minimal errors (a.errors + b.errors in 32 bits).  Order:
+ *     fragments ascending, inside a fragment by ascending a, then by ascending (p(b), b).  out_off: NULL, or n_fragments + 1 entries: each fragment's first pair
+ *     record, the last entry = *out_count.  out_class: NULL, or n_fragments bytes: 0 neither mate has a record; 1 only A has; 2 only B has; 3 both have, no concordant
+ *     pair; 4 at least one pair record; 5 not joined because one of its mates has more than max_records records (max_records > 0).  out_off and out_class are written
+ *     whenever the call gets past its checks, also on FMGPU_ERR_CAPACITY.
+ *   - *out_count is exact on success and on FMGPU_ERR_CAPACITY alike (then nothing is written to `out`); out == NULL with capacity == 0 is the counting call.
+ *   - Before the first use of the device, FMGPU_ERR_INVALID, each with a message of its own, for: a null spec or out_count.  Then n_fragments == 0 returns 0 with
+ *     *out_count = 0 and out_off[0] = 0 before anything else is looked at.  Then FMGPU_ERR_INVALID for: a null qoff_a; strand_shift, interleaved, orientation or best out
+ *     of range; reserved != 0; min_tlen > max_tlen; a qoff_b or positions_b (or count_b) that does not match the mode; null positions while their count is > 0; a null
+ *     out while capacity > 0.  Then FMGPU_ERR_UNSUPPORTED where count_a or count_b reaches 2^32 - 256 or n_fragments reaches 2^31 - 1.
+ *   - On the device, in the first passes, FMGPU_ERR_INVALID, looked for in this order and for array A before array B; nothing is written (out_off and out_class
+ *     neither, *out_count = 0) and the message names the array and the lowest offender: a record whose read number lies beyond the batch; a record whose read number lies
+ *     below its predecessor's; a read r with qoff[r + 1] < qoff[r]; a record with pos >= 2^62 (so that pos + m does not wrap for any m below 2^62).
+ *   - Every array (positions, offsets, out, out_off, out_class) may be host or device memory; host arrays are staged.  The spec is host memory.  Device arrays need
+ *     no alignment beyond their element's.
+ *   - Passes: per record (order, range, pos, each read's records), per read (offsets), per fragment (classes 0, 1, 2, 5), the B-side records ordered by (read, seq_id,
+ *     pos, index) with three stable hipcub radix sorts of index values and gathered into 32-byte records, per A-side record a bisection of its fragment's B-records to the
+ *     first one with its seq_id and pos >= p(a) - max_tlen and a walk up to pos <= p(a) + max_tlen (tlen >= |p(a) - p(b)|: the window suffices, the join is never
+ *     quadratic in a fragment's records) that counts — with best after a walk that takes the minimum —, two scans, ONE read-back (the number of pairs and the error
+ *     words), and the walk again to write.  The call returns after completion and frees its scratch: 37 bytes per fragment, 12 per A-side record and 56 per B-side record
+ *     (interleaved mode: 68 per record), plus hipcub's own.
+ * Not built: mate fields in fmgpu_positions_sam, a call that maps and joins, mates through the feeds, RF / FF orientations, rescue of an unmapped mate, insert-size
+ * estimation, pair lines as text. */
+#define FMGPU_MATES_FR  0   /* mates on opposite strands, the forward one upstream, no dovetail */
+#define FMGPU_MATES_ANY 1   /* any strands, any order */
+typedef struct fmgpu_mate_pair {           /* 32 bytes */
+    uint64_t fragment;                     /* the fragment's number */
+    uint64_t tlen;                         /* max(e(a), e(b)) - min(p(a), p(b)) */
+    uint32_t a, b;                         /* record index of mate A in positions_a, of mate B in positions_b (interleaved mode: both index positions_a) */
+    uint32_t errors;                       /* errors of record a + errors of record b */
+    uint32_t flags;                        /* bit 0: pos of a <= pos of b (mate A is the leftmost) */
+} fmgpu_mate_pair;
+typedef struct fmgpu_mates_spec {          /* 56 bytes, host memory */
+    const uint64_t* qoff_a;                /* read offsets of batch A (its reads + 1 entries, host or device, qoff[0] need not be 0): only the lengths are used */
+    const uint64_t* qoff_b;                /* the same for batch B; NULL in interleaved mode */
+    uint64_t n_fragments;
+    uint64_t min_tlen, max_tlen;           /* inclusive */
+    uint64_t max_records;                  /* 0 = no limit; else a fragment one of whose mates has more records is not joined (class 5) */
+    uint8_t  strand_shift;                 /* 0: read = qidx, strand 0; 1: read = qidx >> 1, strand = qidx & 1 (the *_strands numbering) */
+    uint8_t  interleaved;                  /* 0: A holds mate 1 of every fragment, B mate 2, fragment = read; 1: one batch, fragment = read >> 1, mate = read & 1 */
+    uint8_t  orientation;                  /* FMGPU_MATES_FR, FMGPU_MATES_ANY */
+    uint8_t  best;                         /* 1: of a fragment's concordant pairs only those with the minimal a.errors + b.errors */
+    uint8_t  reserved[4];                  /* 0 */
+} fmgpu_mates_spec;
+int fmgpu_positions_mates(const fmgpu_position* positions_a, uint64_t count_a,
+                          const fmgpu_position* positions_b, uint64_t count_b,
+                          const fmgpu_mates_spec* spec,
+                          fmgpu_mate_pair* out, uint64_t capacity, uint64_t* out_count,
+                          uint64_t* out_off, uint8_t* out_class, void* stream);
 
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
