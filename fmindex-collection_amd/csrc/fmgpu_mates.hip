@@ -17,9 +17,8 @@
 //  k_mates_walk<WRITE> the same walk again: each lane writes its pairs behind its offset as whole 32-byte records
 // Every pass behind the first two reads the error words and does nothing once one is set: a batch that is out of order indexes nothing.
 // Scratch: 37 bytes per fragment (its two slots among them), 12 bytes per A-side record, 56 bytes per B-side record, plus hipcub's own; freed on return.
-#include "fmgpu_common.h"
-
-#include <hipcub/hipcub.hpp>
+// The run boundaries of the first pass (run_edges) and the host-side odds and ends are fmgpu_positions.h's, shared with fmgpu_sam.hip and fmgpu_format.hip.
+#include "fmgpu_positions.h"
 
 namespace fmgpu {
 namespace {
@@ -69,14 +68,13 @@ __global__ __launch_bounds__(256) void k_mates_records(MatesArgs a, int side) {
     const fmgpu_position* __restrict__ p = side ? a.pb : a.pa;
     const uint64_t count = side ? a.count_b : a.count_a;
     if (i >= count) return;
-    const uint64_t read = p[i].qidx >> a.shift;
-    if (read >= a.reads) { atomicMin(&a.err[E_RANGE + side], (unsigned long long)i); return; }
-    const uint64_t before = i ? p[i - 1].qidx >> a.shift : kNone, behind = i + 1 < count ? p[i + 1].qidx >> a.shift : kNone;
-    if (i && before > read) atomicMin(&a.err[E_ORDER + side], (unsigned long long)i);
+    uint64_t read;
+    bool first, last;
+    if (!run_edges(p, count, i, a.shift, a.reads, &a.err[E_RANGE + side], &a.err[E_ORDER + side], &read, &first, &last)) return;
     if (p[i].pos >= kPosLimit) atomicMin(&a.err[E_POS + side], (unsigned long long)i);
     const uint64_t slot = a.interleaved ? read : 2 * read + (uint64_t)side;
-    if (before != read) a.first[slot] = (uint32_t)i;
-    if (behind != read) a.end[slot] = (uint32_t)i + 1u;
+    if (first) a.first[slot] = (uint32_t)i;
+    if (last) a.end[slot] = (uint32_t)i + 1u;
 }
 
 __global__ __launch_bounds__(256) void k_mates_qoff(MatesArgs a, int side) {
@@ -192,17 +190,6 @@ __global__ __launch_bounds__(256) void k_mates_fragments(MatesArgs a) {
         if (c) a.cls[f] = CLS_PAIRED;
     }
     a.fcount[f] = c;
-}
-
-struct Widen { __host__ __device__ uint64_t operator()(uint32_t v) const { return v; } };
-using Widened = hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*>;
-
-int first_offset_zero(uint64_t* out_off, hipStream_t stream) {
-    if (!out_off) return 0;
-    if (!is_device_pointer(out_off)) { out_off[0] = 0; return 0; }
-    FM_HIP(hipMemsetAsync(out_off, 0, 8, stream));
-    FM_HIP(hipStreamSynchronize(stream));
-    return 0;
 }
 
 }  // namespace

@@ -14,19 +14,18 @@
 //                 window leaves as aligned 16-byte stores: only the first and last bytes of the text leave byte by byte.  Equal windows balance a heavy-tailed batch by construction.
 // Every pass behind the first reads the error words and does nothing once one is set: a batch that is out of order indexes nothing.
 // Scratch: 32 bytes per read and 12 bytes per line of the bound, plus the scans' own, freed on return.
-#include "fmgpu_common.h"
+// The record loads and run boundaries, digit counts, name tables, the LDS window and its stores are fmgpu_positions.h's, shared with fmgpu_format.hip and fmgpu_mates.hip;
+// here: SAM's line (describe, the field_* helpers) and the copy of SEQ and QUAL (put_run).
+#include "fmgpu_positions.h"
 #include "fmgpu_pieces.h"
-
-#include <hipcub/hipcub.hpp>
 
 namespace fmgpu {
 namespace {
 
-constexpr uint32_t kSamWindow = 16384;                      // bytes of LDS a workgroup formats into (a multiple of 16)
 constexpr uint64_t kNone = ~0ull;
 constexpr uint32_t kNoRecord32 = 0xffffffffu;
 constexpr uint64_t kMaxSamLines = (1ull << 32) - 256;
-constexpr uint64_t kMaxSamBytes = 1ull << 31;               // a read or a name of this many bytes is refused
+constexpr uint64_t kMaxSamBytes = kMaxRowBytes;             // a read of this many symbols is refused, as a name or quality string of this many bytes is (table_row)
 
 // the error words behind the offsets: the lowest record whose read is >= nq; whose read lies below its predecessor's; the lowest read whose offsets decrease; the lowest
 // (line << 8 | code) the measure pass refuses as invalid; ... as unsupported; and (no error) the number of lines
@@ -34,11 +33,10 @@ enum : int { E_RANGE = 0, E_ORDER = 1, E_QOFF = 2, E_LINE = 3, E_LONG = 4, E_LIN
 enum : uint32_t { BAD_NONE = 0, BAD_RNAME_ROW = 1, BAD_RNAME_SPAN = 2, BAD_QUAL_ROW = 3, BAD_QUAL_SPAN = 4, BAD_QUAL_LEN = 5, BAD_SNAME_ROW = 6, BAD_SNAME_SPAN = 7 };
 enum : uint32_t { LONG_NONE = 0, LONG_READ = 1, LONG_NAME = 2, LONG_LINE = 3 };
 
-struct SamTable { const uint8_t* bytes; uint64_t n_bytes; const fmgpu_text_span* spans; uint64_t count; };
 struct SamArgs {
     const fmgpu_position* pos; uint64_t count;
     const uint8_t* qbuf; const uint64_t* qoff; uint64_t nq;
-    SamTable read_names, quals, seq_names;
+    NameTable read_names, quals, seq_names;
     uint8_t shift, use_read_names, use_quals, use_seq_names, cigar, emit_unmapped, secondary_seq, mapq_unique, mapq_multi;
     int aligned16;                                          // the records may be loaded as 16-byte pieces
     unsigned long long* key;                                // per read: (errors << 32 | record) of its primary record
@@ -49,37 +47,16 @@ struct SamArgs {
     uint64_t bound;                                         // count + (emit_unmapped ? nq : 0) >= the number of lines
 };
 
-__device__ const uint64_t kPow10[20] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull, 1000000000ull, 10000000000ull,
-                                        100000000000ull, 1000000000000ull, 10000000000000ull, 100000000000000ull, 1000000000000000ull, 10000000000000000ull,
-                                        100000000000000000ull, 1000000000000000000ull, 10000000000000000000ull};
-
-// decimal digits of v (0 has one): floor(log10) estimated from the bit length (1233 / 4096 ~ log10 2), corrected by one compare
-__device__ __forceinline__ uint32_t digits10(uint64_t v) {
-    v |= 1ull;
-    const uint32_t t = ((64u - (uint32_t)__clzll((long long)v)) * 1233u) >> 12;
-    return t + 1u - (v < kPow10[t] ? 1u : 0u);
-}
-
-__device__ __forceinline__ fmgpu_position load_record(const fmgpu_position* __restrict__ p, uint64_t i, int aligned16) {
-    fmgpu_position r;
-    if (aligned16) {
-        const ulonglong2 a = reinterpret_cast<const ulonglong2*>(p)[2 * i], b = reinterpret_cast<const ulonglong2*>(p)[2 * i + 1];
-        r.qidx = a.x; r.seq_id = a.y; r.pos = b.x; r.errors = (uint32_t)b.y; r.hit = (uint32_t)(b.y >> 32);
-    } else r = p[i];
-    return r;
-}
-
 __device__ __forceinline__ bool failed(const SamArgs& a) { return (a.err[E_RANGE] & a.err[E_ORDER] & a.err[E_QOFF]) != kNone; }
 
 __global__ __launch_bounds__(256) void k_sam_records(SamArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.count) return;
-    const uint64_t read = a.pos[i].qidx >> a.shift;
-    if (read >= a.nq) { atomicMin(&a.err[E_RANGE], (unsigned long long)i); return; }
-    const uint64_t before = i ? a.pos[i - 1].qidx >> a.shift : kNone, behind = i + 1 < a.count ? a.pos[i + 1].qidx >> a.shift : kNone;
-    if (i && before > read) atomicMin(&a.err[E_ORDER], (unsigned long long)i);
-    if (before != read) a.first[read] = (uint32_t)i;
-    if (behind != read) a.end[read] = (uint32_t)i + 1u;
+    uint64_t read;
+    bool first, last;
+    if (!run_edges(a.pos, a.count, i, a.shift, a.nq, &a.err[E_RANGE], &a.err[E_ORDER], &read, &first, &last)) return;
+    if (first) a.first[read] = (uint32_t)i;
+    if (last) a.end[read] = (uint32_t)i + 1u;
     atomicMin(&a.key[read], ((unsigned long long)a.pos[i].errors << 32) | (unsigned long long)i);
 }
 
@@ -113,18 +90,12 @@ struct Line {
     uint64_t length;
 };
 
-// row `row` of a table; stop: the name ends in front of its first ' ' or '\t'
-__device__ __forceinline__ uint32_t row_of(const SamTable& t, uint64_t row, bool stop, const uint8_t** src, uint64_t* len, uint32_t* toolong) {
-    *src = t.bytes; *len = 0;
-    if (row >= t.count) return 1;
-    const uint64_t o = t.spans[row].offset, n = t.spans[row].len;
-    if (n > t.n_bytes || o > t.n_bytes - n) return 2;
-    if (n >= kMaxSamBytes) { if (!*toolong) *toolong = LONG_NAME; return 0; }
-    const uint8_t* s = t.bytes + o;
-    uint64_t m = n;
-    if (stop) for (uint64_t j = 0; j < n; ++j) { const uint8_t b = s[j]; if (b == ' ' || b == '\t') { m = j; break; } }
-    *src = s; *len = m;
-    return 0;
+// table_row for a line: a row that is too long is no invalid line, it makes the line unsupported (where nothing else has yet)
+__device__ __forceinline__ uint32_t row_of(const NameTable& t, uint64_t row, bool stop, const uint8_t** src, uint32_t* len, uint32_t* toolong) {
+    const uint32_t b = table_row(t, row, stop, src, len);
+    if (b != ROW_LONG) return b;
+    if (!*toolong) *toolong = LONG_NAME;
+    return ROW_OK;
 }
 
 // [lo, hi): reads known to hold the line's (lstart[lo] <= line < lstart[hi])
@@ -153,16 +124,15 @@ __device__ __forceinline__ Line describe(const SamArgs& a, uint64_t line, uint64
         d.mapq = !secondary && a.nmin[lo] == 1u ? a.mapq_unique : a.mapq_multi;
         d.nh = a.end[lo] - first;
     }
-    uint32_t b;
-    uint64_t n = 0;
+    uint32_t b, n = 0;
     d.rname = nullptr; d.rn = digits10(d.read);
     if (a.use_read_names) {
         if ((b = row_of(a.read_names, d.read, true, &d.rname, &n, &d.toolong))) d.bad = BAD_RNAME_ROW + b - 1;
-        d.rn = n ? (uint32_t)n : 1u;
+        d.rn = n ? n : 1u;
         if (!n) d.rname = nullptr;
     }
     d.qual = nullptr;
-    uint64_t qn = 0;
+    uint32_t qn = 0;
     if (a.use_quals) {
         if ((b = row_of(a.quals, d.read, false, &d.qual, &qn, &d.toolong)) && !d.bad) d.bad = BAD_QUAL_ROW + b - 1;
         else if (!b && !d.toolong && qn != 0 && qn != d.m && !d.bad) d.bad = BAD_QUAL_LEN;
@@ -172,7 +142,7 @@ __device__ __forceinline__ Line describe(const SamArgs& a, uint64_t line, uint64
         d.sn = digits10(d.rec.seq_id);
         if (a.use_seq_names) {
             if ((b = row_of(a.seq_names, d.rec.seq_id, true, &d.sname, &n, &d.toolong)) && !d.bad) d.bad = BAD_SNAME_ROW + b - 1;
-            d.sn = n ? (uint32_t)n : 1u;
+            d.sn = n ? n : 1u;
             if (!n) d.sname = nullptr;
         }
     }
@@ -224,22 +194,8 @@ __device__ __forceinline__ uint64_t wave_search(const uint64_t* __restrict__ a, 
     return lo;
 }
 
-struct Window {                                             // positions count from the 16-byte piece of the output address that holds the text's first byte
-    uint8_t* lds; uint64_t lo;
-    __device__ __forceinline__ void put(uint64_t at, uint32_t b) const { const uint64_t k = at - lo; if (k < kSamWindow) lds[k] = (uint8_t)b; }
-};
-
-__device__ __forceinline__ void put_decimal(const Window& w, uint64_t v, uint64_t end) {       // its last digit at end - 1
-    while (v >> 32) {
-        const uint64_t q = v / 1000000000ull;
-        uint32_t r = (uint32_t)(v - q * 1000000000ull);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { w.put(--end, '0' + r % 10u); r /= 10u; }
-        v = q;
-    }
-    uint32_t x = (uint32_t)v;
-    do { w.put(--end, '0' + x % 10u); x /= 10u; } while (x);
-}
+// the fields of a line in a Window (fmgpu_positions.h) whose positions count from the 16-byte piece of the output address that holds the text's first byte: each
+// returns the position behind what it wrote
 __device__ __forceinline__ uint64_t field_decimal(const Window& w, uint64_t at, uint64_t v, uint32_t sep) {
     const uint32_t d = digits10(v);
     put_decimal(w, v, at + d);
@@ -254,10 +210,9 @@ __device__ __forceinline__ uint64_t field_text(const Window& w, uint64_t at, con
 __device__ __forceinline__ uint64_t field_name(const Window& w, uint64_t hi, uint64_t at, const uint8_t* src, uint32_t n, bool numbered, uint64_t number) {
     if (!src && numbered) return field_decimal(w, at, number, '\t');
     if (!src) { w.put(at, '*'); w.put(at + 1, '\t'); return at + 2; }
-    if (at < hi && at + n > w.lo) {
-        const uint32_t j0 = at < w.lo ? (uint32_t)(w.lo - at) : 0u, j1 = at + n > hi ? (uint32_t)(hi - at) : n;
-        for (uint32_t j = j0; j < j1; ++j) w.lds[at + j - w.lo] = src[j];
-    }
+    uint32_t j0, j1;
+    window_clip(w.lo, hi, at, n, &j0, &j1);
+    for (uint32_t j = j0; j < j1; ++j) w.lds[at + j - w.lo] = src[j];
     w.put(at + n, '\t');
     return at + n + 1;
 }
@@ -266,8 +221,8 @@ __device__ __forceinline__ uint64_t field_name(const Window& w, uint64_t hi, uin
 // 16-byte pieces that hold their source, reversed in registers where `rev` (byte j of the line is byte len - 1 - j of src), each sent through the strand's 256 entries
 // of tab (nullptr: as it is).  Every lane of the wave calls it; a lane without such a field passes len = 0.
 __device__ __forceinline__ void put_run(const Window& w, uint64_t hi, const uint8_t* src, uint32_t len, uint64_t at, uint32_t rev, const uint8_t* tab) {
-    uint32_t j0 = 0, j1 = 0;                                // bytes j0 .. j1 - 1 of the field lie in the window
-    if (len && at < hi && at + len > w.lo) { j0 = at < w.lo ? (uint32_t)(w.lo - at) : 0u; j1 = at + len > hi ? (uint32_t)(hi - at) : len; }
+    uint32_t j0, j1;                                        // bytes j0 .. j1 - 1 of the field lie in the window
+    window_clip(w.lo, hi, at, len, &j0, &j1);
     unsigned long long todo = __ballot(j1 > j0);
     const uint32_t lane = threadIdx.x & 63u, slot = lane >> 3, sub = lane & 7u;
     while (todo) {                                          // eight fields per round, eight lanes (128 bytes a step) each
@@ -299,14 +254,14 @@ __device__ __forceinline__ void put_run(const Window& w, uint64_t hi, const uint
 
 __global__ __launch_bounds__(256) void k_sam_write(SamArgs a, const uint8_t* __restrict__ tables, const uint64_t* __restrict__ off, uint64_t lines, uint64_t total,
                                                    uint8_t* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kSamWindow];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kTextWindow];
     __shared__ uint8_t tab[512];                            // the SEQ byte of a symbol: [0, 256) strand 0, [256, 512) strand 1 (complemented)
     tab[threadIdx.x] = tables[threadIdx.x];
     tab[256u + threadIdx.x] = tables[256u + threadIdx.x];
     const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
     uint8_t* const gbase = out - shift;                     // position 0: 16-byte aligned, never stored to below position `shift`
-    const uint64_t lo = (uint64_t)blockIdx.x * kSamWindow, extent = shift + total;
-    const uint64_t hi = lo + kSamWindow < extent ? lo + kSamWindow : extent;
+    const uint64_t lo = (uint64_t)blockIdx.x * kTextWindow, extent = shift + total;
+    const uint64_t hi = lo + kTextWindow < extent ? lo + kTextWindow : extent;
     const uint64_t from = lo > shift ? lo : shift;          // the window holds positions [from, hi) of the text = bytes [from - shift, hi - shift)
     if (from >= hi) return;                                 // (uniform)
     const uint64_t o0 = from - shift, o1 = hi - shift;
@@ -350,22 +305,7 @@ __global__ __launch_bounds__(256) void k_sam_write(SamArgs a, const uint8_t* __r
         put_run(w, hi, qual, qual_len, qual_at, rev, nullptr);
     }
     __syncthreads();
-    const uint32_t pieces = (uint32_t)((hi - lo + 15u) / 16u);
-    for (uint32_t j = threadIdx.x; j < pieces; j += 256u) {
-        const uint64_t p0 = lo + 16u * j;
-        if (p0 >= from && p0 + 16u <= hi) *reinterpret_cast<uint4*>(gbase + p0) = *reinterpret_cast<const uint4*>(lds + 16u * j);
-        else for (uint32_t k = 0; k < 16u; ++k) if (p0 + k >= from && p0 + k < hi) gbase[p0 + k] = lds[16u * j + k];
-    }
-}
-
-struct Widen { __host__ __device__ uint64_t operator()(uint32_t v) const { return v; } };
-using Widened = hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*>;
-
-int check_table(const fmgpu_name_table* t, const char* which) {
-    if (!t) return 0;
-    if (!t->bytes && t->n_bytes) return fail(FMGPU_ERR_INVALID, std::string("fmgpu_sam_spec: the ") + which + " table has no bytes but n_bytes > 0");
-    if (!t->spans && t->count) return fail(FMGPU_ERR_INVALID, std::string("fmgpu_sam_spec: the ") + which + " table has no spans but count > 0");
-    return 0;
+    window_flush(lds, gbase, lo, from, hi);
 }
 
 const char* const kBadText[] = {"", "names a row beyond the read_names table", "has a read name span that leaves the table's bytes", "names a row beyond the quals table",
@@ -398,19 +338,14 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
     if (spec->strands && !spec->strands->complement) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: strands has a null complement");
     if (spec->strands && (spec->strands->n < 1 || spec->strands->n > 256)) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: strands->n must be in [1, 256]");
     int rc;
-    if ((rc = check_table(spec->read_names, "read_names")) || (rc = check_table(spec->quals, "quals")) || (rc = check_table(spec->seq_names, "seq_names"))) return rc;
+    if ((rc = check_name_table(spec->read_names, "fmgpu_sam_spec", "read_names")) || (rc = check_name_table(spec->quals, "fmgpu_sam_spec", "quals")) ||
+        (rc = check_name_table(spec->seq_names, "fmgpu_sam_spec", "seq_names"))) return rc;
     *out_bytes = 0;
     if (out_lines) *out_lines = 0;
     const uint64_t bound = count + (spec->emit_unmapped ? nq : 0);
     if (count >= kMaxSamLines || nq >= kMaxSamLines || bound >= kMaxSamLines)
         return fail(FMGPU_ERR_UNSUPPORTED, "fmgpu_positions_sam: count, nq and count + (emit_unmapped ? nq : 0), the bound on the lines, must each stay below 2^32 - 256");
-    if (bound == 0) {                                               // no line
-        if (!out_line_off) return 0;
-        if (!is_device_pointer(out_line_off)) { out_line_off[0] = 0; return 0; }
-        FM_HIP(hipMemsetAsync(out_line_off, 0, 8, stream));
-        FM_HIP(hipStreamSynchronize(stream));
-        return 0;
-    }
+    if (bound == 0) return first_offset_zero(out_line_off, stream); // no line
 
     SamArgs a;
     std::memset(&a, 0, sizeof a);
@@ -427,12 +362,8 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
     if ((rc = spos.in(positions, count * sizeof(fmgpu_position), stream))) return rc;
     if (nq && (rc = soff.in(spec->qoff, (nq + 1) * 8, stream))) return rc;
     const fmgpu_name_table* tabs[3] = {spec->read_names, spec->quals, spec->seq_names};
-    SamTable* dst[3] = {&a.read_names, &a.quals, &a.seq_names};
-    for (int k = 0; k < 3; ++k) {
-        if (!tabs[k]) continue;
-        if ((rc = sbytes[k].in(tabs[k]->bytes, tabs[k]->n_bytes, stream)) || (rc = sspans[k].in(tabs[k]->spans, tabs[k]->count * sizeof(fmgpu_text_span), stream))) return rc;
-        *dst[k] = SamTable{(const uint8_t*)sbytes[k].dev, tabs[k]->n_bytes, (const fmgpu_text_span*)sspans[k].dev, tabs[k]->count};
-    }
+    NameTable* dst[3] = {&a.read_names, &a.quals, &a.seq_names};
+    for (int k = 0; k < 3; ++k) if (tabs[k] && (rc = stage_name_table(tabs[k], sbytes[k], sspans[k], stream, dst[k]))) return rc;
     a.use_read_names = spec->read_names != nullptr; a.use_quals = spec->quals != nullptr; a.use_seq_names = spec->seq_names != nullptr;
     a.pos = (const fmgpu_position*)spos.dev;
     a.aligned16 = (reinterpret_cast<uintptr_t>(a.pos) & 15u) == 0;
@@ -509,7 +440,7 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
     a.qbuf = sq.dev ? (const uint8_t*)sq.dev : spec->qbuf;          // (a batch without a symbol: the pointer is never read through)
     if ((rc = sout.out(out, total, stream))) { (void)hipStreamSynchronize(stream); return rc; }
     uint8_t* const dout = (uint8_t*)sout.dev;
-    const uint64_t windows = ((reinterpret_cast<uintptr_t>(dout) & 15u) + total + kSamWindow - 1) / kSamWindow;
+    const uint64_t windows = ((reinterpret_cast<uintptr_t>(dout) & 15u) + total + kTextWindow - 1) / kTextWindow;
     FM_GRID(wgrid, windows * 256);
     k_sam_write<<<wgrid, dim3(256), 0, stream>>>(a, small.as<uint8_t>(), doff, lines, total, dout);
     FM_LAUNCHED("k_sam_write");

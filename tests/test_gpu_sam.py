@@ -325,6 +325,52 @@ def test_a_capacity_one_byte_short_leaves_out_untouched_with_exact_counts():
         assert rc == 0 and (out.to_array(np.uint8, fill.size) if device else out)[:n].tobytes() == want
 
 
+def long_names(count, rng):
+    """names of 100 .. 400 bytes without a blank; every third gets one in its second half (QNAME and RNAME end in front of it)"""
+    names = []
+    for i in range(count):
+        name = bytearray(rng.integers(33, 127, size=int(rng.integers(100, 401))).astype(np.uint8).tobytes())
+        if i % 3 == 1:
+            name[int(rng.integers(len(name) // 2, len(name)))] = b" \t"[i % 2]
+        names.append(bytes(name))
+    return names
+
+
+def test_names_that_cross_the_window_edges():
+    """QNAME and RNAME are copied by their lane, the part inside the workgroup's 16 KiB window: long names on short reads, so that names lie across the edges between
+    windows.  That some do is asserted from the model's text alone, for each of the two output alignments, before the device is asked."""
+    rng = np.random.default_rng(31)
+    nq, window = 300, 16384
+    qbuf, qoff, _, quals, _ = make_batch(rng.integers(0, 60, size=nq).tolist(), seed=32)
+    names, seqs = fm.pack_names(long_names(nq, rng)), fm.pack_names(long_names(40, rng))
+    rec = make_records([(1, 1, 2, 0)[r % 4] for r in range(nq)], seed=33, nseq=40)
+    assert len(rec) == 300
+    want, woff = model.format_sam(rec, qbuf, qoff, CHAR_OF, DNA5, table_model(names), table_model(quals), table_model(seqs))
+    assert len(want) > 4 * window + 16                                        # at least four edges at either alignment
+    st = capi.Strands(DNA5.ctypes.data_as(capi.u8p), 5, 0)
+    dq, do, dpos = DeviceBuffer.from_array(qbuf), DeviceBuffer.from_array(qoff), DeviceBuffer.from_array(rec)
+    spec, keep = raw_spec(dq, do, nq, st, names, quals, seqs)
+    guard = 64
+    for shift in (0, 5):
+        # windows are cut at multiples of 16384 counted from the 16-byte piece of the output address that holds the first byte: the edges in bytes of the text
+        edges = range(window - shift, len(want), window)
+        assert len(edges) >= 4
+        crossing = {"QNAME": 0, "RNAME": 0}
+        for l in range(len(woff) - 1):
+            f = want[woff[l]: woff[l + 1]].split(b"\t")
+            for field, start, n in (("QNAME", woff[l], len(f[0])), ("RNAME", woff[l] + len(f[0]) + len(f[1]) + 2, len(f[2]))):
+                crossing[field] += any(start < e < start + n for e in edges)
+        assert crossing["QNAME"] >= 1 and crossing["RNAME"] >= 1, (shift, crossing)
+        fill = np.full(guard + 16 + len(want) + guard, 0xAA, dtype=np.uint8)
+        buf = DeviceBuffer.from_array(fill)
+        assert buf.ptr % 256 == 0
+        rc, n, lines = raw(dpos, len(rec), spec, buf.ptr + guard + shift, len(want))
+        assert rc == 0 and n == len(want) and lines == len(woff) - 1, capi.lib().fmgpu_last_error()
+        back = buf.to_array(np.uint8, fill.size)
+        assert back[guard + shift: guard + shift + n].tobytes() == want, shift
+        assert (back[: guard + shift] == 0xAA).all() and (back[guard + shift + n:] == 0xAA).all(), shift
+
+
 def test_fastq_to_sam_end_to_end_against_the_indexed_text():
     """Does not lean on the model: FASTQ bytes -> parse_queries -> map_reads (both strands, the pair ladder of Hamming schemes k = 0 .. 2) -> format_sam; every mapped
     line is held against the text that was indexed."""
