@@ -954,6 +954,13 @@ int fmgpu_index_destroy(fmgpu_index_t h) {
 
 static bool lf_table_wanted() { return opt_on(FMGPU_OPT_LF_TABLE); }
 
+// the enumerator of a fmgpu_layout value without its FMGPU_ prefix, for messages
+static std::string layout_name(int32_t layout) {
+    static const char* const names[] = {"IB8", "IB16", "IB32", "IB16A", "IBP16", "EPR8", "EPR16", "EPR32", "EPRV2_8", "EPRV2_16", "EPRV2_32", "WAVELET",
+                                        "EPRV3_8", "EPRV3_16", "EPRV3_32", "EPRV4", "EPRV5", "IEPRV7", "FBV_64_64K", "FBV_512_64K", "FBV_2048_64K"};
+    return layout >= 0 && layout < (int32_t)(sizeof(names) / sizeof(names[0])) ? std::string(names[layout]) : "layout " + std::to_string(layout);
+}
+
 int fmgpu_index_create(const fmgpu_index_desc* desc, fmgpu_index_t* out) {
     if (!desc || !out) return fail(FMGPU_ERR_INVALID, "desc / out is null");
     *out = nullptr;
@@ -962,6 +969,9 @@ int fmgpu_index_create(const fmgpu_index_desc* desc, fmgpu_index_t* out) {
     if (!desc->C) return fail(FMGPU_ERR_INVALID, "C is null");
     if (desc->bwt_rev && (desc->bwt_rev->n != desc->bwt.n || desc->bwt_rev->sigma != desc->bwt.sigma))
         return fail(FMGPU_ERR_INVALID, "bwt don't have the same size: " + std::to_string(desc->bwt.n) + " " + std::to_string(desc->bwt_rev->n));   // fmindex/BiFMIndex.h:48-50
+    // BiFMIndex<String> has one String type (fmindex/BiFMIndex.h:17): the cursor steps and the searches pick their reader by bwt's layout and read bwt_rev through it
+    if (desc->bwt_rev && desc->bwt_rev->layout != desc->bwt.layout)
+        return fail(FMGPU_ERR_INVALID, "bwt and bwt_rev must have the same layout: bwt is " + layout_name(desc->bwt.layout) + ", bwt_rev is " + layout_name(desc->bwt_rev->layout));
     std::unique_ptr<Index> x(new (std::nothrow) Index());
     if (!x) return fail(FMGPU_ERR_NOMEM, "host allocation");
     (void)hipGetDevice(&x->hdr.device);
@@ -1314,6 +1324,7 @@ int fmgpu_cursor_extend(fmgpu_index_t h, int32_t direction, uint64_t count, cons
     if (direction == 1 && !x->bidirectional) return fail(FMGPU_ERR_INVALID, "extendRight needs a BiFMIndex");
     if (count == 0) return 0;
     if (!lb || !len || !out_lb || !out_len || (x->bidirectional && (!lb_rev || !out_lb_rev))) return fail(FMGPU_ERR_INVALID, "cursor arrays are null");
+    if (!x->bidirectional) lb_rev = nullptr;                     // an FMIndexCursor has no lb_rev: neither staged nor looked at by the guard
     hipStream_t stream = (hipStream_t)stream_;
     const uint64_t fan = symb ? 1 : (uint64_t)x->bwt.sigma;
     Staged slb, srev, slen, ssym, olb, orev, olen;

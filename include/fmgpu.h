@@ -114,7 +114,8 @@ typedef struct fmgpu_sparse_array_desc {
     fmgpu_dense_vector_desc field[2];             /* documents.data[0] = seqId, data[1] = pos */
 } fmgpu_sparse_array_desc;
 
-/* FMIndex (fmindex/FMIndex.h:21-23) or BiFMIndex (fmindex/BiFMIndex.h:31-35) */
+/* FMIndex (fmindex/FMIndex.h:21-23) or BiFMIndex (fmindex/BiFMIndex.h:31-35).  BiFMIndex<String> holds both strings in one String type: bwt_rev must
+ * have bwt's n, sigma and layout, or fmgpu_index_create returns FMGPU_ERR_INVALID (the kernels choose their reader by bwt's layout for both). */
 typedef struct fmgpu_index_desc {
     fmgpu_string_desc bwt;
     const fmgpu_string_desc* bwt_rev;             /* NULL => unidirectional FMIndex */
@@ -375,14 +376,22 @@ int fmgpu_search_ng21_q4(fmgpu_index_t h, const uint8_t* packed, const uint64_t*
                          fmgpu_hit* out, uint64_t capacity, uint64_t* out_count, fmgpu_stats* stats, void* stream);
 
 /* A profile of the same search: out_depth[q] = query symbols consumed until the cursor holds at most one row (0 rows included), or
- * length + 1 if it still holds several rows at the end.  (Tells how much of a batch the one-row walk tables can serve; bench.py reports
+ * length + 1 if it still holds several rows at the end.  The root cursor holds all n rows, so an empty read gives 1 (0 when n <= 1, where nothing
+ * is consumed of any read).  A symbol >= sigma is counted as consumed and empties the cursor.  nq == 0 returns 0; a null qbuf, qoff or out_depth
+ * with nq > 0 is FMGPU_ERR_INVALID.  (Tells how much of a batch the one-row walk tables can serve; bench.py reports
  * the distribution for each text.) */
 int fmgpu_search_exact_depth(fmgpu_index_t h, const uint8_t* qbuf, const uint64_t* qoff, uint64_t nq, uint32_t* out_depth, void* stream);
 
 /* Cursor steps, batched: FMIndexCursor / BiFMIndexCursor::extendLeft(symb), extendRight(symb) (fmindex/FMIndexCursor.h:33-37,
  * fmindex/BiFMIndexCursor.h:113-128) for `count` cursors {lb, lb_rev, len}, or — symb == NULL — extendLeft() / extendRight() over all
  * symbols (FMIndexCursor.h:38-53, BiFMIndexCursor.h:58-82): then every cursor yields sigma cursors, out[i * sigma + c].
- * direction 0 = left, 1 = right (BiFMIndex only).  lb_rev / out_lb_rev may be NULL for a unidirectional FMIndex.
+ * direction 0 = left, 1 = right (BiFMIndex only).  For a unidirectional FMIndex lb_rev is ignored and may be NULL, and out_lb_rev may be NULL
+ * (where it is given it receives zeros).
+ * A cursor that does not lie inside the index (lb + len > n, or lb_rev + len > n on a BiFMIndex; a len of 2^64 - 1 does not wrap), or a symb[i] >= sigma,
+ * yields {0, 0, 0} for that cursor — in every one of its sigma slots in the all-symbols form; no table is read for it, the other cursors of the batch
+ * are not affected.  An empty cursor inside the index (len == 0, lb <= n) is stepped like any other: the result is empty and carries the reference's lb.
+ * FMGPU_ERR_INVALID: a null handle; a direction other than 0 and 1; direction 1 on a unidirectional FMIndex; with count > 0 a null lb, len, out_lb
+ * or out_len, and on a BiFMIndex a null lb_rev or out_lb_rev.  count == 0 returns 0 whatever the pointers.
  * symbolLeft / symbolRight of a cursor (BiFMIndexCursor.h:180-190) are fmgpu_string_query(what = 2) on bwt at lb / on bwtRev at lb_rev. */
 int fmgpu_cursor_extend(fmgpu_index_t h, int32_t direction, uint64_t count, const uint64_t* lb, const uint64_t* lb_rev, const uint64_t* len,
                         const uint8_t* symb, uint64_t* out_lb, uint64_t* out_lb_rev, uint64_t* out_len, void* stream);

@@ -6,7 +6,7 @@
      every boundary, against the oracle and against the plain count #{j < i : text[j] == c} (a numpy cumulative sum, independent of the oracle).
   2. Searches aimed at the edges: a collection of 131 371 rows (two 16-bit boundaries, the EPR periods beside them), reads cut from the suffixes of the rows
      beside each boundary — exact search through every kernel selection, scheme searches (Hamming, edit, ng21, backtracking, SMEMs, scoring matrix), cursor
-     steps, locate, locate_hits and extract, per layout, alphabet and row width, against the CPU walk of the oracle.
+     steps (all symbols at once and one symbol per call), the depth profile, locate, locate_hits and extract, per layout, alphabet and row width, against the CPU walk of the oracle.
   3. The same check list with 64-bit rows on super-blocks of 2^16 rows (three of them), so that the super tables of Formats A / P / M, the builder's, the
      locate kernels' and the lean kernel's LDS copy are read beyond their first entry.
   4. The symbol-plane table (Format S, k_exact_s) in that build: count fields of 16 bits in both row widths, three super-blocks — exact search by every selection
@@ -27,6 +27,7 @@ import fmindex_collection_amd as fm
 from fmindex_collection_amd import capi
 from fmindex_collection_amd.capi import HIT_DTYPE, POSITION_DTYPE
 from tests import smem_brute as sb
+from tests.cursor_model import depth_model, single_steps
 from tests.util import make_text, oracle_arrays, string_arrays
 from tests.test_gpu_parity import LAYOUTS, HIT_KEYS, mutated_queries
 from tests.golden.make_golden import EDGE_SIGMAS, super_period, edge_sizes, edge_text, edge_rows
@@ -272,6 +273,8 @@ def expected(sigma):
             step = (ox.extend_right_all if right else ox.extend_left_all)(fo.Cursor(int(a), int(r), int(l)))
             out[k] = [(c.lb, c.lb_rev, c.len) for c in step]
         E["extend/right" if right else "extend/left"] = out
+        E["extend1/right" if right else "extend1/left"] = single_steps(ox, cur, right)         # extendLeft(c) / extendRight(c): one oracle call per cursor and symbol
+    E["depth"] = depth_model(ox, reads)
     # locate: every row within 130 of a boundary
     near = np.unique(np.concatenate([np.arange(b - 130, b + 131) for b in BOUNDARIES])).astype(np.uint64)
     near = near[near < N_ROWS]
@@ -404,6 +407,9 @@ def collect(gx, sigma, R=None, tag="default"):
     for right in (False, True):
         olb, orev, olen = gx.extend(cur[:, 0], cur[:, 1], cur[:, 2], None, right=right)
         R["extend/%s@%s" % ("right" if right else "left", tag)] = np.stack([olb, orev, olen], axis=2)
+        one = [gx.extend(cur[:, 0], cur[:, 1], cur[:, 2], symb=c, right=right) for c in range(sigma)]      # the single-symbol form, one batched call per symbol
+        R["extend1/%s@%s" % ("right" if right else "left", tag)] = np.stack([np.stack(step, axis=1) for step in one], axis=1)
+    R["depth@%s" % tag] = fm.search_no_errors.depth(gx, queries).astype(np.uint64)
     gx.accelerate_lf(False)
     schemes("no_lf", ("ragged", "len20"))
     R["locate@%s/no_lf" % tag] = np.stack(gx.locate(E["locate_rows"]), axis=1)
