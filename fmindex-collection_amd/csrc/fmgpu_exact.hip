@@ -697,6 +697,14 @@ struct ExactAccel {                                 // (entry shapes by row widt
     const void* walk2;                              // per row LF^(2J) + the 2J symbols met as two codes (or null)
 };
 
+// table accesses of one single step of k_exact_kstep (fmgpu_stats, include/fmgpu.h): on the one-symbol blocks one 12-byte entry per interval end, one if both ends lie in
+// the same 64-row block (the second load then hits the entry the first one fetched), always two for a delimiter on a table with fused presence bits; any other
+// occurrence table is counted as two entries per step
+template <class Occ>
+__device__ __forceinline__ uint32_t single_step_accesses(const Occ&, idx_t, idx_t, uint32_t) { return 2u; }
+template <int SIGMA>
+__device__ __forceinline__ uint32_t single_step_accesses(const OccA<SIGMA>& occ, idx_t a, idx_t b, uint32_t c) { return (c == 0 && occ.v.fused) || (a >> 6) != (b >> 6) ? 2u : 1u; }
+
 template <class Occ>
 __global__ __launch_bounds__(256) void k_exact_kstep(Occ occ, ExactAccel ac, uint32_t R,
                                                      const uint8_t* __restrict__ qbuf, const uint64_t* __restrict__ qoff, uint64_t nq, idx_t n,
@@ -784,7 +792,7 @@ __global__ __launch_bounds__(256) void k_exact_kstep(Occ occ, ExactAccel ac, uin
                 if (c >= sigma) break;
                 idx_t ra, rb;
                 occ.lf2(lb, lb + len, c, ra, rb);
-                tbytes += 24u; tacc += 2u;
+                { const uint32_t k = single_step_accesses(occ, lb, lb + len, c); tbytes += 12u * k; tacc += k; }
                 if (rb == ra) break;
                 lb = ra; len = rb - ra; ++steps; ++done;
                 continue;
@@ -824,7 +832,7 @@ __global__ __launch_bounds__(256) void k_exact_kstep(Occ occ, ExactAccel ac, uin
             if (c >= sigma) { lb = 0; len = 0; break; }
             idx_t ra, rb;
             occ.lf2(lb, lb + len, c, ra, rb);
-            tbytes += 24u; tacc += 2u;
+            { const uint32_t k = single_step_accesses(occ, lb, lb + len, c); tbytes += 12u * k; tacc += k; }
             lb = ra; len = rb - ra;
         }
         store_interval(out_lb, out_len, q, lb, len);

@@ -163,11 +163,78 @@ typedef struct fmgpu_stats {
      * not count): table_bytes = sum over issued table loads of the entry bytes consumed (a 12-byte block entry, an 8-byte walk entry, a
      * 64-byte block of an extend-all, a 16-byte frame ...), table_accesses = number of such accesses that can each touch a different
      * memory line (two loads into the same 64-byte block count once).  Query and result traffic is coalesced and not included.
-     * Exact search along the sample chain: 64 bytes per block of the seek (the whole block is fetched), 4 per rank -> position word, 8 per chain entry. */
+     * The exact-search family (fmgpu_search_exact and its _packed / _q4 forms, the walk of fmgpu_search_smems) counts by the rule below. */
     uint64_t table_bytes;
     uint64_t table_accesses;
-    uint64_t table_steps;    /* exact search from an interval table in front of the pair table, or along the sample chain: LF steps that the entries stood for (entries read x their symbols); else 0 */
+    uint64_t table_steps;    /* exact search from an interval table in front of the pair table or the symbol planes, or along the sample chain: LF steps that the entries stood for (entries used x their symbols); else 0 */
 } fmgpu_stats;
+
+/* ---- What fmgpu_stats.table_bytes / table_accesses / table_steps hold after an exact search ------------------------------------------------
+ * The three fields are sums over the reads of a batch: a read's share depends on the read, the text and the tables of the handle, not on the reads
+ * it shares a wave or a call with (a batch split into two calls adds up to the whole batch's).  tests/exact_traffic_model.py restates this text
+ * on the CPU and tests/test_gpu_exact_traffic.py compares every kernel with it, exactly.
+ *
+ * The walk.  A read of m symbols is consumed from its LAST symbol to its first.  A step starts from an interval [a, b) of rows (the first from
+ * [0, n)) and consumes one symbol c: a = C[c] + rank(a, c), b likewise; the walk ends after the step that leaves a == b, or with the read.  lf_steps
+ * counts these steps whatever table served them.  A symbol c >= sigma is a step that empties the interval and is NO access.  An access counts
+ * when it is issued, also when the step then comes out empty (a pair that finds nothing, a chain entry that does not match).
+ * "One per end, one if shared" below means: one access for end a and one for end b, but one in all when a >> k == b >> k for blocks of 2^k rows.
+ *
+ *   what serves the call                                   one access                                                  bytes per access
+ *   one-symbol blocks (k_exact_a; the single steps of      one block entry per end, one if shared (k = 6)              12
+ *     every kernel below; the walk of fmgpu_search_smems)
+ *     ... the delimiter (c == 0) on a handle with          always 2                                                    12
+ *         FMGPU_FMT_FUSED
+ *   pair table (k_exact_p)                                  two symbols y, x, both in 1 .. 4: one 128-row line per      68
+ *                                                          end, one if shared (k = 7)
+ *     ... the odd symbol of a read of odd length,          the FIRST step, taken from C when in 1 .. 4: none; a         0
+ *         no interval table in front                       delimiter or foreign byte there is a single step
+ *   symbol planes (k_exact_s)                              one 64-row line per end, one if shared (k = 6)              44
+ *   multi-ary tree (k_exact_m)                             per step, per level and end one block of 64 node-local      4 + 8 d for a level of d digit bits
+ *                                                          positions, one if shared (k = 6)
+ *   EPR / EPRV2 blocks read in place (k_exact)             none                                                        0
+ *   interval-table entry                                   the entry                                                   8 (16 with 64-bit rows)
+ *   k-step table (k_exact_kstep)                           one context entry per end for K symbols, one if shared      12
+ *                                                          (k = 6)
+ *   walk tables (k_exact_kstep)                            one entry                                                   LF^J: 8 (16); LF^2J: 12 (16)
+ *   sample chain (k_exact_chain)                           each block of the seek; the rank -> position word; each     64; 4; 8
+ *                                                          chain entry read
+ *   fmgpu_search_smems on any other layout                 none                                                        0
+ *
+ * Pair table.  Without an interval table a read of odd length takes its odd symbol first (above), then pairs.  A pair that holds a delimiter or a
+ * foreign byte reads no line; it, and a pair whose line(s) were read and that came out empty, is taken as two single steps on the one-symbol blocks
+ * (the second only if the first left rows).  A symbol left over behind the last pair is a single step.
+ * Tree.  The levels take digits of 3 / 3 / 2 bits from the top for 8-bit symbols (bit_width(sigma - 1) bits: 1, 2, 3, 2+2, 3+2, 3+3, 3+2+2, 3+3+2).  At a
+ * level the position of row i inside its node is the number of rows < i whose symbols share the higher digits of c; every level of a step is
+ * read, also when an upper level already left a == b.
+ * Interval table of L symbols (in front of the pair table, the symbol planes or inside k_exact_kstep; n > 1).  A read with m >= L whose last L symbols are
+ * all in 1 .. sigma - 1 reads its entry: one access.  If the entry is not empty the read starts behind those L symbols, which cost nothing else; otherwise, and
+ * for every other read, the walk starts from [0, n) as if there were no table — on the pair table in pairs from the last symbol, so that an odd symbol is
+ * left over at the END and is a single step, never a step from C.  table_steps += L per entry that was used, in front of the pair table and the symbol
+ * planes; k_exact_kstep leaves table_steps 0.
+ * k_exact_kstep (any k-step / walk table, or an interval table that k_exact_p / k_exact_s do not serve).  After the interval entry, the main phase takes one
+ * table load per pass: with one row left and 2J symbols remaining (LF^2J table) or J (LF^J table), J = 32 / bit_width(sigma - 2), one walk entry; else with
+ * a k-step table one context entry per end for the next K symbols; else one single step.  The phase ends, without an access, at a stretch that is too short
+ * or holds a symbol outside 1 .. sigma - 1; and, with the access counted, at a walk entry that met a delimiter and at a context or single step that comes out
+ * empty.  A walk entry whose symbols differ from the read's: the symbols before the first differing one still go K at a time through the context table,
+ * then the phase ends.  The tail phase takes single steps to the read's end or the empty interval; a step that came out empty in the main phase is issued
+ * again there and counts again.  On an occurrence table other than the one-symbol blocks a single step of this kernel counts 2 accesses of 12 bytes.
+ * Sample chain (32-bit rows, sigma 5, a batch whose longest read has >= 48 symbols).  The pair-table walk as above, but at the first pass of the pair loop (so
+ * behind the odd symbol, then behind every pair or couple of single steps) at which the interval is one row and >= 32 symbols remain, the read is parked.
+ * Seek: the 64-byte block of the row is read (one access); if the row is not sampled, fewer than rate - 1 steps were sought, the next symbol is in 1 .. 4
+ * and the row holds it, the read steps to the next row and repeats.  Jump, only from a sampled row: the 4-byte rank -> position word and the row's 8-byte
+ * chain entry; then, while >= rate symbols remain and the entry is usable (not the first sample of its sequence, no delimiter among the rate symbols in front
+ * of it), the entry in front of it is read (8 bytes) and the rate symbols compared: equal moves there (rate steps, table_steps += rate), unequal ends the jump.
+ * The rest is the pair-table walk again, in pairs from where the read stands (a symbol left over is a single step at the end).
+ *
+ * By hand, "x y z" (z consumed first) on a 32-bit-row sigma = 5 handle with FMGPU_FMT_PAIRS, no other table, a short batch: z in 1 .. 4 comes from C, no access;
+ * the pair (y, x) starts from [C[z], C[z + 1]): 68 bytes if both ends share a 128-row line, else 136; if it comes out empty, y is read again as a single step
+ * (12 or 24 bytes from the same interval) and x, if y left rows, as another.  With FMGPU_SEL_EXACT_ONE_SYMBOL: three steps of 12 or 24 bytes each, as long as rows are left.
+ *
+ * Other kernels.  k_scheme_lean (k-mismatch search on dense DNA blocks or one-symbol blocks) uses the fields as plain counters: table_accesses = blocks it
+ * fetched (a node whose ends lie in two blocks counts two, a node re-visited for its next sibling fetches again), table_bytes = visited nodes of SEVERAL rows — a
+ * count, not bytes (the other visited nodes stood on one row) — and table_steps = nodes that prefix-table entries stood for.  The other depth-first kernels and
+ * locate follow the one-line description at the fields; no test pins them yet. */
 
 /* Library options: process-wide, read when a handle is created / a call starts (set them before, not during, the calls they concern).
  * The first seven, FMGPU_OPT_BUCKET_ROWS and FMGPU_OPT_SAMPLE_CHAIN choose what a handle holds or how a batch / a construction is prepared — results never depend on them; FORCE_WIDE, KERNEL_SELECT and FAIL_SCRATCH are test hooks. */

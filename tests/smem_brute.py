@@ -51,6 +51,17 @@ def match_lengths(text, read, sigma):
     return L
 
 
+def walk_reads(read, sigma):
+    """per end e of the read, the symbols its walk may consume: read[b + 1 .. e] behind the last break b at or before e (empty where read[e] is one).  A one-symbol
+    backward search of such a piece, stopped at the first empty extension, visits the intervals the walk of end e visits: tests/exact_traffic_model.py prices them"""
+    out, first = [], 0
+    for e in range(len(read)):
+        if is_break(read[e], sigma):
+            first = e + 1
+        out.append(np.asarray(read[first: e + 1], dtype=np.uint8))
+    return out
+
+
 def walk_steps(read, L, sigma):
     """extensions of a one-symbol walk: L[e] that succeed, plus the one that came out empty where the walk did not stop at the read's start or at a break"""
     return sum(L) + sum(1 for e in range(len(read)) if L[e] <= e and not is_break(read[e - L[e]], sigma))
