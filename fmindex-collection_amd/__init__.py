@@ -20,7 +20,7 @@ from . import search_scheme  # noqa: F401
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer",
-           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "join_mates", "MatePairs", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
+           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "join_mates", "MatePairs", "format_sam_mates", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
 
 
 class _Options:
@@ -1745,3 +1745,68 @@ def join_mates(positions_a, qoff_a, positions_b=None, qoff_b=None, strands=True,
                                        capi.ptr(cls), sp))
     del keep_a, keep_b, offs
     return MatePairs(pairs[:int(total.value)], off, cls[:n])
+
+
+# ---- positions and mate pairs to paired-end SAM records on the device (fmgpu_positions_sam_mates)
+def format_sam_mates(positions_a, queries_a, positions_b=None, queries_b=None, pairs=None, interleaved=False, char_of="dna5", strands=None, read_names=None, quals_a=None,
+                     quals_b=None, seq_names=None, cigar=True, strip_mate_suffix=True, mapq=(60, 0), device=False, want_line_offsets=False, stream=None):
+    """fmgpu_positions_sam_mates: the two mates of every fragment as two SAM lines with the mate fields filled in (flags 1, 2, 8, 32, 64, 128, RNEXT, PNEXT, TLEN), made
+    on the device: line 2f is mate A of fragment f, line 2f + 1 mate B.  positions_a / positions_b: what map_reads returned for the two batches (POSITION_DTYPE arrays,
+    DeviceBuffers or torch tensors); queries_a / queries_b: the FORWARD batches ((qbuf, qoff) of numpy arrays or DeviceBuffers, or lists of sequences); pairs: what
+    join_mates returned (a MatePairs), a MATE_PAIR_DTYPE array or a DeviceBuffer of such records, None for no pair.  interleaved=True: one batch (positions_b and
+    queries_b stay None) whose reads 2f and 2f + 1 are the mates of fragment f.  A fragment with pairs takes the pair with the fewest errors, the first one among
+    equals, and is proper; in every other fragment each mate takes its own primary record.  strands, char_of, the tables, cigar and mapq as format_sam takes them
+    (read_names: the names of batch A; quals_b stays None for an interleaved batch); strip_mate_suffix removes a trailing "/1" or "/2" from QNAME.
+    Returns the text as bytes, or with device=True (DeviceBuffer, bytes); with want_line_offsets also the uint64 offsets of the lines (2 fragments + 1 entries)."""
+    pa, count_a, keep_a = _records(positions_a)
+    pb, count_b, keep_b = _records(positions_b)
+    if interleaved and (positions_b is not None or queries_b is not None or quals_b is not None):
+        raise ValueError("an interleaved batch has no positions_b, no queries_b and no quals_b")
+    if not interleaved and (positions_b is None or queries_b is None):
+        raise ValueError("separate batches need positions_b and queries_b")
+    if isinstance(pairs, MatePairs):
+        pairs = pairs.pairs
+    if isinstance(pairs, np.ndarray):
+        pairs = np.ascontiguousarray(pairs, dtype=capi.MATE_PAIR_DTYPE)
+    pp, n_pairs = (None, 0) if pairs is None else _buffer(pairs)
+    n_pairs //= capi.MATE_PAIR_DTYPE.itemsize
+    batches = []
+    for queries in (queries_a,) if interleaved else (queries_a, queries_b):
+        if isinstance(queries, PackedQueries):
+            raise ValueError("format_sam_mates takes the byte form of the batches")
+        qbuf, qoff, nq = _queries(queries)
+        if isinstance(qoff, np.ndarray):
+            qoff = _u64(qoff)
+        if isinstance(qbuf, np.ndarray):
+            qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+        batches.append((qbuf, qoff, max(nq, 0)))
+    reads = batches[0][2]
+    if interleaved and reads % 2:
+        raise ValueError("an interleaved batch holds an even number of reads")
+    if not interleaved and batches[1][2] != reads:
+        raise ValueError("both batches have one read per fragment")
+    n = reads // 2 if interleaved else reads
+    table = char_table("dna5") if isinstance(char_of, str) and char_of == "dna5" else np.ascontiguousarray(np.asarray(char_of, dtype=np.uint8))
+    if table.size != 256:
+        raise ValueError("a character table has 256 entries")
+    st, comp = _strands(strands, False)
+    ptrs = [_buffer(b)[0] if n > 0 else None for batch in batches for b in batch[:2]] + [None, None]
+    spec = capi.SamMatesSpec(ptrs[0], ptrs[1], ptrs[2], ptrs[3], n, table.ctypes.data, C.pointer(st) if st is not None else None, None, None, None, None,
+                             1 if interleaved else 0, 1 if cigar else 0, 1 if strip_mate_suffix else 0, int(mapq[0]), int(mapq[1]), (C.c_uint8 * 3)(0, 0, 0))
+    keep = [comp, table, batches, keep_a, keep_b, pairs]
+    for field, names in (("read_names", read_names), ("quals_a", quals_a), ("quals_b", quals_b), ("seq_names", seq_names)):
+        if names is not None:
+            t, alive = _name_table(names)
+            keep.append((t, alive))
+            setattr(spec, field, C.pointer(t))
+    sp = None if stream is None else C.c_void_p(stream if isinstance(stream, int) else getattr(stream, "cuda_stream", 0))
+    L, nbytes = capi.lib(), C.c_uint64()
+    pp = pp if n_pairs else None
+    capi.check(L.fmgpu_positions_sam_mates(pa, count_a, pb, count_b, pp, n_pairs, C.byref(spec), None, 0, C.byref(nbytes), None, sp))     # the counting call sizes the text exactly
+    total = int(nbytes.value)
+    off = np.zeros(2 * n + 1, dtype=np.uint64) if want_line_offsets else None
+    out = DeviceBuffer(max(total, 8)) if device else np.zeros(max(total, 1), dtype=np.uint8)
+    capi.check(L.fmgpu_positions_sam_mates(pa, count_a, pb, count_b, pp, n_pairs, C.byref(spec), capi.ptr(out), total, C.byref(nbytes), capi.ptr(off), sp))
+    del keep
+    res = (out, total) if device else out[:total].tobytes()
+    return (res, off) if want_line_offsets else res

@@ -205,6 +205,17 @@ class MatesSpec(C.Structure):
 
 
 assert C.sizeof(MatesSpec) == 56
+
+
+class SamMatesSpec(C.Structure):
+    """fmgpu_sam_mates_spec: the two batches, the tables and the switches of fmgpu_positions_sam_mates (host memory)"""
+    _fields_ = [("qbuf_a", C.c_void_p), ("qoff_a", C.c_void_p), ("qbuf_b", C.c_void_p), ("qoff_b", C.c_void_p), ("n_fragments", C.c_uint64), ("char_of", C.c_void_p),
+                ("strands", C.POINTER(Strands)), ("read_names", C.POINTER(NameTable)), ("quals_a", C.POINTER(NameTable)), ("quals_b", C.POINTER(NameTable)),
+                ("seq_names", C.POINTER(NameTable)), ("interleaved", C.c_uint8), ("cigar", C.c_uint8), ("strip_mate_suffix", C.c_uint8), ("mapq_unique", C.c_uint8),
+                ("mapq_multi", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+assert C.sizeof(SamMatesSpec) == 96
 MATES_FR, MATES_ANY = 0, 1
 MATE_CLASSES = ("none", "only_a", "only_b", "discordant", "paired", "skipped")
 COL_QIDX, COL_SEQ_ID, COL_POS, COL_ERRORS, COL_HIT, COL_READ, COL_STRAND, COL_READ_NAME, COL_SEQ_NAME = range(9)
@@ -237,6 +248,7 @@ EXPORTS = [
     "fmgpu_positions_format",
     "fmgpu_positions_sam", "fmgpu_sam_header",
     "fmgpu_positions_mates",
+    "fmgpu_positions_sam_mates",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -402,6 +414,9 @@ def lib():
         L.fmgpu_sam_header.argtypes = [C.POINTER(NameTable), C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_uint64, u64p]
     if hasattr(L, "fmgpu_positions_mates"):
         L.fmgpu_positions_mates.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(MatesSpec), C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "fmgpu_positions_sam_mates"):
+        L.fmgpu_positions_sam_mates.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(SamMatesSpec), C.c_void_p, C.c_uint64, u64p,
+                                                C.c_void_p, C.c_void_p]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

@@ -35,6 +35,10 @@
 //     --mates are the two mates of fragment i.  Both files are mapped as --mode map maps one, and the positions are joined on the device (fmgpu_positions_mates
 //     through fmc::joinMates) with --min_tlen / --max_tlen (0 / 1000): with both strands a pair is concordant in FR orientation, with --no-reverse in any.
 //     --save_output gets "fragment seqId posA strandA posB strandB tlen errors" per pair, strands as + / -.
+//   * --paired-sam (not in the reference; only with --mates): the --save_output file is a paired-end SAM file instead of the pair lines: the header of --sam
+//     followed by two records per fragment made on the device (fmgpu_positions_sam_mates through fmc::formatSamMates) from the positions of the two files and the
+//     joined pairs: a fragment with pairs takes the one with the fewest errors and is proper, elsewhere each mate takes its primary record.  QNAME = the fragment's
+//     number, RNAME as under --sam.
 //   * --device-parse (not in the reference): the --query file is read as bytes and parsed on the device (fmgpu_queries_parse through fmc::parseQueries); its first byte
 //     chooses FASTA ('>') or FASTQ ('@', read only this way).  On a well-formed FASTA — ends in a newline, no '>' inside sequence lines, no '\r' — the output is the
 //     same, byte for byte.  Elsewhere the device rules differ from the reader below: a '\r' in front of a newline belongs to the line end (the reader takes it for
@@ -71,7 +75,7 @@ struct Options {
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
     size_t minTlen = 0, maxTlen = 1000;                          // --mates: the template lengths of a concordant pair, inclusive
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false, sam = false;
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false, sam = false, pairedSam = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -118,6 +122,7 @@ FlagRule const kFlags[] = {
     {"--device-format", false, [](Options& o, char const*) { o.deviceFormat = true; }},
     {"--sam", false, [](Options& o, char const*) { o.sam = true; }},
     {"--mates", true, [](Options& o, char const* v) { o.matesFasta = v; }},
+    {"--paired-sam", false, [](Options& o, char const*) { o.pairedSam = true; }},
     {"--min_tlen", true, [](Options& o, char const* v) { o.minTlen = asCount(v); }},
     {"--max_tlen", true, [](Options& o, char const* v) { o.maxTlen = asCount(v); }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
@@ -427,8 +432,26 @@ struct Run {
         size_t const paired = static_cast<size_t>(std::count(joined.classes.begin(), joined.classes.end(), uint8_t{4}));
         std::printf("%-15s %3zu: %10.3gs - pairs: %10zu in %10zu of %10zu fragments\n", "mates", k, tJoin, joined.pairs.size(), paired, joined.classes.size());
         if (config.outputFile.empty()) return;
+        std::string sam;                                                // --paired-sam: two records per fragment, made on the device from the positions and the pairs
+        if (config.pairedSam) {
+            auto const strands = pairStrands();
+            fmc::SamMatesSpec samSpec;
+            if (bothStrands) samSpec.strands = &strands;
+            samSpec.seqNames = &referenceNames;
+            samSpec.cigar = query.kind == fmc::MapQuery::Kind::Exact;             // (the exact search is ungapped, as under --sam)
+            auto recordsA = first.positions, recordsB = second.positions;
+            for (auto* records : {&recordsA, &recordsB}) for (auto& p : *records) p.seq_id = static_cast<uint32_t>(p.seq_id);      // (what the other files print of it)
+            sam = fmc::samHeader(referenceNames, referenceLengths, "fmindex-collection-gpu-example") +
+                  fmc::formatSamMates(recordsA, forward(reads), recordsB, forward(*mateReads), joined, samSpec).text;
+        }
         auto* out = std::fopen(config.outputFile.c_str(), "w");
         if (!out) throw std::runtime_error("cannot write " + config.outputFile);
+        if (config.pairedSam) {
+            bool const written = std::fwrite(sam.data(), 1, sam.size(), out) == sam.size();
+            std::fclose(out);
+            if (!written) throw std::runtime_error("cannot write " + config.outputFile);
+            return;
+        }
         for (auto const& p : joined.pairs) {
             auto const& a = first.positions[p.a];
             auto const& b = second.positions[p.b];
@@ -565,6 +588,8 @@ int main(int argc, char const* const* argv) try {
                     "                 the mates of fragment i; both files are mapped and their positions joined on the device: --save_output gets\\\n"
                     "                 \"fragment seqId posA strandA posB strandB tlen errors\" per concordant pair (opposite strands, the forward mate\\\n"
                     "                 upstream; with --no-reverse any order))\\\n"
+                    "          --paired-sam (only with --mates: the --save_output file is a paired-end SAM file, the header of --sam and two records per\\\n"
+                    "                 fragment made on the device: the pair with the fewest errors where there is one, else each mate's best record)\\\n"
                     "          --min_tlen <int> --max_tlen <int> (--mates: the template lengths of a concordant pair, inclusive; 0 and 1000)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
@@ -576,9 +601,10 @@ int main(int argc, char const* const* argv) try {
     if (!config.matesFasta.empty() && config.hitMode != HitMode::map) throw std::runtime_error("--mates needs --mode map");
     if (!config.matesFasta.empty() && (config.sam || config.feed)) throw std::runtime_error("--mates does not go with --sam or --feed: pairs are joined from the positions of two whole batches");
     if (!config.matesFasta.empty() && (config.packed || config.deviceFormat || config.readLimit != 0)) throw std::runtime_error("--mates needs byte reads (no --packed), no --device-format and no --queries");
+    if (config.pairedSam && config.matesFasta.empty()) throw std::runtime_error("--paired-sam needs --mates");
     if (config.minTlen > config.maxTlen) throw std::runtime_error("--min_tlen lies above --max_tlen");
     auto withReference = [&](Run& run) {                              // --sam: what the header and RNAME are made of
-        if (!config.sam) return;
+        if (!config.sam && !config.pairedSam) return;
         auto const reference = readFasta(config.referenceFasta, Sigma, config.unknownToA);
         run.referenceNames = fmc::NameTable{readFastaNames(config.referenceFasta)};
         for (auto const& s : reference) run.referenceLengths.push_back(s.size());

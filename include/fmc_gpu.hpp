@@ -1467,6 +1467,87 @@ auto joinMates(std::vector<fmgpu_position> const& positions, Queries const& inte
     return detail::joinMates(positions, off, nullptr, nullptr, spec);
 }
 
+// Paired-end SAM (include/fmgpu.h: fmgpu_positions_sam_mates): fmc::formatSamMates(positionsA, readsA, positionsB, readsB, pairs, spec) is two alignment lines per
+// fragment, line 2f for mate A and line 2f + 1 for mate B, with the mate fields filled in (flags 1, 2, 8, 32, 64, 128, RNEXT, PNEXT, TLEN), formatted on the device from
+// the positions fmc::map returned for the two FORWARD batches and the pairs fmc::joinMates made of them (its result, or any array of pair records).  A fragment with
+// pairs takes the one with the fewest errors, the first among equals, and is proper; elsewhere each mate takes its own primary record.  The overload without a second
+// batch takes one interleaved batch whose reads 2f and 2f + 1 are the mates.  An ArrayView is a pointer and a count in host or device memory; a std::vector converts.
+// readNames are the names of batch A; stripMateSuffix removes a trailing "/1" or "/2" from QNAME.  The counting call sizes the text, as in fmc::formatSam.
+template <typename T>
+struct ArrayView {
+    T const* data{nullptr};
+    size_t   size{0};
+    ArrayView() = default;
+    ArrayView(T const* d, size_t n) : data{n ? d : nullptr}, size{n} {}
+    ArrayView(std::vector<T> const& v) : ArrayView{v.data(), v.size()} {}                     // NOLINT: a vector is a view of itself
+};
+struct SamMatesSpec {
+    CharTable        charOf{CharTable::dna5()};
+    Strands const*   strands{nullptr};
+    NameTable const* readNames{nullptr};
+    NameTable const* qualsA{nullptr};
+    NameTable const* qualsB{nullptr};                                        // stays null for an interleaved batch
+    NameTable const* seqNames{nullptr};
+    bool    cigar{true};
+    bool    stripMateSuffix{true};
+    uint8_t mapqUnique{60}, mapqMulti{0};
+};
+namespace detail {
+inline auto formatSamMates(ArrayView<fmgpu_position> a, ArrayView<fmgpu_position> b, ArrayView<fmgpu_mate_pair> pairs, std::vector<uint8_t> const& bufA,
+                           std::vector<uint64_t> const& offA, std::vector<uint8_t> const* bufB, std::vector<uint64_t> const* offB, SamMatesSpec const& spec,
+                           bool wantLineOffsets) -> SamText {
+    size_t const reads = offA.size() - 1;
+    if (bufB ? offB->size() != offA.size() : reads % 2 != 0) throw std::runtime_error("fmindex-collection (gpu): one read of each batch per fragment");
+    fmgpu_sam_mates_spec s{};
+    s.qbuf_a = bufA.data(); s.qoff_a = offA.data(); s.n_fragments = bufB ? reads : reads / 2; s.char_of = spec.charOf.map.data();
+    if (bufB) { s.qbuf_b = bufB->data(); s.qoff_b = offB->data(); }
+    if (s.n_fragments && !s.qbuf_a) s.qbuf_a = reinterpret_cast<uint8_t const*>(offA.data());        // (batches without a symbol: never read through)
+    if (s.n_fragments && bufB && !s.qbuf_b) s.qbuf_b = reinterpret_cast<uint8_t const*>(offB->data());
+    fmgpu_strands st{};
+    fmgpu_name_table rt{}, qa{}, qb{}, nt{};
+    if (spec.strands) { st = spec.strands->c(); s.strands = &st; }
+    if (spec.readNames) { rt = spec.readNames->c(); s.read_names = &rt; }
+    if (spec.qualsA) { qa = spec.qualsA->c(); s.quals_a = &qa; }
+    if (spec.qualsB) { qb = spec.qualsB->c(); s.quals_b = &qb; }
+    if (spec.seqNames) { nt = spec.seqNames->c(); s.seq_names = &nt; }
+    s.interleaved = bufB ? 0 : 1; s.cigar = spec.cigar ? 1 : 0; s.strip_mate_suffix = spec.stripMateSuffix ? 1 : 0;
+    s.mapq_unique = spec.mapqUnique; s.mapq_multi = spec.mapqMulti;
+    uint64_t bytes = 0;
+    detail::check(fmgpu_positions_sam_mates(a.data, a.size, b.data, b.size, pairs.data, pairs.size, &s, nullptr, 0, &bytes, nullptr, nullptr));      // the counting call sizes the text exactly
+    SamText out;
+    out.text.assign(bytes, '\0');
+    if (wantLineOffsets) out.lineOffsets.assign(2 * s.n_fragments + 1, 0);
+    if (bytes) detail::check(fmgpu_positions_sam_mates(a.data, a.size, b.data, b.size, pairs.data, pairs.size, &s, reinterpret_cast<uint8_t*>(out.text.data()), bytes, &bytes,
+                                                       wantLineOffsets ? out.lineOffsets.data() : nullptr, nullptr));
+    return out;
+}
+}  // namespace detail
+template <typename QueriesA, typename QueriesB>
+auto formatSamMates(ArrayView<fmgpu_position> positionsA, QueriesA const& readsA, ArrayView<fmgpu_position> positionsB, QueriesB const& readsB,
+                    ArrayView<fmgpu_mate_pair> pairs, SamMatesSpec const& spec = {}, bool wantLineOffsets = false) -> SamText {
+    std::vector<uint8_t> bufA, bufB; std::vector<uint64_t> offA, offB;
+    detail::flatten(readsA, bufA, offA);
+    detail::flatten(readsB, bufB, offB);
+    return detail::formatSamMates(positionsA, positionsB, pairs, bufA, offA, &bufB, &offB, spec, wantLineOffsets);
+}
+template <typename QueriesA, typename QueriesB>
+auto formatSamMates(ArrayView<fmgpu_position> positionsA, QueriesA const& readsA, ArrayView<fmgpu_position> positionsB, QueriesB const& readsB, MatePairs const& joined,
+                    SamMatesSpec const& spec = {}, bool wantLineOffsets = false) -> SamText {
+    return formatSamMates(positionsA, readsA, positionsB, readsB, ArrayView<fmgpu_mate_pair>{joined.pairs}, spec, wantLineOffsets);
+}
+template <typename Queries>
+auto formatSamMates(ArrayView<fmgpu_position> positions, Queries const& interleavedReads, ArrayView<fmgpu_mate_pair> pairs, SamMatesSpec const& spec = {},
+                    bool wantLineOffsets = false) -> SamText {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(interleavedReads, buf, off);
+    return detail::formatSamMates(positions, {}, pairs, buf, off, nullptr, nullptr, spec, wantLineOffsets);
+}
+template <typename Queries>
+auto formatSamMates(ArrayView<fmgpu_position> positions, Queries const& interleavedReads, MatePairs const& joined, SamMatesSpec const& spec = {},
+                    bool wantLineOffsets = false) -> SamText {
+    return formatSamMates(positions, interleavedReads, ArrayView<fmgpu_mate_pair>{joined.pairs}, spec, wantLineOffsets);
+}
+
 // A feed (include/fmgpu.h: fmgpu_feed_*): host batches searched chunk by chunk on one index, upload, search and download overlapped.  What a caller that holds its
 // queries in host memory — the reference's Sequences — should search through: `fmc::Feed feed{index}; feed.search_no_errors(queries, delegate);`.  A Sequences object
 // (reads of one-byte symbols, each contiguous) goes down through the `_v` calls without being flattened, a PackedQueries through `_q4`.  The delegates are called as by

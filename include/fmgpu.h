@@ -1093,7 +1093,7 @@ int fmgpu_positions_format(const fmgpu_position* positions, uint64_t count, cons
  * fmgpu_sam_header: "@HD\tVN:1.6\tSO:unknown\n", one "@SQ\tSN:<name up to its first blank>\tLN:<length>\n" per sequence, and "@PG\tID:<program_id>\n" if program_id
  * is not NULL.  Host memory only, no device.  The counting and capacity rule above.  FMGPU_ERR_INVALID for a null out_bytes, a null out while capacity > 0, a null
  * seq_names or seq_lengths while nseq > 0, a table of fewer than nseq rows, a span beyond the table's bytes, an empty SN.
- * Not built: PAF, CIGAR for edit-distance hits, mate fields (RNEXT, PNEXT, TLEN stay * 0 0; the join of two mates' positions itself: fmgpu_positions_mates below), SAM text per chunk inside fmgpu_map or the feeds, BAM or compression. */
+ * Not built: PAF, CIGAR for edit-distance hits, mate fields in this call (RNEXT, PNEXT, TLEN stay * 0 0; paired-end records: fmgpu_positions_sam_mates below), SAM text per chunk inside fmgpu_map or the feeds, BAM or compression. */
 typedef struct fmgpu_sam_spec {            /* 72 bytes, host memory */
     const uint8_t*  qbuf;                  /* the FORWARD batch the positions were mapped from; host or device */
     const uint64_t* qoff;                  /* nq + 1 entries, qoff[0] need not be 0 */
@@ -1149,7 +1149,7 @@ int fmgpu_sam_header(const fmgpu_name_table* seq_names, const uint64_t* seq_leng
  *     quadratic in a fragment's records) that counts — with best after a walk that takes the minimum —, two scans, ONE read-back (the number of pairs and the error
  *     words), and the walk again to write.  The call returns after completion and frees its scratch: 37 bytes per fragment, 12 per A-side record and 56 per B-side record
  *     (interleaved mode: 68 per record), plus hipcub's own.
- * Not built: mate fields in fmgpu_positions_sam, a call that maps and joins, mates through the feeds, RF / FF orientations, rescue of an unmapped mate, insert-size
+ * Not built: a call that maps and joins (paired-end SAM records from the pairs: fmgpu_positions_sam_mates below), mates through the feeds, RF / FF orientations, rescue of an unmapped mate, insert-size
  * estimation, pair lines as text. */
 #define FMGPU_MATES_FR  0   /* mates on opposite strands, the forward one upstream, no dovetail */
 #define FMGPU_MATES_ANY 1   /* any strands, any order */
@@ -1177,6 +1177,78 @@ int fmgpu_positions_mates(const fmgpu_position* positions_a, uint64_t count_a,
                           const fmgpu_mates_spec* spec,
                           fmgpu_mate_pair* out, uint64_t capacity, uint64_t* out_count,
                           uint64_t* out_off, uint8_t* out_class, void* stream);
+
+/* ---- positions and mate pairs to paired-end SAM records on the device -------------------------------------------------------------------------
+ * fmgpu_positions_sam_mates writes the two mates of every fragment as two SAM lines with the mate fields filled in: the positions fmgpu_map* returned for the two
+ * batches and the pair records of fmgpu_positions_mates go in, exactly 2 n_fragments lines come out, line 2f for mate A of fragment f and line 2f + 1 for mate B.  It
+ * needs no index handle.  fmgpu_positions_sam, fmgpu_positions_mates and their structs are as they were; fmgpu_sam_header writes the header in front.
+ *   - Reads: separate mode (interleaved = 0): mate A of fragment f is read f of batch A (qbuf_a / qoff_a, quals_a), mate B read f of batch B (qbuf_b / qoff_b, quals_b).
+ *     Interleaved mode: positions_b is NULL with count_b = 0, qbuf_b, qoff_b and quals_b are NULL, the one batch has 2 n_fragments reads, mates A and B of fragment f are
+ *     its reads 2f and 2f + 1 (quals_a rows 2f and 2f + 1), and pairs[].b indexes positions_a: the convention of fmgpu_positions_mates.  Both record arrays are ordered
+ *     as fmgpu_map* returns them (the read number qidx >> shift does not decrease; shift = 1 with spec->strands, else 0).
+ *   - The policy, one alignment per mate: from a pair record only fragment, a and b are read; errors and tlen are recomputed from the two position records.  The chosen
+ *     pair of a fragment is its pair record with the smallest a.errors + b.errors (in 32 bits), among equals the one with the lowest index in `pairs`, which need not be
+ *     sorted by fragment.  A fragment with a chosen pair is proper and its two mates take that pair's records.  In every other fragment each mate takes its own primary
+ *     record by fmgpu_positions_sam's rule (fewest errors, lowest record index), or none if its read has no record.  No secondary lines are written.
+ *   - Fields of mate X with its own record x (or none) and the other mate's record y (or none); p = pos, m = the read's length, e = p + m, s = strand:
+ *     QNAME  the row of mate A's read in read_names (row f, interleaved 2f) up to its first ' ' or '\t'; with strip_mate_suffix a result of 3 bytes or more that ends in
+ *            "/1" or "/2" loses those two bytes; an empty result is '*'; without a table f in decimal.  Both lines of a fragment carry the same QNAME.
+ *     FLAG   1 + (A: 64, B: 128) + (proper: 2) + (x absent: 4) + (y absent: 8) + (x present, s(x) = 1: 16) + (y present, s(y) = 1: 32)
+ *     RNAME POS   x present: x's name by fmgpu_positions_sam's RNAME rule and p(x) + 1; x absent, y present: y's (the unmapped mate is placed at its mate); else * 0
+ *     MAPQ   x absent: 0; proper: mapq_unique if exactly one pair record of the fragment has the minimal error sum, else mapq_multi; else fmgpu_positions_sam's rule
+ *     CIGAR  "<m>M" if x is present, cigar == 1 and m > 0, else '*'
+ *     RNEXT  both absent: '*'; exactly one absent, or both on one seq_id: '='; else y's RNAME
+ *     PNEXT  y present: p(y) + 1; y absent, x present: p(x) + 1; else 0
+ *     TLEN   both present on one seq_id: t = max(e(x), e(y)) - min(p(x), p(y)); the mate with the smaller pos writes t, the other -t, with equal pos A writes t and B
+ *            -t; t = 0 is written as 0; in every other case 0
+ *     SEQ QUAL    fmgpu_positions_sam's rules for the strand of x, forward if x is absent; m = 0 gives '*', a quality span with len 0 gives '*'
+ *     tags   NM:i:<errors of x> NH:i:<records of this mate's read> if x is present, none otherwise
+ *   - out_line_off: NULL, or 2 n_fragments + 1 entries, the last = *out_bytes; written whenever the call gets past its checks, also on FMGPU_ERR_CAPACITY.  *out_bytes is
+ *     exact on success and on FMGPU_ERR_CAPACITY alike (then nothing is written to `out`); out == NULL with capacity == 0 is the counting call.  n_fragments == 0 returns 0
+ *     behind the argument checks with zero bytes and out_line_off[0] = 0.
+ *   - Before the first use of the device, FMGPU_ERR_INVALID, each with a message of its own, for: a null spec, char_of or out_bytes; a null qbuf_a or qoff_a while
+ *     n_fragments > 0; interleaved, cigar or strip_mate_suffix outside 0 .. 1; reserved != 0; in interleaved mode a qbuf_b, qoff_b, quals_b, positions_b or count_b that
+ *     is set, in separate mode a null qbuf_b or qoff_b while n_fragments > 0; null positions or null pairs while their count is > 0; a null out while capacity > 0; a
+ *     strands with a null complement or n outside 1 .. 256; a table with a null bytes while n_bytes > 0 or a null spans while count > 0.  Then FMGPU_ERR_UNSUPPORTED where
+ *     count_a, count_b or n_pairs reaches 2^32 - 256 or n_fragments reaches 2^31 - 1.
+ *   - On the device, FMGPU_ERR_INVALID, looked for in this order and for A before B; nothing is written (out_line_off neither) and the message names the array and the
+ *     lowest offender: a record whose read lies beyond its batch; a record whose read lies below its predecessor's; a read whose offsets decrease; a record with
+ *     pos >= 2^62; a pair ("pair i") whose fragment is >= n_fragments, whose a or b lies beyond its array, or whose record a or b does not belong to mate A or mate B of
+ *     that fragment; then per line in line order ("fragment f mate A" / "mate B") and inside a line in this order: the read_names row beyond its table or its span
+ *     beyond the bytes, the same for the quality row, a quality span whose len is neither 0 nor m, the same two for the seq_names row of RNAME and then of RNEXT.  A read
+ *     of 2^31 symbols or more, a name or quality span of 2^31 bytes or more, or a line of 2^32 bytes or more returns FMGPU_ERR_UNSUPPORTED in the same way; an
+ *     FMGPU_ERR_INVALID line anywhere goes first.
+ *   - Every array (positions, pairs, qbuf, qoff, out, out_line_off, the bytes and spans of each table) may be host or device memory; host arrays are staged.  The spec,
+ *     char_of and complement are host memory.  A device `out` needs no alignment (the windows of fmgpu_positions_sam).
+ *   - Passes: per record of A and of B (range, order, pos, each read's records and primary), per record (records at the minimum), per pair (validity, the minimal key per
+ *     fragment), per pair (pairs at the minimum), per fragment (offsets of its two reads, the record of each mate), per line (length, names and spans), one scan to 64-bit
+ *     offsets, ONE read-back (size, error words, the symbols of the batches), the write pass over 16 KiB windows of the output.  No lane loops over a fragment's records
+ *     or pairs.  The call returns after completion and frees its scratch: 84 bytes per fragment (24 per mate, 12 for the chosen pair, 12 per line), nothing per record or per pair, plus the scan's own.
+ * Not built: secondary or supplementary lines, MC / MQ tags, CIGAR for edit-distance hits, RF / FF orientations, rescue of an unmapped mate, insert-size estimation, a
+ * call that maps, joins and writes, paired SAM per chunk in the feeds, BAM. */
+typedef struct fmgpu_sam_mates_spec {      /* 96 bytes, host memory */
+    const uint8_t*  qbuf_a;                /* the FORWARD batch of mate A (interleaved: the one batch, 2 n_fragments reads); host or device */
+    const uint64_t* qoff_a;                /* its reads + 1 entries, qoff[0] need not be 0 */
+    const uint8_t*  qbuf_b;                /* the batch of mate B; NULL in interleaved mode */
+    const uint64_t* qoff_b;
+    uint64_t        n_fragments;
+    const uint8_t*  char_of;               /* host, 256 entries: the SEQ byte of symbol value c */
+    const fmgpu_strands* strands;          /* NULL: strand 0 everywhere, read = qidx.  Else read = qidx >> 1, strand = qidx & 1; `pair` is ignored */
+    const fmgpu_name_table* read_names;    /* NULL: QNAME = the fragment's number in decimal; else the rows of batch A's reads */
+    const fmgpu_name_table* quals_a;       /* NULL: QUAL = '*' */
+    const fmgpu_name_table* quals_b;       /* the same for batch B; NULL in interleaved mode */
+    const fmgpu_name_table* seq_names;     /* NULL: RNAME = seq_id in decimal */
+    uint8_t interleaved;                   /* 0: two batches, fragment = read; 1: one batch, fragment = read >> 1, mate = read & 1 */
+    uint8_t cigar;                         /* 0: '*';  1: "<m>M" (the caller states the search was ungapped) */
+    uint8_t strip_mate_suffix;             /* 1: a QNAME of 3 bytes or more that ends in "/1" or "/2" loses those two bytes */
+    uint8_t mapq_unique, mapq_multi;
+    uint8_t reserved[3];                   /* 0 */
+} fmgpu_sam_mates_spec;
+int fmgpu_positions_sam_mates(const fmgpu_position* positions_a, uint64_t count_a,
+                              const fmgpu_position* positions_b, uint64_t count_b,
+                              const fmgpu_mate_pair* pairs, uint64_t n_pairs,
+                              const fmgpu_sam_mates_spec* spec,
+                              uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* out_line_off, void* stream);
 
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
