@@ -14,13 +14,13 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import FmgpuError, DeviceBuffer, PinnedBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE, TEXT_SPAN_DTYPE, MATE_PAIR_DTYPE
+from .capi import FmgpuError, DeviceBuffer, PinnedBuffer, LAYOUTS, UINT64_MAX, HIT_DTYPE, POSITION_DTYPE, TEXT_RANGE_DTYPE, SEED_SPAN_DTYPE, TEXT_SPAN_DTYPE, MATE_PAIR_DTYPE, CHAIN_DTYPE
 from . import search_scheme  # noqa: F401
 
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer",
-           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "join_mates", "MatePairs", "format_sam_mates", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
+           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "join_mates", "MatePairs", "format_sam_mates", "chain_seeds", "SeedChains", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
 
 
 class _Options:
@@ -1745,6 +1745,59 @@ def join_mates(positions_a, qoff_a, positions_b=None, qoff_b=None, strands=True,
                                        capi.ptr(cls), sp))
     del keep_a, keep_b, offs
     return MatePairs(pairs[:int(total.value)], off, cls[:n])
+
+
+# ---- located seeds joined to collinear chains on the device (fmgpu_seeds_chain)
+class SeedChains:
+    """what chain_seeds returns: chains (a CHAIN_DTYPE array in output order: queries ascending, inside a query the best chain first), off (uint64, nq + 1 entries: each
+    query's first chain), cls (uint8 per query, an index into capi.CHAIN_CLASSES) and anchors (uint32: the indices into `positions` of every chain's anchors, chain k's at
+    [first, first + n_anchors); None without want_anchors)"""
+
+    def __init__(self, chains, off, cls, anchors):
+        self.chains, self.off, self.cls, self.anchors = chains, off, cls, anchors
+
+    def __len__(self):
+        return len(self.chains)
+
+    def anchors_of(self, k):
+        """the indices into `positions` of chain k's anchors, first to last"""
+        if self.anchors is None:
+            raise ValueError("chain_seeds(want_anchors=False) kept no anchors")
+        c = self.chains[k]
+        return self.anchors[int(c["first"]): int(c["first"]) + int(c["n_anchors"])]
+
+
+def chain_seeds(positions, spans, nq, max_gap=5000, max_skew=500, gap_cost=0.5, max_lookback=64, min_score=0, min_anchors=1, max_chains=0, max_anchors=0,
+                want_anchors=True, stream=None):
+    """fmgpu_seeds_chain: the located seeds of every query joined to collinear chains, on the device.  positions: what index.locate_hits returned for the hits of
+    search_smems (a POSITION_DTYPE array, or a DeviceBuffer / torch tensor of such records); spans: the SEED_SPAN_DTYPE records of the same search_smems call (array or
+    DeviceBuffer); nq: the queries in the numbering of qidx (twice the reads for a both_strands batch).  A link needs 1 <= dt, dq <= max_gap and |dt - dq| <= max_skew and
+    costs gap_cost per base of skew (kept in 8 fractional bits); max_lookback (1 .. 256) candidates are looked at per anchor.  A chain is reported with score >= min_score
+    and at least min_anchors anchors, max_chains > 0 keeps the best max_chains per query, max_anchors > 0 leaves a query with more anchors out (class 3).  Returns a
+    SeedChains (chains, off, cls, anchors); the counting call sizes `chains` exactly."""
+    pp, count, keep_p = _records(positions)
+    if isinstance(spans, np.ndarray):
+        spans = np.ascontiguousarray(spans, dtype=SEED_SPAN_DTYPE)
+    sp_ptr, sp_bytes = _buffer(spans)
+    n_spans = sp_bytes // SEED_SPAN_DTYPE.itemsize
+    q8 = int(round(float(gap_cost) * 256))
+    if q8 < 0:
+        raise ValueError("gap_cost is not negative")
+    nq = int(nq)
+    spec = capi.ChainSpec(nq, int(max_gap), int(max_skew), q8, int(max_lookback), int(min_score), int(min_anchors), int(max_chains), int(max_anchors), (C.c_uint8 * 8)())
+    sp = None if stream is None else C.c_void_p(stream if isinstance(stream, int) else getattr(stream, "cuda_stream", 0))
+    L, total = capi.lib(), C.c_uint64()
+    args = (pp, count, sp_ptr if n_spans else None, n_spans, C.byref(spec))
+    capi.check(L.fmgpu_seeds_chain(*args, None, 0, C.byref(total), None, None, None, sp))                 # the counting call sizes the chains exactly
+    chains = np.zeros(int(total.value), dtype=CHAIN_DTYPE)
+    off, cls = np.zeros(nq + 1, dtype=np.uint64), np.zeros(max(nq, 1), dtype=np.uint8)
+    anchors = np.zeros(max(count, 1), dtype=np.uint32) if want_anchors else None
+    capi.check(L.fmgpu_seeds_chain(*args, capi.ptr(chains) if chains.size else None, chains.size, C.byref(total), capi.ptr(anchors) if want_anchors else None,
+                                   capi.ptr(off), capi.ptr(cls), sp))
+    del keep_p
+    if want_anchors:
+        anchors = np.ascontiguousarray(anchors[: int(chains["n_anchors"].sum(dtype=np.uint64))])
+    return SeedChains(chains[: int(total.value)], off, cls[:nq], anchors)
 
 
 # ---- positions and mate pairs to paired-end SAM records on the device (fmgpu_positions_sam_mates)

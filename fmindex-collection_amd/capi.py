@@ -216,6 +216,27 @@ class SamMatesSpec(C.Structure):
 
 
 assert C.sizeof(SamMatesSpec) == 96
+
+
+class Chain(C.Structure):
+    """fmgpu_chain: one collinear chain of located seeds (fmgpu_seeds_chain)"""
+    _fields_ = [("qidx", C.c_uint64), ("seq_id", C.c_uint64), ("tbeg", C.c_uint64), ("tend", C.c_uint64), ("qbeg", C.c_uint32), ("qend", C.c_uint32),
+                ("score", C.c_uint32), ("n_anchors", C.c_uint32), ("first", C.c_uint32), ("flags", C.c_uint32)]
+
+
+CHAIN_DTYPE = np.dtype([("qidx", "<u8"), ("seq_id", "<u8"), ("tbeg", "<u8"), ("tend", "<u8"), ("qbeg", "<u4"), ("qend", "<u4"), ("score", "<u4"), ("n_anchors", "<u4"),
+                        ("first", "<u4"), ("flags", "<u4")])
+assert CHAIN_DTYPE.itemsize == C.sizeof(Chain) == 56
+
+
+class ChainSpec(C.Structure):
+    """fmgpu_chain_spec: the query count, the link conditions, the filters and the guards of fmgpu_seeds_chain (host memory)"""
+    _fields_ = [("nq", C.c_uint64), ("max_gap", C.c_uint32), ("max_skew", C.c_uint32), ("gap_cost_q8", C.c_uint32), ("max_lookback", C.c_uint32),
+                ("min_score", C.c_uint32), ("min_anchors", C.c_uint32), ("max_chains", C.c_uint32), ("max_anchors", C.c_uint32), ("reserved", C.c_uint8 * 8)]
+
+
+assert C.sizeof(ChainSpec) == 48
+CHAIN_CLASSES = ("none", "chained", "filtered", "skipped")
 MATES_FR, MATES_ANY = 0, 1
 MATE_CLASSES = ("none", "only_a", "only_b", "discordant", "paired", "skipped")
 COL_QIDX, COL_SEQ_ID, COL_POS, COL_ERRORS, COL_HIT, COL_READ, COL_STRAND, COL_READ_NAME, COL_SEQ_NAME = range(9)
@@ -249,6 +270,7 @@ EXPORTS = [
     "fmgpu_positions_sam", "fmgpu_sam_header",
     "fmgpu_positions_mates",
     "fmgpu_positions_sam_mates",
+    "fmgpu_seeds_chain",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -417,6 +439,9 @@ def lib():
     if hasattr(L, "fmgpu_positions_sam_mates"):
         L.fmgpu_positions_sam_mates.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(SamMatesSpec), C.c_void_p, C.c_uint64, u64p,
                                                 C.c_void_p, C.c_void_p]
+    if hasattr(L, "fmgpu_seeds_chain"):
+        L.fmgpu_seeds_chain.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(ChainSpec), C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

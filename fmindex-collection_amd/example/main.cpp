@@ -35,6 +35,9 @@
 //     --mates are the two mates of fragment i.  Both files are mapped as --mode map maps one, and the positions are joined on the device (fmgpu_positions_mates
 //     through fmc::joinMates) with --min_tlen / --max_tlen (0 / 1000): with both strands a pair is concordant in FR orientation, with --no-reverse in any.
 //     --save_output gets "fragment seqId posA strandA posB strandB tlen errors" per pair, strands as + / -.
+//   * --chain-seeds (not in the reference; --mode map, not --packed, --feed, --pair-strands, --device-format, --sam or --mates): in place of the scheme search the
+//     seeds of every read (fmgpu_search_smems: --min_seed, default 19; --max_seed_rows, default 50) are located (fmgpu_locate_hits) and joined to collinear chains on
+//     the device (fmgpu_seeds_chain through fmc::chainSeeds).  --save_output gets "qidx seq_id tbeg tend qbeg qend score n_anchors" per chain.
 //   * --paired-sam (not in the reference; only with --mates): the --save_output file is a paired-end SAM file instead of the pair lines: the header of --sam
 //     followed by two records per fragment made on the device (fmgpu_positions_sam_mates through fmc::formatSamMates) from the positions of the two files and the
 //     joined pairs: a fragment with pairs takes the one with the fewest errors and is proper, elsewhere each mate takes its primary record.  QNAME = the fragment's
@@ -75,7 +78,8 @@ struct Options {
     size_t firstK = 0, lastK = 6, stepK = 1;
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
     size_t minTlen = 0, maxTlen = 1000;                          // --mates: the template lengths of a concordant pair, inclusive
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false, sam = false, pairedSam = false;
+    size_t minSeed = 19, maxSeedRows = 50;                       // --chain-seeds: the shortest seed kept, the most rows a kept seed may have (0 = no limit)
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false, sam = false, pairedSam = false, chainSeeds = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -125,6 +129,9 @@ FlagRule const kFlags[] = {
     {"--paired-sam", false, [](Options& o, char const*) { o.pairedSam = true; }},
     {"--min_tlen", true, [](Options& o, char const* v) { o.minTlen = asCount(v); }},
     {"--max_tlen", true, [](Options& o, char const* v) { o.maxTlen = asCount(v); }},
+    {"--chain-seeds", false, [](Options& o, char const*) { o.chainSeeds = true; }},
+    {"--min_seed", true, [](Options& o, char const* v) { o.minSeed = asCount(v); }},
+    {"--max_seed_rows", true, [](Options& o, char const* v) { o.maxSeedRows = asCount(v); }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
     {"--ext", true, [](Options&, char const*) {}},
     {"--threads", true, [](Options&, char const*) {}},
@@ -398,6 +405,7 @@ struct Run {
             for (size_t j = 0; j <= k; ++j) query.expanded.push_back(stretch(schemeByName(config.schemeName, j, j), firstLength));
         }
         if constexpr (!std::is_same_v<Queries, fmc::PackedQueries>) if (mateReads) return matesMapped(reads, query, k, clock);
+        if constexpr (!std::is_same_v<Queries, fmc::PackedQueries>) if (config.chainSeeds) return seedsChained(reads, k, clock);
         auto const mapped = config.feed ? mapThroughFeed(reads, query) : mapAtOnce(reads, query);
         double const tMap = clock.reset();
         std::string sam;
@@ -459,6 +467,38 @@ struct Run {
                          bothStrands && (a.qidx & 1) ? '-' : '+', static_cast<size_t>(b.pos), bothStrands && (b.qidx & 1) ? '-' : '+', static_cast<size_t>(p.tlen),
                          static_cast<size_t>(p.errors));
         }
+        std::fclose(out);
+    }
+
+    // --chain-seeds: in place of the scheme search the seeds of every read (fmgpu_search_smems through fmc::search_smems: --min_seed, --max_seed_rows), located
+    // (fmgpu_locate_hits) and joined to collinear chains on the device (fmgpu_seeds_chain through fmc::chainSeeds).  Every read of the batch is a query of its own,
+    // a reverse complement too.  --save_output gets "qidx seq_id tbeg tend qbeg qend score n_anchors" per chain, in the call's output order.
+    void seedsChained(std::vector<std::vector<uint8_t>> const& reads, size_t k, StopWatch& clock) const {
+        std::vector<fmgpu_hit> seeds;
+        std::vector<fmgpu_seed_span> spans;
+        fmc::search_smems(index, reads, config.minSeed, config.maxSeedRows, [&](size_t read, auto const& cursor, size_t qbeg, size_t qlen) {
+            fmgpu_hit h{};
+            h.qidx = read; h.lb = cursor.lb; h.len = cursor.len;
+            seeds.push_back(h);
+            spans.push_back({static_cast<uint32_t>(qbeg), static_cast<uint32_t>(qlen)});
+        });
+        double const tSeeds = clock.reset();
+        auto const anchors = index.locateHits(seeds);
+        double const tLocate = clock.reset();
+        fmc::ChainSpec spec;
+        spec.queries = reads.size();
+        spec.wantAnchors = false;
+        auto const chained = fmc::chainSeeds(anchors, spans, spec);
+        double const tChain = clock.reset();
+        size_t const with = static_cast<size_t>(std::count(chained.classes.begin(), chained.classes.end(), uint8_t{1}));
+        std::printf("%-15s %3zu: %10.3gs (%10.3gs +%10.3gs +%10.3gs ) - seeds: %10zu anchors: %10zu chains: %10zu in %10zu of %10zu queries\n", "chain-seeds", k,
+                    tSeeds + tLocate + tChain, tSeeds, tLocate, tChain, seeds.size(), anchors.size(), chained.chains.size(), with, reads.size());
+        if (config.outputFile.empty()) return;
+        auto* out = std::fopen(config.outputFile.c_str(), "w");
+        if (!out) throw std::runtime_error("cannot write " + config.outputFile);
+        for (auto const& c : chained.chains)
+            std::fprintf(out, "%zu %zu %zu %zu %zu %zu %zu %zu\n", static_cast<size_t>(c.qidx), static_cast<size_t>(static_cast<uint32_t>(c.seq_id)), static_cast<size_t>(c.tbeg),
+                         static_cast<size_t>(c.tend), static_cast<size_t>(c.qbeg), static_cast<size_t>(c.qend), static_cast<size_t>(c.score), static_cast<size_t>(c.n_anchors));
         std::fclose(out);
     }
 
@@ -591,6 +631,10 @@ int main(int argc, char const* const* argv) try {
                     "          --paired-sam (only with --mates: the --save_output file is a paired-end SAM file, the header of --sam and two records per\\\n"
                     "                 fragment made on the device: the pair with the fewest errors where there is one, else each mate's best record)\\\n"
                     "          --min_tlen <int> --max_tlen <int> (--mates: the template lengths of a concordant pair, inclusive; 0 and 1000)\\\n"
+                    "          --chain-seeds (--mode map, not --packed, --feed, --pair-strands, --device-format, --sam or --mates: in place of the scheme search\\\n"
+                    "                 the seeds of every read are located and joined to collinear chains on the device: --save_output gets\\\n"
+                    "                 \"qidx seq_id tbeg tend qbeg qend score n_anchors\" per chain)\\\n"
+                    "          --min_seed <int> --max_seed_rows <int> (--chain-seeds: the shortest seed kept, the most rows of a kept seed; 19 and 50)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
     }
@@ -603,6 +647,9 @@ int main(int argc, char const* const* argv) try {
     if (!config.matesFasta.empty() && (config.packed || config.deviceFormat || config.readLimit != 0)) throw std::runtime_error("--mates needs byte reads (no --packed), no --device-format and no --queries");
     if (config.pairedSam && config.matesFasta.empty()) throw std::runtime_error("--paired-sam needs --mates");
     if (config.minTlen > config.maxTlen) throw std::runtime_error("--min_tlen lies above --max_tlen");
+    if (config.chainSeeds && config.hitMode != HitMode::map) throw std::runtime_error("--chain-seeds needs --mode map");
+    if (config.chainSeeds && (config.packed || config.feed || config.pairStrands || config.deviceFormat || config.sam || !config.matesFasta.empty()))
+        throw std::runtime_error("--chain-seeds needs byte reads (no --packed) and does not go with --feed, --pair-strands, --device-format, --sam or --mates");
     auto withReference = [&](Run& run) {                              // --sam: what the header and RNAME are made of
         if (!config.sam && !config.pairedSam) return;
         auto const reference = readFasta(config.referenceFasta, Sigma, config.unknownToA);

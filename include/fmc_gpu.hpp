@@ -1467,6 +1467,45 @@ auto joinMates(std::vector<fmgpu_position> const& positions, Queries const& inte
     return detail::joinMates(positions, off, nullptr, nullptr, spec);
 }
 
+// Seed chains (include/fmgpu.h: fmgpu_seeds_chain): fmc::chainSeeds(positions, spans, spec) joins the located seeds of every query — the positions of
+// index.locateHits for the hit records of fmgpu_search_smems, with that call's seed spans — to collinear chains on the device, best first inside a query.
+// spec.queries counts the queries in the numbering of qidx (twice the reads for a both-strand batch).
+struct ChainSpec {
+    uint64_t queries{0};
+    uint32_t maxGap{5000}, maxSkew{500};                                     // a link needs 1 <= dt, dq <= maxGap and |dt - dq| <= maxSkew
+    double   gapCost{0.5};                                                   // per base of skew, kept in 8 fractional bits
+    uint32_t maxLookback{64};                                                // 1 .. 256 candidates per anchor
+    uint32_t minScore{0}, minAnchors{1};
+    uint32_t maxChains{0};                                                   // > 0: the best maxChains of a query
+    uint32_t maxAnchors{0};                                                  // > 0: a query with more anchors is left out (class 3)
+    bool     wantAnchors{true};
+};
+struct SeedChains {
+    std::vector<fmgpu_chain> chains;                                         // queries ascending, inside a query by descending score, then by the first anchor's place
+    std::vector<uint64_t>    offsets;                                        // queries + 1 entries: each query's first chain
+    std::vector<uint8_t>     classes;                                        // per query: 0 no anchor, 1 chained, 2 nothing past the filters, 3 left out by maxAnchors
+    std::vector<uint32_t>    anchors;                                        // chain k's anchors, indices into positions: [chains[k].first, + chains[k].n_anchors)
+};
+inline auto chainSeeds(std::vector<fmgpu_position> const& positions, std::vector<fmgpu_seed_span> const& spans, ChainSpec const& spec) -> SeedChains {
+    if (!(spec.gapCost >= 0.0) || spec.gapCost > 256.0) throw std::runtime_error("fmindex-collection (gpu): gapCost lies in 0 .. 256");
+    fmgpu_chain_spec s{};
+    s.nq = spec.queries; s.max_gap = spec.maxGap; s.max_skew = spec.maxSkew; s.gap_cost_q8 = static_cast<uint32_t>(spec.gapCost * 256.0 + 0.5);
+    s.max_lookback = spec.maxLookback; s.min_score = spec.minScore; s.min_anchors = spec.minAnchors; s.max_chains = spec.maxChains; s.max_anchors = spec.maxAnchors;
+    fmgpu_position const* p = positions.empty() ? nullptr : positions.data();
+    fmgpu_seed_span const* sp = spans.empty() ? nullptr : spans.data();
+    uint64_t count = 0;
+    detail::check(fmgpu_seeds_chain(p, positions.size(), sp, spans.size(), &s, nullptr, 0, &count, nullptr, nullptr, nullptr, nullptr));     // the counting call sizes the chains exactly
+    SeedChains out;
+    out.chains.resize(count); out.offsets.assign(s.nq + 1, 0); out.classes.assign(s.nq, 0);
+    if (spec.wantAnchors) out.anchors.assign(positions.size(), 0);
+    detail::check(fmgpu_seeds_chain(p, positions.size(), sp, spans.size(), &s, count ? out.chains.data() : nullptr, count, &count,
+                                    out.anchors.empty() ? nullptr : out.anchors.data(), out.offsets.data(), out.classes.empty() ? nullptr : out.classes.data(), nullptr));
+    uint64_t used = 0;
+    for (auto const& c : out.chains) used += c.n_anchors;
+    if (spec.wantAnchors) out.anchors.resize(used);
+    return out;
+}
+
 // Paired-end SAM (include/fmgpu.h: fmgpu_positions_sam_mates): fmc::formatSamMates(positionsA, readsA, positionsB, readsB, pairs, spec) is two alignment lines per
 // fragment, line 2f for mate A and line 2f + 1 for mate B, with the mate fields filled in (flags 1, 2, 8, 32, 64, 128, RNEXT, PNEXT, TLEN), formatted on the device from
 // the positions fmc::map returned for the two FORWARD batches and the pairs fmc::joinMates made of them (its result, or any array of pair records).  A fragment with

@@ -1250,6 +1250,77 @@ int fmgpu_positions_sam_mates(const fmgpu_position* positions_a, uint64_t count_
                               const fmgpu_sam_mates_spec* spec,
                               uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* out_line_off, void* stream);
 
+/* ---- located seeds to collinear chains on the device ------------------------------------------------------------------------------------------
+ * fmgpu_seeds_chain takes the positions fmgpu_locate_hits returned for the records of fmgpu_search_smems, with the seed spans, and says which anchors belong together:
+ * every query's anchors joined to collinear chains, best first.  A chain gives the approximate mapping position of a read no search scheme reaches, and the window for
+ * an aligner behind it.  It needs no index handle: it reads position records and seed spans only.  Every other call and struct is as it was.
+ *   - Input: qidx does not decrease over `positions`; hit indexes `spans`; errors is ignored.  Anchor i is (qidx, seq_id, t = pos, q = spans[hit].qbeg,
+ *     l = spans[hit].qlen).  The two strands of a read in the both-strand numbering are two queries: a chain never mixes qidx values.
+ *   - Order: inside a query the anchors are ordered by (seq_id, t, q, index in `positions`).  A run is a maximal stretch with one (qidx, seq_id).
+ *   - Scores: for anchor i the candidates j are the up to max_lookback anchors directly in front of it in its run.  A candidate must satisfy dt = t_i - t_j >= 1,
+ *     dq = q_i - q_j >= 1, dt <= max_gap, dq <= max_gap and dd = |dt - dq| <= max_skew.  gain = min(l_i, dq, dt) - ((gap_cost_q8 * dd) >> 8), in 64 bits; a candidate
+ *     counts only with gain >= 1.  value = f(j) + gain.  f(i) = l_i with no predecessor, unless the best value is GREATER than l_i: then f(i) = that value and p(i) = the
+ *     candidate that gave it, among equal values the one nearest to i in the order.  f grows strictly along links, and with q + l < 2^31 every f is below 2^32.
+ *   - Chains (minimap2's rule, best ends first and backtrack until a used anchor, stated so that it runs in parallel): t(i) = the largest f over the anchors reachable
+ *     from i through links, i included.  The heir of j is its child with the largest t, among equals the child earliest in the order.  A chain starts at every anchor that
+ *     is not the heir of its predecessor and follows heirs to a leaf.  Its score is f(leaf), or f(leaf) - f(p(start)) if the start has a predecessor; then bit 0 of flags
+ *     is set: a branch off a better chain.
+ *   - Filters: a chain is reported if score >= min_score and n_anchors >= max(min_anchors, 1).  max_chains then applies to what remains.
+ *   - Output order: ascending qidx; inside a query descending score, then the place of the chain's first anchor in the order above.  out_anchor: NULL, or `count`
+ *     entries: for the reported chains only and in output order the indices into `positions` of each chain's anchors, first to last (chain k: out_anchor[first ..
+ *     first + n_anchors)); what lies behind them is unspecified.  out_off: NULL, or nq + 1 entries: each query's first chain, the last entry = *out_count.  out_class:
+ *     NULL, or nq bytes: 0 no anchor; 1 at least one chain reported; 2 anchors, but no chain past the filters; 3 left out by max_anchors.
+ *   - *out_count is exact on success and on FMGPU_ERR_CAPACITY alike (then nothing is written to `out` or out_anchor); out_off and out_class are written whenever the call
+ *     gets past its checks; out == NULL with capacity == 0 is the counting call.  nq == 0 or count == 0 returns 0 (behind the checks of the next item) with
+ *     *out_count = 0, offsets 0 and classes 0.
+ *   - Before the first use of the device, FMGPU_ERR_INVALID, each with a message of its own, for: a null spec or out_count; max_gap or max_skew outside 1 .. 2^31 - 1;
+ *     gap_cost_q8 above 65536; max_lookback outside 1 .. 256; reserved != 0; null positions or spans while count > 0; a null out while capacity > 0.  Then
+ *     FMGPU_ERR_UNSUPPORTED where count or n_spans reaches 2^32 - 256.
+ *   - On the device, FMGPU_ERR_INVALID, looked for in this order; nothing is written (out_off and out_class neither, *out_count = 0) and the message names the lowest
+ *     offending record: qidx >= nq; a qidx below its predecessor's; hit >= n_spans; pos >= 2^62; a record whose span has qlen == 0 or qbeg + qlen >= 2^31 (spans no
+ *     record names are not looked at).
+ *   - Every array (positions, spans, out, out_anchor, out_off, out_class) may be host or device memory; host arrays are staged.  The spec is host memory.
+ *   - Passes: per record (the checks, each query's records); the order by four stable hipcub radix sorts of index values (q, t, seq_id, qidx); a gather into 16-byte
+ *     anchor records that also settles the runs of one anchor; run boundaries; three sweeps per run (f and p forward; t, heir, chain length and leaf backward; each
+ *     anchor's chain start and rank forward), runs of up to 32 anchors one per lane, longer runs one per wave with the last max_lookback anchors in an LDS ring and one
+ *     cross-lane maximum per step; filters and two scans; ONE read-back (the number of chains, the error words); one sort of the kept chains; chain records; a scatter
+ *     in which every anchor writes itself to first + rank.  No lane walks a chain or loops over more than max_lookback candidates, nothing is quadratic in a run.
+ *   - Cost of long runs: a run of n anchors takes n x ceil(max_lookback / 64) wave steps in each of the first two sweeps and n in the third, one behind the other on ONE
+ *     wave: a single run of 10^5 anchors (a read of a tandem repeat) is 10^5 x ceil(max_lookback / 64) dependent steps per sweep and bounds the call, however small the
+ *     rest of the batch.  max_anchors is the caller's guard for it, beside fmgpu_search_smems' max_rows.
+ *   - The call returns after completion and frees its scratch: 85 bytes per anchor (24 the sorts, 16 the anchor record, 45 the sweeps' and the passes' words), 25 per
+ *     query, 12 per reported chain, plus hipcub's own.
+ * Not built: extension or alignment of chains, chains across the two strands of a query, MAPQ, chaining inside fmgpu_map or the feeds, rescue of an unmapped mate. */
+typedef struct fmgpu_chain {               /* 56 bytes */
+    uint64_t qidx, seq_id;
+    uint64_t tbeg, tend;                   /* pos of the first anchor; pos + qlen of the last */
+    uint32_t qbeg, qend;                   /* qbeg of the first anchor; qbeg + qlen of the last */
+    uint32_t score, n_anchors;
+    uint32_t first;                        /* the chain's anchors are out_anchor[first .. first + n_anchors) */
+    uint32_t flags;                        /* bit 0: a branch: the chain's first anchor has a predecessor in a better chain, score = f(leaf) - f(that predecessor) */
+} fmgpu_chain;
+typedef struct fmgpu_chain_spec {          /* 48 bytes, host memory */
+    uint64_t nq;                           /* queries in the numbering of qidx (doubled for the both-strand numbering) */
+    uint32_t max_gap, max_skew;            /* each 1 .. 2^31 - 1 */
+    uint32_t gap_cost_q8;                  /* 0 .. 65536: penalty per base of skew, 8 fractional bits */
+    uint32_t max_lookback;                 /* 1 .. 256 */
+    uint32_t min_score, min_anchors;
+    uint32_t max_chains;                   /* 0 = all; else the first max_chains of a query in output order */
+    uint32_t max_anchors;                  /* 0 = no limit; else a query with more anchors is left out (class 3) */
+    uint8_t  reserved[8];                  /* 0 */
+} fmgpu_chain_spec;
+#ifdef __cplusplus
+static_assert(sizeof(fmgpu_chain) == 56 && sizeof(fmgpu_chain_spec) == 48, "fmgpu_chain / fmgpu_chain_spec: the sizes stated above");
+#endif
+int fmgpu_seeds_chain(const fmgpu_position* positions, uint64_t count,
+                      const fmgpu_seed_span* spans, uint64_t n_spans,
+                      const fmgpu_chain_spec* spec,
+                      fmgpu_chain* out, uint64_t capacity, uint64_t* out_count,
+                      uint32_t* out_anchor,   /* NULL, or `count` entries */
+                      uint64_t* out_off,      /* NULL, or nq + 1 entries */
+                      uint8_t* out_class,     /* NULL, or nq bytes */
+                      void* stream);
+
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
 int fmgpu_free(void* ptr);
