@@ -24,12 +24,12 @@
 // caller's guard.  Every pass behind the first reads the error words and does nothing once one is set.
 // Scratch: 85 bytes per anchor (24 the sorts' keys and index values, 16 the anchor record, 32 the sweeps' eight words, 13 flags, scan, run and slot words) and 0.25 for the
 // list of long runs, 25 per query, 12 per kept chain, plus hipcub's own; freed on return.
+// The run boundaries of the first pass (run_edges) and the hipcub calls written once (cub_size, cub_run) are fmgpu_positions.h's.
 #include "fmgpu_positions.h"
 
 namespace fmgpu {
 namespace {
 
-constexpr uint64_t kNone = ~0ull;
 constexpr uint32_t kNo = 0xffffffffu;
 constexpr uint64_t kMaxChainRecords = (1ull << 32) - 256;
 constexpr uint64_t kPosLimit = 1ull << 62;
@@ -451,14 +451,15 @@ int fmgpu_seeds_chain(const fmgpu_position* positions, uint64_t count, const fmg
     while (q_bits < 64 && (nq - 1) >> q_bits) ++q_bits;
 
     Bits run_starts(a.flag, BitOf{F_START}), kept_starts(a.flag, BitOf{F_KEEP});
-    size_t tb = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, run_starts, a.scan, (size_t)(count + 1), stream));
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, a.qcount, a.qoff, (size_t)(nq + 1), stream));
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t3, (uint32_t*)k0, (uint32_t*)k1, v0, v1, (size_t)count, 0, 31, stream));
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t4, k0, k1, v1, v0, (size_t)count, 0, 62, stream));
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t5, k0, k1, v0, v1, (size_t)count, 0, 64, stream));
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t6, k0, k1, v1, v0, (size_t)count, 0, q_bits, stream));
-    tb = std::max(std::max(t1, t2), std::max(std::max(t3, t4), std::max(t5, t6)));
+    auto scan_runs = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, run_starts, a.scan, (size_t)(count + 1), stream); };
+    auto scan_kept = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, kept_starts, a.scan, (size_t)(count + 1), stream); };
+    auto scan_queries = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, a.qcount, a.qoff, (size_t)(nq + 1), stream); };
+    auto sort_q = [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, (uint32_t*)k0, (uint32_t*)k1, v0, v1, (size_t)count, 0, 31, stream); };
+    auto sort_t = [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, v1, v0, (size_t)count, 0, 62, stream); };
+    auto sort_seq = [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, v0, v1, (size_t)count, 0, 64, stream); };
+    auto sort_qidx = [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, v1, v0, (size_t)count, 0, q_bits, stream); };
+    size_t tb = 0;
+    FM_HIP(cub_size(&tb, scan_runs, scan_kept, scan_queries, sort_q, sort_t, sort_seq, sort_qidx));
     if ((rc = tmp.alloc(tb))) return rc;
 
     FM_HIP(hipMemsetAsync(a.qfirst, 0xff, nq * 4, stream));
@@ -472,26 +473,21 @@ int fmgpu_seeds_chain(const fmgpu_position* positions, uint64_t count, const fmg
     FM_GRID(qgrid, nq + 1);
     k_chain_check<<<grid, dim3(256), 0, stream>>>(a);
     FM_LAUNCHED("k_chain_check");
-    size_t t = tb;
     k_chain_key_q<<<grid, dim3(256), 0, stream>>>(a, (uint32_t*)k0, v0);
     FM_LAUNCHED("k_chain_key_q");
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t, (uint32_t*)k0, (uint32_t*)k1, v0, v1, (size_t)count, 0, 31, stream));      // v1: by q, then index
+    FM_HIP(cub_run(sort_q, tmp));                                   // v1: by q, then index
     k_chain_key<0><<<grid, dim3(256), 0, stream>>>(a, v1, k0);
     FM_LAUNCHED("k_chain_key");
-    t = tb;
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t, k0, k1, v1, v0, (size_t)count, 0, 62, stream));                            // v0: by t, stable
+    FM_HIP(cub_run(sort_t, tmp));                                   // v0: by t, stable
     k_chain_key<1><<<grid, dim3(256), 0, stream>>>(a, v0, k0);
     FM_LAUNCHED("k_chain_key");
-    t = tb;
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t, k0, k1, v0, v1, (size_t)count, 0, 64, stream));                            // v1: by seq_id, stable
+    FM_HIP(cub_run(sort_seq, tmp));                                 // v1: by seq_id, stable
     k_chain_key<2><<<grid, dim3(256), 0, stream>>>(a, v1, k0);
     FM_LAUNCHED("k_chain_key");
-    t = tb;
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t, k0, k1, v1, v0, (size_t)count, 0, q_bits, stream));                        // v0: by qidx, stable: the order
+    FM_HIP(cub_run(sort_qidx, tmp));                                // v0: by qidx, stable: the order
     k_chain_gather<<<grid, dim3(256), 0, stream>>>(a);
     FM_LAUNCHED("k_chain_gather");
-    t = tb;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, run_starts, a.scan, (size_t)(count + 1), stream));
+    FM_HIP(cub_run(scan_runs, tmp));
     k_chain_runs<<<grid, dim3(256), 0, stream>>>(a);
     FM_LAUNCHED("k_chain_runs");
     k_chain_short<<<grid, dim3(256), 0, stream>>>(a);
@@ -500,12 +496,10 @@ int fmgpu_seeds_chain(const fmgpu_position* positions, uint64_t count, const fmg
     FM_LAUNCHED("k_chain_long");
     k_chain_keep<<<grid, dim3(256), 0, stream>>>(a);
     FM_LAUNCHED("k_chain_keep");
-    t = tb;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, kept_starts, a.scan, (size_t)(count + 1), stream));
+    FM_HIP(cub_run(scan_kept, tmp));
     k_chain_queries<<<qgrid, dim3(256), 0, stream>>>(a);
     FM_LAUNCHED("k_chain_queries");
-    t = tb;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, a.qcount, a.qoff, (size_t)(nq + 1), stream));
+    FM_HIP(cub_run(scan_queries, tmp));
     uint64_t back[2 + E_WORDS];                                     // the number of chains, the error words, the kept chain starts: the call's one read-back
     FM_HIP(hipMemcpyAsync(back, a.qoff + nq, sizeof back, hipMemcpyDeviceToHost, stream));
     FM_HIP(hipStreamSynchronize(stream));
@@ -526,21 +520,20 @@ int fmgpu_seeds_chain(const fmgpu_position* positions, uint64_t count, const fmg
     DBuf chains, tmp2;
     if ((rc = chains.alloc((kept + 2 * (total + 1)) * 4))) return rc;
     uint32_t *sorted = chains.as<uint32_t>(), *out_n = sorted + kept, *first = out_n + (total + 1);
-    size_t t7 = 0, t8 = 0;
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t7, k0, k1, v1, sorted, (size_t)kept, 0, 64, stream));
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t8, out_n, first, (size_t)(total + 1), stream));
-    if ((rc = tmp2.alloc(std::max(t7, t8)))) return rc;
+    auto sort_kept = [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, v1, sorted, (size_t)kept, 0, 64, stream); };
+    auto scan_anchors = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, out_n, first, (size_t)(total + 1), stream); };
+    size_t tb2 = 0;
+    FM_HIP(cub_size(&tb2, sort_kept, scan_anchors));
+    if ((rc = tmp2.alloc(tb2))) return rc;
     if ((rc = sout.out(out, total * sizeof(fmgpu_chain), stream))) return rc;
     k_chain_compact<<<grid, dim3(256), 0, stream>>>(a, k0, v1);
     FM_LAUNCHED("k_chain_compact");
-    t = tmp2.bytes;
-    FM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp2.p, t, k0, k1, v1, sorted, (size_t)kept, 0, 64, stream));
+    FM_HIP(cub_run(sort_kept, tmp2));
     FM_HIP(hipMemsetAsync(out_n, 0, (total + 1) * 4, stream));
     FM_GRID(kgrid, kept);
     k_chain_emit<<<kgrid, dim3(256), 0, stream>>>(a, sorted, kept, (fmgpu_chain*)sout.dev, out_n);
     FM_LAUNCHED("k_chain_emit");
-    t = tmp2.bytes;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp2.p, t, out_n, first, (size_t)(total + 1), stream));
+    FM_HIP(cub_run(scan_anchors, tmp2));
     FM_GRID(ogrid, total);
     k_chain_first<<<ogrid, dim3(256), 0, stream>>>((fmgpu_chain*)sout.dev, first, total);
     FM_LAUNCHED("k_chain_first");

@@ -7,7 +7,8 @@
 //                    OUTPUT ADDRESS, and streams LDS to global memory as aligned 16-byte stores; only the head and tail of the range leave byte by byte.  A range larger
 //                    than the LDS window (long names) is walked window by window; a name of 64 bytes and more is copied by its whole wave.
 // Scratch: 12 bytes per record (the length word and the offset) and the scan's own, freed on return.
-// The record loads, digit counts, name tables, the LDS window and its stores are fmgpu_positions.h's, shared with fmgpu_sam.hip; here: the columns and how a name is copied.
+// The record loads, digit counts, name tables, the LDS window and its stores and the end of the call behind its read-back are fmgpu_positions.h's, shared with fmgpu_sam.hip
+// and fmgpu_sam_mates.hip; here: the columns and how a name is copied.
 #include "fmgpu_positions.h"
 
 namespace fmgpu {
@@ -176,13 +177,14 @@ int fmgpu_positions_format(const fmgpu_position* positions, uint64_t count, cons
     if ((rc = lens.alloc((count + 1) * 4)) || (rc = off.alloc((count + 4) * 8))) return rc;
     uint64_t* const doff = off.as<uint64_t>();
     Widened lengths(lens.as<uint32_t>(), Widen{});
+    auto scan_lengths = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, lengths, doff, (size_t)(count + 1), stream); };
     size_t tb = 0;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lengths, doff, (size_t)(count + 1), stream));
+    FM_HIP(cub_size(&tb, scan_lengths));
     if ((rc = tmp.alloc(tb))) return rc;
     FM_HIP(hipMemsetAsync(doff + count + 1, 0xff, 24, stream));
     k_format_measure<<<mgrid, dim3(256), 0, stream>>>(dpos, count, a, aligned16, lens.as<uint32_t>(), reinterpret_cast<unsigned long long*>(doff + count + 1));
     FM_LAUNCHED("k_format_measure");
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, lengths, doff, (size_t)(count + 1), stream));
+    FM_HIP(cub_run(scan_lengths, tmp));
     uint64_t back[4] = {0, 0, 0, 0};                                // the size of the text and the error words: the call's one read-back
     FM_HIP(hipMemcpyAsync(back, doff + count, 32, hipMemcpyDeviceToHost, stream));
     FM_HIP(hipStreamSynchronize(stream));
@@ -192,15 +194,8 @@ int fmgpu_positions_format(const fmgpu_position* positions, uint64_t count, cons
                                        (row ? " names a row beyond its name table" : " has a name span that leaves the table's bytes"));
     }
     if (back[3] != kNoRecord) return fail(FMGPU_ERR_UNSUPPORTED, "fmgpu_positions_format: record " + std::to_string(back[3]) + " has a name of 2^31 bytes or more (or a line of 2^32)");
-    const uint64_t total = back[0];
-    *out_bytes = total;
-    if (out_line_off) FM_HIP(hipMemcpyAsync(out_line_off, doff, (count + 1) * 8, hipMemcpyDefault, stream));
-    if (!out && !capacity) { FM_HIP(hipStreamSynchronize(stream)); return 0; }
-    if (total > capacity) {
-        FM_HIP(hipStreamSynchronize(stream));
-        return fail(FMGPU_ERR_CAPACITY, "the text takes " + std::to_string(total) + " bytes: more than `capacity`");
-    }
-    if ((rc = sout.out(out, total, stream))) { (void)hipStreamSynchronize(stream); return rc; }
+    bool write;
+    if ((rc = text_tail(back[0], doff, count, out, capacity, out_bytes, out_line_off, sout, stream, &write)) || !write) return rc;
     FM_GRID(wgrid, ((count + 255) / 256) * 256);
     k_format_write<<<wgrid, dim3(256), 0, stream>>>(dpos, count, a, aligned16, doff, (uint8_t*)sout.dev);
     FM_LAUNCHED("k_format_write");

@@ -17,22 +17,16 @@
 //  k_mates_walk<WRITE> the same walk again: each lane writes its pairs behind its offset as whole 32-byte records
 // Every pass behind the first two reads the error words and does nothing once one is set: a batch that is out of order indexes nothing.
 // Scratch: 37 bytes per fragment (its two slots among them), 12 bytes per A-side record, 56 bytes per B-side record, plus hipcub's own; freed on return.
-// The run boundaries of the first pass (run_edges) and the host-side odds and ends are fmgpu_positions.h's, shared with fmgpu_sam.hip and fmgpu_format.hip.
-#include "fmgpu_positions.h"
+// The slots, the first pass, the staging of the two sides and the report of the error words are fmgpu_mate_slots.h's, shared with fmgpu_sam_mates.hip; the run boundaries
+// (run_edges) and the hipcub calls written once (cub_size, cub_run) are fmgpu_positions.h's.
+#include "fmgpu_mate_slots.h"
 
 namespace fmgpu {
 namespace {
 
-constexpr uint64_t kNone = ~0ull;
-constexpr uint32_t kNoRecord32 = 0xffffffffu;
-constexpr uint64_t kMaxMateRecords = (1ull << 32) - 256;
-constexpr uint64_t kMaxFragments = (1ull << 31) - 1;        // two slots per fragment, numbered in 32 bits
-constexpr uint64_t kPosLimit = 1ull << 62;
 constexpr uint64_t kStrandBit = 1ull << 63;
 
-// the error words behind out_off's scratch, in the order they are reported: the lowest record whose read lies beyond the batch (array A, array B); whose read lies
-// below its predecessor's; the lowest read whose offsets decrease; the lowest record whose pos is 2^62 or more
-enum : int { E_RANGE = 0, E_ORDER = 2, E_QOFF = 4, E_POS = 6, E_WORDS = 8 };
+enum : int { E_WORDS = E_MATE_WORDS };                      // the error words behind out_off's scratch: fmgpu_mate_slots.h's eight
 enum : uint8_t { CLS_NONE = 0, CLS_ONLY_A = 1, CLS_ONLY_B = 2, CLS_DISCORDANT = 3, CLS_PAIRED = 4, CLS_SKIPPED = 5 };
 enum : int { WALK_MIN = 0, WALK_COUNT = 1, WALK_WRITE = 2 };
 
@@ -65,16 +59,8 @@ __device__ __forceinline__ bool failed(const MatesArgs& a) {
 
 __global__ __launch_bounds__(256) void k_mates_records(MatesArgs a, int side) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const fmgpu_position* __restrict__ p = side ? a.pb : a.pa;
     const uint64_t count = side ? a.count_b : a.count_a;
-    if (i >= count) return;
-    uint64_t read;
-    bool first, last;
-    if (!run_edges(p, count, i, a.shift, a.reads, &a.err[E_RANGE + side], &a.err[E_ORDER + side], &read, &first, &last)) return;
-    if (p[i].pos >= kPosLimit) atomicMin(&a.err[E_POS + side], (unsigned long long)i);
-    const uint64_t slot = a.interleaved ? read : 2 * read + (uint64_t)side;
-    if (first) a.first[slot] = (uint32_t)i;
-    if (last) a.end[slot] = (uint32_t)i + 1u;
+    if (i < count) (void)mate_record(side ? a.pb : a.pa, count, i, side, a.shift, a.reads, a.interleaved, a.err, a.first, a.end);
 }
 
 __global__ __launch_bounds__(256) void k_mates_qoff(MatesArgs a, int side) {
@@ -235,14 +221,11 @@ int fmgpu_positions_mates(const fmgpu_position* positions_a, uint64_t count_a, c
     a.shift = spec->strand_shift; a.interleaved = spec->interleaved; a.any = spec->orientation == FMGPU_MATES_ANY; a.best = spec->best;
 
     int rc;
-    Staged spa, spb, sqa, sqb, sout;
-    if ((rc = spa.in(positions_a, count_a * sizeof(fmgpu_position), stream)) || (rc = sqa.in(spec->qoff_a, (a.reads + 1) * 8, stream))) return rc;
-    a.pa = (const fmgpu_position*)spa.dev; a.qoff_a = (const uint64_t*)sqa.dev;
-    if (spec->interleaved) { a.pb = a.pa; a.qoff_b = a.qoff_a; }
-    else {
-        if ((rc = spb.in(positions_b, count_b * sizeof(fmgpu_position), stream)) || (rc = sqb.in(spec->qoff_b, (n + 1) * 8, stream))) return rc;
-        a.pb = (const fmgpu_position*)spb.dev; a.qoff_b = (const uint64_t*)sqb.dev;
-    }
+    Staged spos[2], soff[2], sout;
+    const fmgpu_position* dpos[2];
+    const uint64_t* dqoff[2];
+    if ((rc = stage_mate_sides(positions_a, count_a, positions_b, count_b, spec->qoff_a, spec->qoff_b, n, spec->interleaved, spos, soff, dpos, dqoff, stream))) return rc;
+    a.pa = dpos[0]; a.pb = dpos[1]; a.qoff_a = dqoff[0]; a.qoff_b = dqoff[1];
     const uint64_t ca = a.count_a, cb = a.count_b;
     const bool join = ca && cb;                                     // without a record on either side there is nothing to order or to walk
 
@@ -260,18 +243,19 @@ int fmgpu_positions_mates(const fmgpu_position* positions_a, uint64_t count_a, c
     while (read_bits < 32 && (a.reads - 1) >> read_bits) ++read_bits;
 
     Widened counts(a.cnt, Widen{});
-    size_t tb = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, counts, a.rstart, (size_t)(ca + 1), stream));
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, a.fcount, a.foff, (size_t)(n + 1), stream));
+    auto scan_counts = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, counts, a.rstart, (size_t)(ca + 1), stream); };
+    auto scan_fragments = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, a.fcount, a.foff, (size_t)(n + 1), stream); };
+    auto sort_pos = [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, v0, v1, (size_t)cb, 0, 62, stream); };
+    auto sort_seq = [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0, k1, v1, v0, (size_t)cb, 0, 64, stream); };
+    auto sort_read = [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, (uint32_t*)k0, (uint32_t*)k1, v0, v1, (size_t)cb, 0, read_bits, stream); };
+    size_t tb = 0;
+    FM_HIP(cub_size(&tb, scan_counts, scan_fragments));
     if (join) {
         if ((rc = keys.alloc(cb * 16)) || (rc = vals.alloc(cb * 8)) || (rc = sorted.alloc(cb * sizeof(Sorted)))) return rc;
         k0 = keys.as<uint64_t>(); k1 = k0 + cb; v0 = vals.as<uint32_t>(); v1 = v0 + cb;
         a.sb = sorted.as<Sorted>();
-        FM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t3, k0, k1, v0, v1, (size_t)cb, 0, 62, stream));
-        FM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t4, k0, k1, v1, v0, (size_t)cb, 0, 64, stream));
-        FM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t5, (uint32_t*)k0, (uint32_t*)k1, v0, v1, (size_t)cb, 0, read_bits, stream));
+        FM_HIP(cub_size(&tb, sort_pos, sort_seq, sort_read));
     }
-    tb = std::max(std::max(t1, t2), std::max(t3, std::max(t4, t5)));
     if ((rc = tmp.alloc(tb))) return rc;
 
     FM_HIP(hipMemsetAsync(a.first, 0xff, 2 * n * 4, stream));
@@ -299,44 +283,29 @@ int fmgpu_positions_mates(const fmgpu_position* positions_a, uint64_t count_a, c
     FM_GRID(agrid, ca + 1);
     if (join) {
         FM_GRID(bgrid, cb);
-        size_t t = tb;
         k_mates_key_pos<<<bgrid, dim3(256), 0, stream>>>(a, k0, v0);
         FM_LAUNCHED("k_mates_key_pos");
-        FM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t, k0, k1, v0, v1, (size_t)cb, 0, 62, stream));                        // v1: by pos, then index
+        FM_HIP(cub_run(sort_pos, tmp));                             // v1: by pos, then index
         k_mates_key_seq<<<bgrid, dim3(256), 0, stream>>>(a, v1, k0);
         FM_LAUNCHED("k_mates_key_seq");
-        t = tb;
-        FM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t, k0, k1, v1, v0, (size_t)cb, 0, 64, stream));                        // v0: by seq_id, stable
+        FM_HIP(cub_run(sort_seq, tmp));                             // v0: by seq_id, stable
         k_mates_key_read<<<bgrid, dim3(256), 0, stream>>>(a, v0, (uint32_t*)k0);
         FM_LAUNCHED("k_mates_key_read");
-        t = tb;
-        FM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t, (uint32_t*)k0, (uint32_t*)k1, v0, v1, (size_t)cb, 0, read_bits, stream));    // v1: by read, stable: the order
+        FM_HIP(cub_run(sort_read, tmp));                            // v1: by read, stable: the order
         k_mates_compact<<<bgrid, dim3(256), 0, stream>>>(a, v1);
         FM_LAUNCHED("k_mates_compact");
         if (a.best) { k_mates_walk<WALK_MIN><<<agrid, dim3(256), 0, stream>>>(a, nullptr); FM_LAUNCHED("k_mates_walk"); }
         k_mates_walk<WALK_COUNT><<<agrid, dim3(256), 0, stream>>>(a, nullptr);
         FM_LAUNCHED("k_mates_walk");
     } else FM_HIP(hipMemsetAsync(a.cnt, 0, (ca + 1) * 4, stream));
-    size_t t = tb;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, counts, a.rstart, (size_t)(ca + 1), stream));
+    FM_HIP(cub_run(scan_counts, tmp));
     k_mates_fragments<<<fgrid, dim3(256), 0, stream>>>(a);
     FM_LAUNCHED("k_mates_fragments");
-    t = tb;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, a.fcount, a.foff, (size_t)(n + 1), stream));
+    FM_HIP(cub_run(scan_fragments, tmp));
     uint64_t back[1 + E_WORDS];                                     // the number of pairs and the error words: the call's one read-back
     FM_HIP(hipMemcpyAsync(back, a.foff + n, sizeof back, hipMemcpyDeviceToHost, stream));
     FM_HIP(hipStreamSynchronize(stream));
-    const uint64_t* err = back + 1;
-    static const char* const kArray[2] = {"positions_a", "positions_b"};
-    static const char* const kOffsets[2] = {"qoff_a", "qoff_b"};
-    for (int s = 0; s < 2; ++s) if (err[E_RANGE + s] != kNone)
-        return fail(FMGPU_ERR_INVALID, std::string("fmgpu_positions_mates: ") + kArray[s] + ": record " + std::to_string(err[E_RANGE + s]) + " names a read beyond the batch");
-    for (int s = 0; s < 2; ++s) if (err[E_ORDER + s] != kNone)
-        return fail(FMGPU_ERR_INVALID, std::string("fmgpu_positions_mates: ") + kArray[s] + ": record " + std::to_string(err[E_ORDER + s]) + " names a read below its predecessor's");
-    for (int s = 0; s < 2; ++s) if (err[E_QOFF + s] != kNone)
-        return fail(FMGPU_ERR_INVALID, std::string("fmgpu_positions_mates: ") + kOffsets[s] + ": read " + std::to_string(err[E_QOFF + s]) + " has an offset above its successor's");
-    for (int s = 0; s < 2; ++s) if (err[E_POS + s] != kNone)
-        return fail(FMGPU_ERR_INVALID, std::string("fmgpu_positions_mates: ") + kArray[s] + ": record " + std::to_string(err[E_POS + s]) + " has a pos of 2^62 or more");
+    if ((rc = mate_errors(back + 1, "fmgpu_positions_mates"))) return rc;
     const uint64_t total = back[0];
     *out_count = total;
     if (out_off) FM_HIP(hipMemcpyAsync(out_off, a.foff, (n + 1) * 8, hipMemcpyDefault, stream));

@@ -1,12 +1,16 @@
-// fmgpu_positions.h — what the fmgpu_positions_* calls share (fmgpu_format.hip, fmgpu_sam.hip, fmgpu_mates.hip): records and the runs of a read in a sorted record array,
-// digit counts, name tables and their row lookup, the LDS window a workgroup formats text into and how it leaves as aligned 16-byte stores, and the host-side odds and
-// ends around them.  Nothing here depends on the row width or on an index.  Everything on the device side is force-inlined into the kernels of the including unit.
+// fmgpu_positions.h — what the calls on located positions share (fmgpu_format.hip, fmgpu_sam.hip, fmgpu_mates.hip, fmgpu_sam_mates.hip, fmgpu_chain.hip): records and
+// the runs of a read in a sorted record array, digit counts, name tables and their row lookup, the LDS window a workgroup formats text into and how it leaves as aligned
+// 16-byte stores, and on the host a hipcub call written once for sizing and running, the end of a text call behind its read-back and the odds and ends around them.
+// Nothing here depends on the row width or on an index.  Everything on the device side is force-inlined into the kernels of the including unit.
 #pragma once
 #include "fmgpu_common.h"
 
 #include <hipcub/hipcub.hpp>
 
 namespace fmgpu {
+
+constexpr uint64_t kNone = ~0ull;                           // an error word that no offender has lowered; a 64-bit "nothing"
+constexpr uint32_t kNoRecord32 = 0xffffffffu;               // a read, slot or fragment without a record
 
 static __device__ const uint64_t kPow10[20] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull, 1000000000ull, 10000000000ull,
                                                100000000000ull, 1000000000000ull, 10000000000000ull, 100000000000000ull, 1000000000000000ull, 10000000000000000ull,
@@ -101,6 +105,19 @@ __device__ __forceinline__ void window_flush(const uint8_t* lds, uint8_t* gbase,
 struct Widen { __host__ __device__ uint64_t operator()(uint32_t v) const { return v; } };      // 32-bit lengths and counts scanned to 64-bit offsets
 using Widened = hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*>;
 
+// a hipcub call is written once, as a callable (void* tmp, size_t& bytes) -> hipError_t around it: asked without a buffer it states the temporary bytes it takes
+// (cub_size folds those of several calls into the most that any of them takes and ends at the first that fails), with a buffer of that size it runs (cub_run)
+template <class... Calls> inline hipError_t cub_size(size_t* most, Calls&&... calls) {
+    hipError_t e = hipSuccess;
+    auto one = [&](auto& call) { size_t bytes = 0; e = call(nullptr, bytes); if (bytes > *most) *most = bytes; return e == hipSuccess; };
+    (void)(one(calls) && ...);
+    return e;
+}
+template <class Call> inline hipError_t cub_run(Call&& call, const DBuf& tmp) {
+    size_t bytes = tmp.bytes;
+    return call(tmp.p, bytes);
+}
+
 // nothing to report: out_off[0] = 0, in host or device memory
 inline int first_offset_zero(uint64_t* out_off, hipStream_t stream) {
     if (!out_off) return 0;
@@ -109,6 +126,26 @@ inline int first_offset_zero(uint64_t* out_off, hipStream_t stream) {
     FM_HIP(hipStreamSynchronize(stream));
     return 0;
 }
+
+// the end of a text call behind its one read-back: `total` bytes in `lines` lines whose offsets stand at doff.  *out_bytes and out_line_off are written, the counting
+// call (no out, no capacity) ends here and so does one whose capacity is too small; otherwise `out` is staged and *write says that the caller's write pass is due.
+// (The SAM writers stage their read batches behind this, so `out` is allocated in front of them; an empty text stages nothing.)
+inline int text_tail(uint64_t total, const uint64_t* doff, uint64_t lines, uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* out_line_off, Staged& sout,
+                     hipStream_t stream, bool* write) {
+    *write = false;
+    *out_bytes = total;
+    if (out_line_off) FM_HIP(hipMemcpyAsync(out_line_off, doff, (lines + 1) * 8, hipMemcpyDefault, stream));
+    if (!out && !capacity) { FM_HIP(hipStreamSynchronize(stream)); return 0; }
+    if (total > capacity) {
+        FM_HIP(hipStreamSynchronize(stream));
+        return fail(FMGPU_ERR_CAPACITY, "the text takes " + std::to_string(total) + " bytes: more than `capacity`");
+    }
+    if (const int rc = sout.out(out, total, stream)) { (void)hipStreamSynchronize(stream); return rc; }
+    *write = true;
+    return 0;
+}
+// the windows of kTextWindow bytes that `total` bytes at dout touch, counted from the 16-byte piece of the address that holds the first byte
+inline uint64_t text_windows(const void* dout, uint64_t total) { return ((reinterpret_cast<uintptr_t>(dout) & 15u) + total + kTextWindow - 1) / kTextWindow; }
 
 // a table that is given (null: nothing to check) has bytes and spans where it states some; spec: the struct the message names, which: the table's member
 inline int check_name_table(const fmgpu_name_table* t, const char* spec, const char* which) {

@@ -14,23 +14,19 @@
 //                 window leaves as aligned 16-byte stores: only the first and last bytes of the text leave byte by byte.  Equal windows balance a heavy-tailed batch by construction.
 // Every pass behind the first reads the error words and does nothing once one is set: a batch that is out of order indexes nothing.
 // Scratch: 32 bytes per read and 12 bytes per line of the bound, plus the scans' own, freed on return.
-// The record loads and run boundaries, digit counts, name tables, the LDS window and its stores are fmgpu_positions.h's, shared with fmgpu_format.hip and fmgpu_mates.hip;
-// the field_* helpers and the copy of SEQ and QUAL (put_run) are fmgpu_sam_fields.h's, shared with fmgpu_sam_mates.hip; here: SAM's line (describe).
+// The record loads and run boundaries, digit counts, name tables, the LDS window and its stores and the end of the call behind its read-back are fmgpu_positions.h's, shared
+// with fmgpu_format.hip, fmgpu_mates.hip, fmgpu_sam_mates.hip and fmgpu_chain.hip; a line's defects, names and quality string, the frame of the write kernel, the field_*
+// helpers and the copy of SEQ and QUAL (put_run) are fmgpu_sam_fields.h's, shared with fmgpu_sam_mates.hip; here: SAM's line (describe).
 #include "fmgpu_sam_fields.h"
 
 namespace fmgpu {
 namespace {
 
-constexpr uint64_t kNone = ~0ull;
-constexpr uint32_t kNoRecord32 = 0xffffffffu;
 constexpr uint64_t kMaxSamLines = (1ull << 32) - 256;
-constexpr uint64_t kMaxSamBytes = kMaxRowBytes;             // a read of this many symbols is refused, as a name or quality string of this many bytes is (table_row)
 
 // the error words behind the offsets: the lowest record whose read is >= nq; whose read lies below its predecessor's; the lowest read whose offsets decrease; the lowest
-// (line << 8 | code) the measure pass refuses as invalid; ... as unsupported; and (no error) the number of lines
+// (line << 8 | code) the measure pass refuses as invalid; ... as unsupported (the codes: fmgpu_sam_fields.h); and (no error) the number of lines
 enum : int { E_RANGE = 0, E_ORDER = 1, E_QOFF = 2, E_LINE = 3, E_LONG = 4, E_LINES = 5, E_WORDS = 6 };
-enum : uint32_t { BAD_NONE = 0, BAD_RNAME_ROW = 1, BAD_RNAME_SPAN = 2, BAD_QUAL_ROW = 3, BAD_QUAL_SPAN = 4, BAD_QUAL_LEN = 5, BAD_SNAME_ROW = 6, BAD_SNAME_SPAN = 7 };
-enum : uint32_t { LONG_NONE = 0, LONG_READ = 1, LONG_NAME = 2, LONG_LINE = 3 };
 
 struct SamArgs {
     const fmgpu_position* pos; uint64_t count;
@@ -89,14 +85,6 @@ struct Line {
     uint64_t length;
 };
 
-// table_row for a line: a row that is too long is no invalid line, it makes the line unsupported (where nothing else has yet)
-__device__ __forceinline__ uint32_t row_of(const NameTable& t, uint64_t row, bool stop, const uint8_t** src, uint32_t* len, uint32_t* toolong) {
-    const uint32_t b = table_row(t, row, stop, src, len);
-    if (b != ROW_LONG) return b;
-    if (!*toolong) *toolong = LONG_NAME;
-    return ROW_OK;
-}
-
 // [lo, hi): reads known to hold the line's (lstart[lo] <= line < lstart[hi])
 __device__ __forceinline__ Line describe(const SamArgs& a, uint64_t line, uint64_t lo, uint64_t hi) {
     Line d;                                                 // the last read r with lstart[r] <= line: the one that has lines (lstart increases strictly over such reads)
@@ -123,28 +111,12 @@ __device__ __forceinline__ Line describe(const SamArgs& a, uint64_t line, uint64
         d.mapq = !secondary && a.nmin[lo] == 1u ? a.mapq_unique : a.mapq_multi;
         d.nh = a.end[lo] - first;
     }
-    uint32_t b, n = 0;
-    d.rname = nullptr; d.rn = digits10(d.read);
-    if (a.use_read_names) {
-        if ((b = row_of(a.read_names, d.read, true, &d.rname, &n, &d.toolong))) d.bad = BAD_RNAME_ROW + b - 1;
-        d.rn = n ? n : 1u;
-        if (!n) d.rname = nullptr;
-    }
+    name_of(a.read_names, a.use_read_names, d.read, BAD_RNAME_ROW, &d.rname, &d.rn, &d.bad, &d.toolong);
     d.qual = nullptr;
     uint32_t qn = 0;
-    if (a.use_quals) {
-        if ((b = row_of(a.quals, d.read, false, &d.qual, &qn, &d.toolong)) && !d.bad) d.bad = BAD_QUAL_ROW + b - 1;
-        else if (!b && !d.toolong && qn != 0 && qn != d.m && !d.bad) d.bad = BAD_QUAL_LEN;
-    }
+    if (a.use_quals) qual_of(a.quals, d.read, d.m, &d.qual, &qn, &d.bad, &d.toolong);
     d.sname = nullptr; d.sn = 1;
-    if (d.mapped) {
-        d.sn = digits10(d.rec.seq_id);
-        if (a.use_seq_names) {
-            if ((b = row_of(a.seq_names, d.rec.seq_id, true, &d.sname, &n, &d.toolong)) && !d.bad) d.bad = BAD_SNAME_ROW + b - 1;
-            d.sn = n ? n : 1u;
-            if (!n) d.sname = nullptr;
-        }
-    }
+    if (d.mapped) name_of(a.seq_names, a.use_seq_names, d.rec.seq_id, BAD_SNAME_ROW, &d.sname, &d.sn, &d.bad, &d.toolong);
     d.star_seq = d.m == 0 || (secondary && !a.secondary_seq);
     d.star_qual = d.star_seq || !a.use_quals || qn == 0;
     d.star_cigar = !d.mapped || !a.cigar || d.m == 0;
@@ -182,32 +154,21 @@ __global__ __launch_bounds__(256) void k_sam_write(SamArgs a, const uint8_t* __r
                                                    uint8_t* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kTextWindow];
     __shared__ uint8_t tab[512];                            // the SEQ byte of a symbol: [0, 256) strand 0, [256, 512) strand 1 (complemented)
-    tab[threadIdx.x] = tables[threadIdx.x];
-    tab[256u + threadIdx.x] = tables[256u + threadIdx.x];
-    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
-    uint8_t* const gbase = out - shift;                     // position 0: 16-byte aligned, never stored to below position `shift`
-    const uint64_t lo = (uint64_t)blockIdx.x * kTextWindow, extent = shift + total;
-    const uint64_t hi = lo + kTextWindow < extent ? lo + kTextWindow : extent;
-    const uint64_t from = lo > shift ? lo : shift;          // the window holds positions [from, hi) of the text = bytes [from - shift, hi - shift)
-    if (from >= hi) return;                                 // (uniform)
-    const uint64_t o0 = from - shift, o1 = hi - shift;
-    // l0: the last line that starts at or before o0; l1: the first line that starts at or behind o1 (off[0] = 0 < o1; a line has at least its '\n': the offsets
-    // increase strictly); r0, r1: the reads of lines l0 and l1 - 1 (lstart[0] = 0): every wave finds the four by itself, 64 probes per step
-    const uint64_t l0 = wave_search(off, lines, o0, false), l1 = wave_search(off, lines, o1, true) + 1;
-    const uint64_t r0 = wave_search(a.lstart, a.nq, l0, false), r1 = wave_search(a.lstart, a.nq, l1 - 1, false);
+    Frame f;
+    if (!frame_open(tables, tab, off, lines, total, out, &f)) return;
+    // r0, r1: the reads of lines l0 and l1 - 1 (lstart[0] = 0), found by every wave like the lines themselves
+    const uint64_t r0 = wave_search(a.lstart, a.nq, f.l0, false), r1 = wave_search(a.lstart, a.nq, f.l1 - 1, false);
     __syncthreads();
-    const Window w{lds, lo};
-    const uint64_t n = l1 - l0;
+    const Window w{lds, f.lo};
+    const uint64_t hi = f.hi, n = f.l1 - f.l0;
     for (uint64_t base = 0; base < n; base += 256u) {
         const uint64_t j = base + 4u * (threadIdx.x & 63u) + (threadIdx.x >> 6);      // consecutive lines go to the four waves in turn
-        const bool mine = j < n;
-        const uint8_t *seq = nullptr, *qual = nullptr;
-        uint32_t seq_len = 0, qual_len = 0, rev = 0;
-        uint64_t seq_at = 0, qual_at = 0;
-        if (mine) {
-            const uint64_t l = l0 + j;
+        Runs r = {nullptr, nullptr, 0, 0, 0, 0};
+        uint32_t rev = 0;
+        if (j < n) {
+            const uint64_t l = f.l0 + j;
             const Line d = describe(a, l, r0, r1 + 1);
-            uint64_t at = off[l] + shift;
+            uint64_t at = off[l] + f.shift;
             at = field_name(w, hi, at, d.rname, d.rn, !a.use_read_names, d.read);
             at = field_decimal(w, at, d.flag, '\t');
             if (d.mapped) { at = field_name(w, hi, at, d.sname, d.sn, !a.use_seq_names, d.rec.seq_id); at = field_decimal(w, at, d.rec.pos + 1, '\t'); }
@@ -217,27 +178,14 @@ __global__ __launch_bounds__(256) void k_sam_write(SamArgs a, const uint8_t* __r
             else { at = field_decimal(w, at, d.m, 'M'); w.put(at, '\t'); ++at; }
             at = field_text(w, at, "*\t0\t0\t", 6);
             rev = d.mapped && a.shift && (d.rec.qidx & 1u) ? 1u : 0u;
-            if (d.star_seq) { w.put(at, '*'); at += 1; } else { seq = d.q; seq_len = d.m; seq_at = at; at += d.m; }
-            w.put(at, '\t'); ++at;
-            if (d.star_qual) { w.put(at, '*'); at += 1; } else { qual = d.qual; qual_len = d.m; qual_at = at; at += d.m; }
-            if (d.mapped) {
-                at = field_text(w, at, "\tNM:i:", 6);
-                at = field_decimal(w, at, d.rec.errors, '\t');
-                at = field_text(w, at, "NH:i:", 5);
-                at = field_decimal(w, at, d.nh, '\n');
-            } else w.put(at, '\n');
+            field_tail(w, at, d.star_seq, d.star_qual, d.m, d.q, d.qual, d.mapped, d.rec.errors, d.nh, &r);
         }
-        put_run(w, hi, seq, seq_len, seq_at, rev, tab);
-        put_run(w, hi, qual, qual_len, qual_at, rev, nullptr);
+        put_run(w, hi, r.seq, r.seq_len, r.seq_at, rev, tab);
+        put_run(w, hi, r.qual, r.qual_len, r.qual_at, rev, nullptr);
     }
     __syncthreads();
-    window_flush(lds, gbase, lo, from, hi);
+    window_flush(lds, f.gbase, f.lo, f.from, f.hi);
 }
-
-const char* const kBadText[] = {"", "names a row beyond the read_names table", "has a read name span that leaves the table's bytes", "names a row beyond the quals table",
-                                "has a quality span that leaves the table's bytes", "has a quality span whose len is neither 0 nor the read's length",
-                                "names a row beyond the seq_names table", "has a sequence name span that leaves the table's bytes"};
-const char* const kLongText[] = {"", "is a read of 2^31 symbols or more", "has a name or quality span of 2^31 bytes or more", "makes a line of 2^32 bytes or more"};
 
 }  // namespace
 }  // namespace fmgpu
@@ -261,9 +209,9 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
     if (spec->emit_unmapped > 1) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: emit_unmapped must be 0 or 1");
     if (spec->secondary_seq > 1) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: secondary_seq must be 0 or 1");
     if (spec->reserved[0] || spec->reserved[1] || spec->reserved[2]) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: reserved must be 0");
-    if (spec->strands && !spec->strands->complement) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: strands has a null complement");
-    if (spec->strands && (spec->strands->n < 1 || spec->strands->n > 256)) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_spec: strands->n must be in [1, 256]");
     int rc;
+    uint8_t tables[512];
+    if ((rc = seq_tables(spec->char_of, spec->strands, "fmgpu_sam_spec", tables))) return rc;
     if ((rc = check_name_table(spec->read_names, "fmgpu_sam_spec", "read_names")) || (rc = check_name_table(spec->quals, "fmgpu_sam_spec", "quals")) ||
         (rc = check_name_table(spec->seq_names, "fmgpu_sam_spec", "seq_names"))) return rc;
     *out_bytes = 0;
@@ -279,10 +227,6 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
     a.shift = spec->strands ? 1 : 0;
     a.cigar = spec->cigar; a.emit_unmapped = spec->emit_unmapped; a.secondary_seq = spec->secondary_seq;
     a.mapq_unique = spec->mapq_unique; a.mapq_multi = spec->mapq_multi;
-    uint8_t tables[512], comp[256];
-    for (int c = 0; c < 256; ++c) comp[c] = (uint8_t)c;
-    if (spec->strands) strands_table(spec->strands->complement, spec->strands->n, comp);
-    for (int c = 0; c < 256; ++c) { tables[c] = spec->char_of[c]; tables[256 + c] = spec->char_of[comp[c]]; }
 
     Staged spos, soff, sq, sbytes[3], sspans[3], sout;
     if ((rc = spos.in(positions, count * sizeof(fmgpu_position), stream))) return rc;
@@ -311,10 +255,11 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
     FM_HIP(hipMemsetAsync(a.err, 0xff, E_WORDS * 8, stream));
 
     Widened lcounts(a.lcount, Widen{}), lengths(lens.as<uint32_t>(), Widen{});
-    size_t tb1 = 0, tb2 = 0;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, lcounts, a.lstart, (size_t)(nq + 1), stream));
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, lengths, doff, (size_t)(bound + 1), stream));
-    if ((rc = tmp.alloc(tb1 > tb2 ? tb1 : tb2))) return rc;
+    auto scan_lines = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, lcounts, a.lstart, (size_t)(nq + 1), stream); };
+    auto scan_lengths = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, lengths, doff, (size_t)(bound + 1), stream); };
+    size_t tb = 0;
+    FM_HIP(cub_size(&tb, scan_lines, scan_lengths));
+    if ((rc = tmp.alloc(tb))) return rc;
     if (count) {
         FM_GRID(rgrid, count);
         k_sam_records<<<rgrid, dim3(256), 0, stream>>>(a);
@@ -325,11 +270,11 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
     FM_GRID(qgrid, nq + 1);
     k_sam_reads<<<qgrid, dim3(256), 0, stream>>>(a);
     FM_LAUNCHED("k_sam_reads");
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb1, lcounts, a.lstart, (size_t)(nq + 1), stream));
+    FM_HIP(cub_run(scan_lines, tmp));
     FM_GRID(mgrid, bound + 1);
     k_sam_measure<<<mgrid, dim3(256), 0, stream>>>(a, lens.as<uint32_t>());
     FM_LAUNCHED("k_sam_measure");
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb2, lengths, doff, (size_t)(bound + 1), stream));
+    FM_HIP(cub_run(scan_lengths, tmp));
     uint64_t back[1 + E_WORDS];                                     // the size of the text, the error words, the number of lines: the call's one read-back
     FM_HIP(hipMemcpyAsync(back, doff + bound, sizeof back, hipMemcpyDeviceToHost, stream));
     FM_HIP(hipStreamSynchronize(stream));
@@ -347,27 +292,20 @@ int fmgpu_positions_sam(const fmgpu_position* positions, uint64_t count, const f
         FM_HIP(hipMemcpyAsync(who, where, 16, hipMemcpyDeviceToHost, stream));
         FM_HIP(hipStreamSynchronize(stream));
         const std::string name = who[1] != kNone ? "record " + std::to_string(who[1]) : "unmapped read " + std::to_string(who[0]);
-        return fail(invalid ? FMGPU_ERR_INVALID : FMGPU_ERR_UNSUPPORTED, "fmgpu_positions_sam: " + name + " " + (invalid ? kBadText : kLongText)[word & 255u]);
+        return fail(invalid ? FMGPU_ERR_INVALID : FMGPU_ERR_UNSUPPORTED, "fmgpu_positions_sam: " + name + " " + line_defect(invalid, word, "the quals"));
     }
     const uint64_t total = back[0], lines = err[E_LINES];
-    *out_bytes = total;
     if (out_lines) *out_lines = lines;
-    if (out_line_off) FM_HIP(hipMemcpyAsync(out_line_off, doff, (lines + 1) * 8, hipMemcpyDefault, stream));
-    if (!out && !capacity) { FM_HIP(hipStreamSynchronize(stream)); return 0; }
-    if (total > capacity) {
-        FM_HIP(hipStreamSynchronize(stream));
-        return fail(FMGPU_ERR_CAPACITY, "the text takes " + std::to_string(total) + " bytes: more than `capacity`");
-    }
+    bool write;
+    if ((rc = text_tail(total, doff, lines, out, capacity, out_bytes, out_line_off, sout, stream, &write)) || !write) return rc;
     if (!total) { FM_HIP(hipStreamSynchronize(stream)); return 0; }
     uint64_t symbols = 0;                                           // the offsets do not decrease: the batch ends at qoff[nq]
     FM_HIP(hipMemcpyAsync(&symbols, a.qoff + nq, 8, hipMemcpyDeviceToHost, stream));
     FM_HIP(hipStreamSynchronize(stream));
     if ((rc = sq.in(spec->qbuf, symbols, stream))) return rc;
     a.qbuf = sq.dev ? (const uint8_t*)sq.dev : spec->qbuf;          // (a batch without a symbol: the pointer is never read through)
-    if ((rc = sout.out(out, total, stream))) { (void)hipStreamSynchronize(stream); return rc; }
     uint8_t* const dout = (uint8_t*)sout.dev;
-    const uint64_t windows = ((reinterpret_cast<uintptr_t>(dout) & 15u) + total + kTextWindow - 1) / kTextWindow;
-    FM_GRID(wgrid, windows * 256);
+    FM_GRID(wgrid, text_windows(dout, total) * 256);
     k_sam_write<<<wgrid, dim3(256), 0, stream>>>(a, small.as<uint8_t>(), doff, lines, total, dout);
     FM_LAUNCHED("k_sam_write");
     if ((rc = sout.finish())) return rc;

@@ -19,26 +19,18 @@
 // Every pass behind the ones that look for an error reads the error words and does nothing once one is set.
 // Scratch: 84 bytes per fragment (24 per slot, 12 for the chosen pair, 12 per line for its length and offset), nothing per record and nothing per pair, plus the
 // scan's own; freed on return.
-// The record loads, run boundaries, digit counts, name tables and the LDS window are fmgpu_positions.h's; the field writers and the copy of SEQ and QUAL are
-// fmgpu_sam_fields.h's, shared with fmgpu_sam.hip; here: the choice of each mate's record and the paired line (describe).
+// The record loads, digit counts, name tables, the LDS window and the end of the call are fmgpu_positions.h's; the slots, their error words, the records pass, the staging of
+// the two sides and the report of those words are fmgpu_mate_slots.h's, shared with fmgpu_mates.hip; a line's defects, names and quality string, the write kernel's frame, the
+// field writers and the copy of SEQ and QUAL are fmgpu_sam_fields.h's, shared with fmgpu_sam.hip; here: the choice of each mate's record and the paired line (describe).
 #include "fmgpu_sam_fields.h"
+#include "fmgpu_mate_slots.h"
 
 namespace fmgpu {
 namespace {
 
-constexpr uint64_t kNone = ~0ull;
-constexpr uint32_t kNoRecord32 = 0xffffffffu;
-constexpr uint64_t kMaxMateRecords = (1ull << 32) - 256;
-constexpr uint64_t kMaxFragments = (1ull << 31) - 1;        // two lines per fragment, numbered in 32 bits
-constexpr uint64_t kMaxSamBytes = kMaxRowBytes;
-constexpr uint64_t kPosLimit = 1ull << 62;
-
-// the error words behind the offsets, in the order they are reported (array A, array B where there are two): the lowest record whose read lies beyond the batch; whose
-// read lies below its predecessor's; the lowest read whose offsets decrease; the lowest record whose pos is 2^62 or more; the lowest pair that names what does not exist;
-// the lowest (line << 8 | code) the measure pass refuses as invalid; ... as unsupported; and (no errors) the symbols of batch A and of batch B
-enum : int { E_RANGE = 0, E_ORDER = 2, E_QOFF = 4, E_POS = 6, E_PAIR = 8, E_LINE = 9, E_LONG = 10, E_SYM = 11, E_WORDS = 13 };
-enum : uint32_t { BAD_NONE = 0, BAD_RNAME_ROW = 1, BAD_RNAME_SPAN = 2, BAD_QUAL_ROW = 3, BAD_QUAL_SPAN = 4, BAD_QUAL_LEN = 5, BAD_SNAME_ROW = 6, BAD_SNAME_SPAN = 7 };
-enum : uint32_t { LONG_NONE = 0, LONG_READ = 1, LONG_NAME = 2, LONG_LINE = 3 };
+// the error words behind the offsets, in the order they are reported: fmgpu_mate_slots.h's eight; the lowest pair that names what does not exist; the lowest
+// (line << 8 | code) the measure pass refuses as invalid; ... as unsupported (the codes: fmgpu_sam_fields.h); and (no errors) the symbols of batch A and of batch B
+enum : int { E_PAIR = E_MATE_WORDS, E_LINE, E_LONG, E_SYM, E_WORDS = E_SYM + 2 };
 enum : uint32_t { NEXT_STAR = 0, NEXT_SAME = 1, NEXT_NAME = 2 };
 
 struct SmArgs {
@@ -68,16 +60,9 @@ __device__ __forceinline__ bool failed(const SmArgs& a) {
 __global__ __launch_bounds__(256) void k_sm_records(SmArgs a, int side) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const fmgpu_position* __restrict__ p = a.pos[side];
-    const uint64_t count = a.count[side];
-    if (i >= count) return;
-    uint64_t read;
-    bool first, last;
-    if (!run_edges(p, count, i, a.shift, a.reads, &a.err[E_RANGE + side], &a.err[E_ORDER + side], &read, &first, &last)) return;
-    if (p[i].pos >= kPosLimit) atomicMin(&a.err[E_POS + side], (unsigned long long)i);
-    const uint64_t slot = a.interleaved ? read : 2 * read + (uint64_t)side;
-    if (first) a.first[slot] = (uint32_t)i;
-    if (last) a.end[slot] = (uint32_t)i + 1u;
-    atomicMin(&a.key[slot], ((unsigned long long)p[i].errors << 32) | (unsigned long long)i);
+    if (i >= a.count[side]) return;
+    const uint64_t slot = mate_record(p, a.count[side], i, side, a.shift, a.reads, a.interleaved, a.err, a.first, a.end);
+    if (slot != kNone) atomicMin(&a.key[slot], ((unsigned long long)p[i].errors << 32) | (unsigned long long)i);
 }
 
 __global__ __launch_bounds__(256) void k_sm_count(SmArgs a, int side) {
@@ -148,25 +133,6 @@ struct Line {
     uint64_t length;
 };
 
-// table_row for a line: a row that is too long is no invalid line, it makes the line unsupported (where nothing else has yet)
-__device__ __forceinline__ uint32_t row_of(const NameTable& t, uint64_t row, bool stop, const uint8_t** src, uint32_t* len, uint32_t* toolong) {
-    const uint32_t b = table_row(t, row, stop, src, len);
-    if (b != ROW_LONG) return b;
-    if (!*toolong) *toolong = LONG_NAME;
-    return ROW_OK;
-}
-
-// the name of sequence `id` as RNAME or RNEXT writes it: *src = nullptr with *numbered where there is no table, nullptr without it for an empty name ('*')
-__device__ __forceinline__ void seq_name(const SmArgs& a, uint64_t id, Line* d, const uint8_t** src, uint32_t* len, bool* numbered) {
-    *src = nullptr; *len = digits10(id); *numbered = true;
-    if (!a.use_seq_names) return;
-    uint32_t b, n = 0;
-    *numbered = false;
-    if ((b = row_of(a.seq_names, id, true, src, &n, &d->toolong)) && !d->bad) d->bad = BAD_SNAME_ROW + b - 1;
-    *len = n ? n : 1u;
-    if (!n) *src = nullptr;
-}
-
 __device__ __forceinline__ Line describe(const SmArgs& a, uint64_t line) {
     Line d;
     const uint32_t side = (uint32_t)(line & 1u), other = side ^ 1u;
@@ -189,32 +155,30 @@ __device__ __forceinline__ Line describe(const SmArgs& a, uint64_t line) {
     d.errors = x.errors;
     d.mapq = !d.has_x ? 0u : (proper ? a.pcnt[f] : a.nmin[line]) == 1u ? a.mapq_unique : a.mapq_multi;
     d.nh = d.has_x ? a.end[line] - a.first[line] : 0u;
-    uint32_t b, n = 0;
     d.qname = nullptr; d.qn = digits10(f);
-    if (a.use_read_names) {
-        if ((b = row_of(a.read_names, a.interleaved ? 2 * f : f, true, &d.qname, &n, &d.toolong))) d.bad = BAD_RNAME_ROW + b - 1;
+    if (a.use_read_names) {                                 // (name_of's logic with the "/1" "/2" strip between the lookup and the length)
+        uint32_t n = 0;
+        if (const uint32_t b = row_of(a.read_names, a.interleaved ? 2 * f : f, true, &d.qname, &n, &d.toolong)) d.bad = BAD_RNAME_ROW + b - 1;
         if (a.strip && n >= 3u && d.qname[n - 2u] == '/' && (d.qname[n - 1u] == '1' || d.qname[n - 1u] == '2')) n -= 2u;
         d.qn = n ? n : 1u;
         if (!n) d.qname = nullptr;
     }
     d.qual = nullptr;
     uint32_t qn = 0;
-    if (a.use_quals[side]) {
-        if ((b = row_of(a.quals[side], row, false, &d.qual, &qn, &d.toolong)) && !d.bad) d.bad = BAD_QUAL_ROW + b - 1;
-        else if (!b && !d.toolong && qn != 0 && qn != d.m && !d.bad) d.bad = BAD_QUAL_LEN;
-    }
+    if (a.use_quals[side]) qual_of(a.quals[side], row, d.m, &d.qual, &qn, &d.bad, &d.toolong);
     // RNAME and POS: the mate's own, else its mate's; RNEXT and PNEXT: the other mate's, else its own
     d.rname = nullptr; d.sn = 1; d.rname_numbered = false; d.rname_id = 0; d.pos1 = 0;
     d.rnext = nullptr; d.nn = 1; d.rnext_numbered = false; d.rnext_id = 0; d.pnext1 = 0; d.rnext_kind = NEXT_STAR;
     if (d.has_x || d.has_y) {
         const fmgpu_position& at = d.has_x ? x : y;
         d.rname_id = at.seq_id; d.pos1 = at.pos + 1;
-        seq_name(a, d.rname_id, &d, &d.rname, &d.sn, &d.rname_numbered);
+        d.rname_numbered = !a.use_seq_names;
+        name_of(a.seq_names, a.use_seq_names, d.rname_id, BAD_SNAME_ROW, &d.rname, &d.sn, &d.bad, &d.toolong);
         d.pnext1 = (d.has_y ? y.pos : x.pos) + 1;
         d.rnext_kind = NEXT_SAME;
         if (d.has_x && d.has_y && x.seq_id != y.seq_id) {
-            d.rnext_kind = NEXT_NAME; d.rnext_id = y.seq_id;
-            seq_name(a, d.rnext_id, &d, &d.rnext, &d.nn, &d.rnext_numbered);
+            d.rnext_kind = NEXT_NAME; d.rnext_id = y.seq_id; d.rnext_numbered = !a.use_seq_names;
+            name_of(a.seq_names, a.use_seq_names, d.rnext_id, BAD_SNAME_ROW, &d.rnext, &d.nn, &d.bad, &d.toolong);
         }
     }
     d.t = 0; d.tneg = false;
@@ -253,31 +217,19 @@ __global__ __launch_bounds__(256) void k_sm_measure(SmArgs a, uint32_t* __restri
 __global__ __launch_bounds__(256) void k_sm_write(SmArgs a, const uint8_t* __restrict__ tables, const uint64_t* __restrict__ off, uint64_t total, uint8_t* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kTextWindow];
     __shared__ uint8_t tab[512];                            // the SEQ byte of a symbol: [0, 256) strand 0, [256, 512) strand 1 (complemented)
-    tab[threadIdx.x] = tables[threadIdx.x];
-    tab[256u + threadIdx.x] = tables[256u + threadIdx.x];
-    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
-    uint8_t* const gbase = out - shift;                     // position 0: 16-byte aligned, never stored to below position `shift`
-    const uint64_t lo = (uint64_t)blockIdx.x * kTextWindow, extent = shift + total;
-    const uint64_t hi = lo + kTextWindow < extent ? lo + kTextWindow : extent;
-    const uint64_t from = lo > shift ? lo : shift;          // the window holds positions [from, hi) of the text = bytes [from - shift, hi - shift)
-    if (from >= hi) return;                                 // (uniform)
-    const uint64_t o0 = from - shift, o1 = hi - shift, lines = 2 * a.n;
-    // l0: the last line that starts at or before o0; l1: the first line that starts at or behind o1 (off[0] = 0 < o1; a line has at least its '\n': the offsets
-    // increase strictly): every wave finds the two by itself, 64 probes per step
-    const uint64_t l0 = wave_search(off, lines, o0, false), l1 = wave_search(off, lines, o1, true) + 1;
+    Frame f;
+    if (!frame_open(tables, tab, off, 2 * a.n, total, out, &f)) return;
     __syncthreads();
-    const Window w{lds, lo};
-    const uint64_t n = l1 - l0;
+    const Window w{lds, f.lo};
+    const uint64_t hi = f.hi, n = f.l1 - f.l0;
     for (uint64_t base = 0; base < n; base += 256u) {
         const uint64_t j = base + 4u * (threadIdx.x & 63u) + (threadIdx.x >> 6);      // consecutive lines go to the four waves in turn
-        const bool mine = j < n;
-        const uint8_t *seq = nullptr, *qual = nullptr;
-        uint32_t seq_len = 0, qual_len = 0, rev = 0;
-        uint64_t seq_at = 0, qual_at = 0;
-        if (mine) {
-            const uint64_t l = l0 + j;
+        Runs r = {nullptr, nullptr, 0, 0, 0, 0};
+        uint32_t rev = 0;
+        if (j < n) {
+            const uint64_t l = f.l0 + j;
             const Line d = describe(a, l);
-            uint64_t at = off[l] + shift;
+            uint64_t at = off[l] + f.shift;
             at = field_name(w, hi, at, d.qname, d.qn, !a.use_read_names, d.f);
             at = field_decimal(w, at, d.flag, '\t');
             at = field_name(w, hi, at, d.rname, d.sn, d.rname_numbered, d.rname_id);
@@ -291,27 +243,14 @@ __global__ __launch_bounds__(256) void k_sm_write(SmArgs a, const uint8_t* __res
             if (d.tneg) { w.put(at, '-'); ++at; }
             at = field_decimal(w, at, d.t, '\t');
             rev = d.rev;
-            if (d.star_seq) { w.put(at, '*'); at += 1; } else { seq = d.q; seq_len = d.m; seq_at = at; at += d.m; }
-            w.put(at, '\t'); ++at;
-            if (d.star_qual) { w.put(at, '*'); at += 1; } else { qual = d.qual; qual_len = d.m; qual_at = at; at += d.m; }
-            if (d.has_x) {
-                at = field_text(w, at, "\tNM:i:", 6);
-                at = field_decimal(w, at, d.errors, '\t');
-                at = field_text(w, at, "NH:i:", 5);
-                at = field_decimal(w, at, d.nh, '\n');
-            } else w.put(at, '\n');
+            field_tail(w, at, d.star_seq, d.star_qual, d.m, d.q, d.qual, d.has_x, d.errors, d.nh, &r);
         }
-        put_run(w, hi, seq, seq_len, seq_at, rev, tab);
-        put_run(w, hi, qual, qual_len, qual_at, rev, nullptr);
+        put_run(w, hi, r.seq, r.seq_len, r.seq_at, rev, tab);
+        put_run(w, hi, r.qual, r.qual_len, r.qual_at, rev, nullptr);
     }
     __syncthreads();
-    window_flush(lds, gbase, lo, from, hi);
+    window_flush(lds, f.gbase, f.lo, f.from, f.hi);
 }
-
-const char* const kBadText[] = {"", "names a row beyond the read_names table", "has a read name span that leaves the table's bytes", "names a row beyond its quality table",
-                                "has a quality span that leaves the table's bytes", "has a quality span whose len is neither 0 nor the read's length",
-                                "names a row beyond the seq_names table", "has a sequence name span that leaves the table's bytes"};
-const char* const kLongText[] = {"", "is a read of 2^31 symbols or more", "has a name or quality span of 2^31 bytes or more", "makes a line of 2^32 bytes or more"};
 
 }  // namespace
 }  // namespace fmgpu
@@ -346,9 +285,9 @@ int fmgpu_positions_sam_mates(const fmgpu_position* positions_a, uint64_t count_
     if (spec->cigar > 1) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_mates_spec: cigar must be 0 or 1");
     if (spec->strip_mate_suffix > 1) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_mates_spec: strip_mate_suffix must be 0 or 1");
     if (spec->reserved[0] || spec->reserved[1] || spec->reserved[2]) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_mates_spec: reserved must be 0");
-    if (spec->strands && !spec->strands->complement) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_mates_spec: strands has a null complement");
-    if (spec->strands && (spec->strands->n < 1 || spec->strands->n > 256)) return fail(FMGPU_ERR_INVALID, "fmgpu_sam_mates_spec: strands->n must be in [1, 256]");
     int rc;
+    uint8_t tables[512];
+    if ((rc = seq_tables(spec->char_of, spec->strands, "fmgpu_sam_mates_spec", tables))) return rc;
     if ((rc = check_name_table(spec->read_names, "fmgpu_sam_mates_spec", "read_names")) || (rc = check_name_table(spec->quals_a, "fmgpu_sam_mates_spec", "quals_a")) ||
         (rc = check_name_table(spec->quals_b, "fmgpu_sam_mates_spec", "quals_b")) || (rc = check_name_table(spec->seq_names, "fmgpu_sam_mates_spec", "seq_names"))) return rc;
     *out_bytes = 0;
@@ -366,19 +305,9 @@ int fmgpu_positions_sam_mates(const fmgpu_position* positions_a, uint64_t count_
     a.n_pairs = n_pairs;
     a.shift = spec->strands ? 1 : 0; a.interleaved = spec->interleaved;
     a.cigar = spec->cigar; a.strip = spec->strip_mate_suffix; a.mapq_unique = spec->mapq_unique; a.mapq_multi = spec->mapq_multi;
-    uint8_t tables[512], comp[256];
-    for (int c = 0; c < 256; ++c) comp[c] = (uint8_t)c;
-    if (spec->strands) strands_table(spec->strands->complement, spec->strands->n, comp);
-    for (int c = 0; c < 256; ++c) { tables[c] = spec->char_of[c]; tables[256 + c] = spec->char_of[comp[c]]; }
 
     Staged spos[2], spairs, soff[2], sq[2], sbytes[4], sspans[4], sout;
-    if ((rc = spos[0].in(positions_a, count_a * sizeof(fmgpu_position), stream)) || (rc = soff[0].in(spec->qoff_a, (a.reads + 1) * 8, stream))) return rc;
-    a.pos[0] = (const fmgpu_position*)spos[0].dev; a.qoff[0] = (const uint64_t*)soff[0].dev;
-    if (inter) { a.pos[1] = a.pos[0]; a.qoff[1] = a.qoff[0]; }
-    else {
-        if ((rc = spos[1].in(positions_b, count_b * sizeof(fmgpu_position), stream)) || (rc = soff[1].in(spec->qoff_b, (n + 1) * 8, stream))) return rc;
-        a.pos[1] = (const fmgpu_position*)spos[1].dev; a.qoff[1] = (const uint64_t*)soff[1].dev;
-    }
+    if ((rc = stage_mate_sides(positions_a, count_a, positions_b, count_b, spec->qoff_a, spec->qoff_b, n, inter, spos, soff, a.pos, a.qoff, stream))) return rc;
     if ((rc = spairs.in(pairs, n_pairs * sizeof(fmgpu_mate_pair), stream))) return rc;
     a.pairs = (const fmgpu_mate_pair*)spairs.dev;
     for (int s = 0; s < 2; ++s) a.aligned16[s] = (reinterpret_cast<uintptr_t>(a.pos[s]) & 15u) == 0;
@@ -409,8 +338,9 @@ int fmgpu_positions_sam_mates(const fmgpu_position* positions_a, uint64_t count_
     FM_HIP(hipMemsetAsync(a.err, 0xff, E_WORDS * 8, stream));
 
     Widened lengths(lens.as<uint32_t>(), Widen{});
+    auto scan_lengths = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, lengths, doff, (size_t)(lines + 1), stream); };
     size_t tb = 0;
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lengths, doff, (size_t)(lines + 1), stream));
+    FM_HIP(cub_size(&tb, scan_lengths));
     if ((rc = tmp.alloc(tb))) return rc;
     for (int s = 0; s < (inter ? 1 : 2); ++s) if (a.count[s]) {
         FM_GRID(rgrid, a.count[s]);
@@ -435,38 +365,24 @@ int fmgpu_positions_sam_mates(const fmgpu_position* positions_a, uint64_t count_
     FM_GRID(mgrid, lines + 1);
     k_sm_measure<<<mgrid, dim3(256), 0, stream>>>(a, lens.as<uint32_t>());
     FM_LAUNCHED("k_sm_measure");
-    FM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, lengths, doff, (size_t)(lines + 1), stream));
+    FM_HIP(cub_run(scan_lengths, tmp));
     uint64_t back[1 + E_WORDS];                                     // the size of the text, the error words, the symbols of the batches: the call's one read-back
     FM_HIP(hipMemcpyAsync(back, doff + lines, sizeof back, hipMemcpyDeviceToHost, stream));
     FM_HIP(hipStreamSynchronize(stream));
     const uint64_t* err = back + 1;
-    static const char* const kArray[2] = {"positions_a", "positions_b"};
-    static const char* const kOffsets[2] = {"qoff_a", "qoff_b"};
     const std::string me = "fmgpu_positions_sam_mates: ";
-    for (int s = 0; s < 2; ++s) if (err[E_RANGE + s] != kNone)
-        return fail(FMGPU_ERR_INVALID, me + kArray[s] + ": record " + std::to_string(err[E_RANGE + s]) + " names a read beyond the batch");
-    for (int s = 0; s < 2; ++s) if (err[E_ORDER + s] != kNone)
-        return fail(FMGPU_ERR_INVALID, me + kArray[s] + ": record " + std::to_string(err[E_ORDER + s]) + " names a read below its predecessor's");
-    for (int s = 0; s < 2; ++s) if (err[E_QOFF + s] != kNone)
-        return fail(FMGPU_ERR_INVALID, me + kOffsets[s] + ": read " + std::to_string(err[E_QOFF + s]) + " has an offset above its successor's");
-    for (int s = 0; s < 2; ++s) if (err[E_POS + s] != kNone)
-        return fail(FMGPU_ERR_INVALID, me + kArray[s] + ": record " + std::to_string(err[E_POS + s]) + " has a pos of 2^62 or more");
+    if ((rc = mate_errors(err, "fmgpu_positions_sam_mates"))) return rc;
     if (err[E_PAIR] != kNone)
         return fail(FMGPU_ERR_INVALID, me + "pairs: pair " + std::to_string(err[E_PAIR]) + " names a fragment >= n_fragments, a record beyond its array or a record that is not its fragment's mate");
     if (err[E_LINE] != kNone || err[E_LONG] != kNone) {
         const bool invalid = err[E_LINE] != kNone;
         const uint64_t word = invalid ? err[E_LINE] : err[E_LONG], line = word >> 8;
         return fail(invalid ? FMGPU_ERR_INVALID : FMGPU_ERR_UNSUPPORTED,
-                    me + "fragment " + std::to_string(line >> 1) + " mate " + (line & 1u ? "B " : "A ") + (invalid ? kBadText : kLongText)[word & 255u]);
+                    me + "fragment " + std::to_string(line >> 1) + " mate " + (line & 1u ? "B " : "A ") + line_defect(invalid, word, "its quality"));
     }
     const uint64_t total = back[0];
-    *out_bytes = total;
-    if (out_line_off) FM_HIP(hipMemcpyAsync(out_line_off, doff, (lines + 1) * 8, hipMemcpyDefault, stream));
-    if (!out && !capacity) { FM_HIP(hipStreamSynchronize(stream)); return 0; }
-    if (total > capacity) {
-        FM_HIP(hipStreamSynchronize(stream));
-        return fail(FMGPU_ERR_CAPACITY, "the text takes " + std::to_string(total) + " bytes: more than `capacity`");
-    }
+    bool write;
+    if ((rc = text_tail(total, doff, lines, out, capacity, out_bytes, out_line_off, sout, stream, &write)) || !write) return rc;
     FM_HIP(hipStreamSynchronize(stream));
     const uint8_t* const qbufs[2] = {spec->qbuf_a, spec->qbuf_b};    // the offsets do not decrease: a batch ends at the last of them
     for (int s = 0; s < (inter ? 1 : 2); ++s) {
@@ -474,10 +390,8 @@ int fmgpu_positions_sam_mates(const fmgpu_position* positions_a, uint64_t count_
         a.qbuf[s] = sq[s].dev ? (const uint8_t*)sq[s].dev : qbufs[s];  // (a batch without a symbol: the pointer is never read through)
     }
     if (inter) a.qbuf[1] = a.qbuf[0];
-    if ((rc = sout.out(out, total, stream))) { (void)hipStreamSynchronize(stream); return rc; }
     uint8_t* const dout = (uint8_t*)sout.dev;
-    const uint64_t windows = ((reinterpret_cast<uintptr_t>(dout) & 15u) + total + kTextWindow - 1) / kTextWindow;
-    FM_GRID(wgrid, windows * 256);
+    FM_GRID(wgrid, text_windows(dout, total) * 256);
     k_sm_write<<<wgrid, dim3(256), 0, stream>>>(a, small.as<uint8_t>(), doff, total, dout);
     FM_LAUNCHED("k_sm_write");
     if ((rc = sout.finish())) return rc;

@@ -74,6 +74,10 @@ def test_filters_and_cuts():
         res = agree(pos, spans, nq, **kw)
         assert len(res) != len(every)
     assert (agree(pos, spans, nq, max_anchors=64).cls == 3).sum() >= 5 and (agree(pos, spans, nq, min_score=1 << 31).cls == 2).sum() >= len(RUNS)
+    # 257 queries: the highest query number is 2^8, one key bit more in the last sort than 256 queries take; anchors in the first query and in the last two
+    rng = np.random.default_rng(9)
+    pos, spans = cases.pack(cases.run_anchors(rng, 5, 0, 1) + cases.run_anchors(rng, 40, 255, 2) + cases.run_anchors(rng, 3, 256, 0), rng)
+    assert agree(pos, spans, 257).cls[[0, 1, 255, 256]].tolist() == [1, 0, 1, 1]
 
 
 def exact_lookback_rows(lookback, further):

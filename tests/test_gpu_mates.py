@@ -71,6 +71,9 @@ def test_runs_that_straddle_the_workgroup_edge_and_empty_mates_everywhere():
     assert check(none, qa, none, qb).cls.tolist() == [0] * n
     # one fragment, one record each
     check(make_side([1], 5, nseq=1, span=300), make_qoff(1, 5), make_side([1], 6, nseq=1, span=300), make_qoff(1, 6), orientation="any")
+    # 257 fragments: the highest read number is 2^8, one key bit more in the last sort than 256 fragments take; the last fragment has records on both sides
+    many = check(make_side([2] * 257, 7, nseq=1, span=300), make_qoff(257, 7), make_side([2] * 257, 8, nseq=1, span=300), make_qoff(257, 8), orientation="any")
+    assert many.cls[256] == 4 and many.cls[255] == 4
 
 
 @pytest.mark.parametrize("strands", [True, False])
@@ -123,6 +126,13 @@ def test_positions_above_2_32_and_below_max_tlen():
     qa, qb = make_qoff(n, 34), make_qoff(n, 35)
     got = check(far_a, qa, far_b, qb, device=("a", "b"), orientation="any", max_tlen=600)
     assert len(got) > 0 and (got.pairs["tlen"] <= 600).all()
+    # seq_id of 2^32 and more, in the opposite order of their low 32 bits: an order of the B side by fewer than 64 bits would misplace every run
+    wide = np.array([(1 << 33) + 1, (1 << 32) + 3, 5], dtype=np.uint64)
+    wide_a, wide_b = far_a.copy(), far_b.copy()
+    wide_a["seq_id"], wide_b["seq_id"] = wide[far_a["seq_id"]], wide[far_b["seq_id"]]
+    for device in ((), ("b",), ("a", "b", "qoff")):
+        assert len(check(wide_a, qa, wide_b, qb, device=device, orientation="any", max_tlen=600)) == len(got)
+    assert len(check(wide_a, qa, wide_b, qb, best=True, max_tlen=600)) > 0             # FR and best: the walks' bisection on the 64-bit seq_id
     # the highest pos the call takes, and a window that reaches below 0: p(a) < max_tlen clamps to 0
     edge_a, edge_b = make_side(per_a, 36, span=300), make_side(per_b, 37, span=300)
     assert len(check(edge_a, qa, edge_b, qb, orientation="any", max_tlen=1000)) > 0
@@ -254,6 +264,8 @@ def test_what_the_device_refuses_names_the_array_and_the_lowest_offender():
         (spoil(ra, 5, pos=1 << 62), spoil(rb, 1, pos=(1 << 64) - 1), qa, qb),                # both arrays: A is named
         (spoil(ra, 5, pos=1 << 62), spoil(rb, 7, qidx=0), bad_q, qb),                        # pos in A, order in B, qoff_a: the kinds in the header's order
         (ra, spoil(rb, len(rb) - 1, qidx=1 << 40), qa, qb),
+        (ra, spoil(rb, 3, pos=1 << 62), qa, qb),                                             # array B alone: its own word
+        (spoil(ra, 9, qidx=2 * n), spoil(rb, 2, qidx=2 * n), qa, qb),                        # beyond the batch in both arrays: A is named
     ]
     for a, b, q1, q2 in cases:
         with pytest.raises(model.MatesError) as e:

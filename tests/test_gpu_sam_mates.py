@@ -216,7 +216,8 @@ def test_every_output_alignment_and_the_guard_bytes():
     da, db, dp = dev(case["rec_a"]), dev(case["rec_b"]), dev(case["pairs"])
     spec, keep = raw_spec(case, batch_a=tuple(dev(x) for x in case["batch_a"]), batch_b=tuple(dev(x) for x in case["batch_b"]))
     guard = 64
-    for shift in range(16):
+
+    def at_alignment(spec, want, shift):
         fill = np.full(guard + 16 + len(want) + guard, 0xAA, dtype=np.uint8)
         buf = DeviceBuffer.from_array(fill)
         assert buf.ptr % 256 == 0
@@ -225,6 +226,24 @@ def test_every_output_alignment_and_the_guard_bytes():
         back = buf.to_array(np.uint8, fill.size)
         assert back[guard + shift: guard + shift + got].tobytes() == want, shift
         assert (back[: guard + shift] == 0xAA).all() and (back[guard + shift + got:] == 0xAA).all(), shift
+    for shift in range(16):
+        at_alignment(spec, want, shift)
+    # names of 100 .. 400 bytes on the same short reads: QNAME and RNAME are copied by their lane, the part inside the workgroup's window, and some lie across the edges
+    # between windows.  That some do is asserted from the model's text alone, for an aligned and for an odd output address, before the device is asked.
+    rng = np.random.default_rng(7)
+    long_names = lambda count: fm.pack_names([bytes(rng.integers(33, 127, size=int(rng.integers(100, 401))).astype(np.uint8)) for _ in range(count)])  # noqa: E731
+    named = dict(case, read_names=long_names(n), seq_names=long_names(4))
+    long_want, long_off = expected(named)
+    long_spec, long_keep = raw_spec(named, batch_a=tuple(dev(x) for x in case["batch_a"]), batch_b=tuple(dev(x) for x in case["batch_b"]))
+    for shift in (0, 5):
+        edges = range(WINDOW - shift, len(long_want), WINDOW)                # in bytes of the text: windows are cut from the 16-byte piece that holds its first byte
+        crossing = {"QNAME": 0, "RNAME": 0}
+        for l in range(len(long_off) - 1):
+            f = long_want[long_off[l]: long_off[l + 1]].split(b"\t")
+            for field, start, size in (("QNAME", long_off[l], len(f[0])), ("RNAME", long_off[l] + len(f[0]) + len(f[1]) + 2, len(f[2]))):
+                crossing[field] += any(start < e < start + size for e in edges)
+        assert len(edges) >= 4 and crossing["QNAME"] >= 1 and crossing["RNAME"] >= 1, (shift, crossing)
+        at_alignment(long_spec, long_want, shift)
     # records at an odd multiple of 8 bytes: no 16-byte loads there
     pad = DeviceBuffer.from_array(np.concatenate([np.zeros(8, dtype=np.uint8), case["rec_a"].view(np.uint8)]))
     out = np.zeros(len(want), dtype=np.uint8)
