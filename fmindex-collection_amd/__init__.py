@@ -20,7 +20,7 @@ from . import search_scheme  # noqa: F401
 __all__ = ["FMIndex", "BiFMIndex", "search_no_errors", "search_backtracking", "search_ng26", "search_ng21", "search", "search_n", "search_best", "search_smems", "search_hamming_sm", "ScoringMatrix", "LocateLinear", "search_locate", "reconstruct_text",
            "search_scheme", "FmgpuError", "DeviceBuffer", "flatten", "device_count", "Replicas", "options",
            "PackedQueries", "pack_queries", "unpack_queries", "pack_queries_device", "Feed", "PinnedBuffer",
-           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "join_mates", "MatePairs", "format_sam_mates", "chain_seeds", "SeedChains", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
+           "symbol_table", "parse_queries", "parse_stream", "ParsedQueries", "MappedText", "TextError", "format_positions", "pack_names", "format_sam", "sam_header", "char_table", "join_mates", "MatePairs", "format_sam_mates", "chain_seeds", "SeedChains", "align_chains", "ChainAlignments", "LINES", "FASTA", "FASTQ", "DROP", "FOREIGN"]
 
 
 class _Options:
@@ -1798,6 +1798,107 @@ def chain_seeds(positions, spans, nq, max_gap=5000, max_skew=500, gap_cost=0.5, 
     if want_anchors:
         anchors = np.ascontiguousarray(anchors[: int(chains["n_anchors"].sum(dtype=np.uint64))])
     return SeedChains(chains[: int(total.value)], off, cls[:nq], anchors)
+
+
+# ---- seed chains to CIGAR alignments on the device (fmgpu_chains_align)
+class ChainAlignments:
+    """what align_chains returns: alignments (a CHAIN_ALIGNMENT_DTYPE array, one record per chain in chain order: first_op, n_ops, status, n_match, n_mismatch, n_ins,
+    n_del) and ops (uint32, len << 4 | code with BAM's codes I = 1, D = 2, S = 4, '=' = 7, X = 8; chain k's at [first_op, first_op + n_ops))"""
+
+    def __init__(self, alignments, ops):
+        self.alignments, self.ops = alignments, ops
+
+    def __len__(self):
+        return len(self.alignments)
+
+    def ops_of(self, k):
+        """the operations of chain k as (length, code) pairs; none for a chain that was left out (status 1)"""
+        r = self.alignments[k]
+        w = self.ops[int(r["first_op"]): int(r["first_op"]) + int(r["n_ops"])]
+        return [(int(x) >> 4, int(x) & 15) for x in w]
+
+    def cigar(self, k, extended=True):
+        """the CIGAR string of chain k: with '=' and 'X', or (extended=False, for SAM) both folded into 'M'.  '*' for a chain that was left out"""
+        ops = self.ops_of(k)
+        if not ops:
+            return "*"
+        if extended:
+            return "".join("%d%s" % (n, capi.OP_CHARS[c]) for n, c in ops)
+        out = []
+        for n, c in ops:
+            ch = "M" if c in (capi.OP_EQ, capi.OP_X) else capi.OP_CHARS[c]
+            if out and out[-1][1] == ch:
+                out[-1][0] += n
+            else:
+                out.append([n, ch])
+        return "".join("%d%s" % (n, ch) for n, ch in out)
+
+
+def align_chains(index, chained, positions, spans, queries, band=64, max_gap_len=5000, max_cells=1 << 24, text=None, stream=None):
+    """fmgpu_chains_align: every chain of chain_seeds aligned between its ends, on the device: the anchors are exact matches, the gaps between consecutive anchors are
+    aligned globally with unit costs on a band of `band` diagonals around the gap's own, and each chain becomes one line of operations with soft clips at the read's
+    ends.  chained: what chain_seeds returned (with its anchors), or (chains, anchors) as arrays or DeviceBuffers; positions and spans: what chain_seeds read; queries:
+    the batch in the numbering of qidx ((qbuf, qoff) or a list of sequences: the doubled batch for both_strands).  text=None reads the window of every chain from
+    `index` with ONE extract call (the extract table is built for the call if the index lacks it, and dropped again); text=(tbuf, toff) hands the windows in (window c
+    at tbuf[toff[c]:toff[c + 1]], arrays or DeviceBuffers) and needs no index.  A chain with a gap longer than max_gap_len on either side, or whose band holds more than
+    max_cells cells, is left out (status 1).  Returns a ChainAlignments (alignments, ops); the counting call sizes `ops` exactly."""
+    if isinstance(chained, SeedChains):
+        if chained.anchors is None:
+            raise ValueError("chain_seeds(want_anchors=False) kept no anchors")
+        chains, anchors = chained.chains, chained.anchors
+    else:
+        chains, anchors = chained
+    if isinstance(chains, np.ndarray):
+        chains = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+    if isinstance(anchors, np.ndarray):
+        anchors = np.ascontiguousarray(anchors, dtype=np.uint32)
+    cp, cbytes = _buffer(chains)
+    n_chains = cbytes // CHAIN_DTYPE.itemsize
+    ap, abytes = _buffer(anchors)
+    n_anchor = abytes // 4
+    pp, count, keep_p = _records(positions)
+    if isinstance(spans, np.ndarray):
+        spans = np.ascontiguousarray(spans, dtype=SEED_SPAN_DTYPE)
+    sp_ptr, sp_bytes = _buffer(spans)
+    n_spans = sp_bytes // SEED_SPAN_DTYPE.itemsize
+    if isinstance(queries, PackedQueries):
+        raise ValueError("align_chains takes the byte form of the batch")
+    qbuf, qoff, nq = _queries(queries)
+    if isinstance(qoff, np.ndarray):
+        qoff = _u64(qoff)
+    if isinstance(qbuf, np.ndarray):
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+    if n_chains == 0:
+        return ChainAlignments(np.zeros(0, dtype=capi.CHAIN_ALIGNMENT_DTYPE), np.zeros(0, dtype=np.uint32))
+    if text is None:
+        host = chains if isinstance(chains, np.ndarray) else chains.to_array(CHAIN_DTYPE, n_chains)
+        built = not (index.formats & capi.FMT_EXTRACT)
+        if built:
+            index.accelerate_extract()
+        try:
+            tbuf, toff = index.extract(host["seq_id"], host["tbeg"], host["tend"] - host["tbeg"])
+        finally:
+            if built:
+                index.accelerate_extract(False)
+        if tbuf.size == 0:
+            tbuf = np.zeros(1, dtype=np.uint8)
+    else:
+        tbuf, toff = text
+        if isinstance(toff, np.ndarray):
+            toff = _u64(toff)
+        if isinstance(tbuf, np.ndarray):
+            tbuf = np.ascontiguousarray(tbuf, dtype=np.uint8)
+    spec = capi.AlignSpec(max(nq, 0), int(max_cells), int(band), int(max_gap_len), (C.c_uint8 * 8)())
+    st = None if stream is None else C.c_void_p(stream if isinstance(stream, int) else getattr(stream, "cuda_stream", 0))
+    L, total = capi.lib(), C.c_uint64()
+    out = np.zeros(n_chains, dtype=capi.CHAIN_ALIGNMENT_DTYPE)
+    args = (cp, n_chains, ap, n_anchor, pp, count, sp_ptr if n_spans else None, n_spans, _buffer(qbuf)[0], _buffer(qoff)[0], _buffer(tbuf)[0], _buffer(toff)[0], C.byref(spec),
+            capi.ptr(out))
+    capi.check(L.fmgpu_chains_align(*args, None, 0, C.byref(total), st))                                  # the counting call sizes the operations exactly
+    ops = np.zeros(max(int(total.value), 1), dtype=np.uint32)
+    capi.check(L.fmgpu_chains_align(*args, capi.ptr(ops), int(total.value), C.byref(total), st))
+    del keep_p
+    return ChainAlignments(out, ops[: int(total.value)])
 
 
 # ---- positions and mate pairs to paired-end SAM records on the device (fmgpu_positions_sam_mates)

@@ -236,6 +236,26 @@ class ChainSpec(C.Structure):
 
 
 assert C.sizeof(ChainSpec) == 48
+
+
+class ChainAlignment(C.Structure):
+    """fmgpu_chain_alignment: where a chain's operations stand, its status and the bases under =, X, I and D (fmgpu_chains_align)"""
+    _fields_ = [("first_op", C.c_uint64), ("n_ops", C.c_uint32), ("status", C.c_uint32), ("n_match", C.c_uint32), ("n_mismatch", C.c_uint32), ("n_ins", C.c_uint32),
+                ("n_del", C.c_uint32)]
+
+
+CHAIN_ALIGNMENT_DTYPE = np.dtype([("first_op", "<u8"), ("n_ops", "<u4"), ("status", "<u4"), ("n_match", "<u4"), ("n_mismatch", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4")])
+assert CHAIN_ALIGNMENT_DTYPE.itemsize == C.sizeof(ChainAlignment) == 32
+
+
+class AlignSpec(C.Structure):
+    """fmgpu_align_spec: the read count, the band and the two guards of fmgpu_chains_align (host memory)"""
+    _fields_ = [("nq", C.c_uint64), ("max_cells", C.c_uint64), ("band", C.c_uint32), ("max_gap_len", C.c_uint32), ("reserved", C.c_uint8 * 8)]
+
+
+assert C.sizeof(AlignSpec) == 32
+OP_I, OP_D, OP_S, OP_EQ, OP_X = 1, 2, 4, 7, 8                    # BAM's operation codes: an operation is len << 4 | code
+OP_CHARS = {OP_I: "I", OP_D: "D", OP_S: "S", OP_EQ: "=", OP_X: "X"}
 CHAIN_CLASSES = ("none", "chained", "filtered", "skipped")
 MATES_FR, MATES_ANY = 0, 1
 MATE_CLASSES = ("none", "only_a", "only_b", "discordant", "paired", "skipped")
@@ -271,6 +291,7 @@ EXPORTS = [
     "fmgpu_positions_mates",
     "fmgpu_positions_sam_mates",
     "fmgpu_seeds_chain",
+    "fmgpu_chains_align",
 ]
 
 # fmgpu_option (include/fmgpu.h) and the defaults the library starts with
@@ -442,6 +463,9 @@ def lib():
     if hasattr(L, "fmgpu_seeds_chain"):
         L.fmgpu_seeds_chain.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(ChainSpec), C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
+    if hasattr(L, "fmgpu_chains_align"):
+        L.fmgpu_chains_align.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.POINTER(AlignSpec), C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p]
     L.fmgpu_set_option.argtypes = [C.c_int32, C.c_int64]
     L.fmgpu_get_option.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
     L.fmgpu_index_formats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

@@ -38,6 +38,8 @@
 //   * --chain-seeds (not in the reference; --mode map, not --packed, --feed, --pair-strands, --device-format, --sam or --mates): in place of the scheme search the
 //     seeds of every read (fmgpu_search_smems: --min_seed, default 19; --max_seed_rows, default 50) are located (fmgpu_locate_hits) and joined to collinear chains on
 //     the device (fmgpu_seeds_chain through fmc::chainSeeds).  --save_output gets "qidx seq_id tbeg tend qbeg qend score n_anchors" per chain.
+//   * --align-chains (not in the reference; only with --chain-seeds): every chain is aligned between its ends on the device (fmgpu_chains_align through
+//     fmc::alignChains, the text under the chains read from the index); each line of --save_output gains "status n_match n_mismatch n_ins n_del cigar".
 //   * --paired-sam (not in the reference; only with --mates): the --save_output file is a paired-end SAM file instead of the pair lines: the header of --sam
 //     followed by two records per fragment made on the device (fmgpu_positions_sam_mates through fmc::formatSamMates) from the positions of the two files and the
 //     joined pairs: a fragment with pairs takes the one with the fewest errors and is proper, elsewhere each mate takes its primary record.  QNAME = the fragment's
@@ -79,7 +81,7 @@ struct Options {
     size_t readLimit = 0, trimTo = 0, hitsPerRead = 0;          // 0 = no limit
     size_t minTlen = 0, maxTlen = 1000;                          // --mates: the template lengths of a concordant pair, inclusive
     size_t minSeed = 19, maxSeedRows = 50;                       // --chain-seeds: the shortest seed kept, the most rows a kept seed may have (0 = no limit)
-    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false, sam = false, pairedSam = false, chainSeeds = false;
+    bool withReverseComplement = true, unknownToA = false, wantHelp = false, packed = false, feed = false, deviceParse = false, pairStrands = false, deviceFormat = false, sam = false, pairedSam = false, chainSeeds = false, alignChains = false;
     HitMode hitMode = HitMode::all;
 };
 
@@ -130,6 +132,7 @@ FlagRule const kFlags[] = {
     {"--min_tlen", true, [](Options& o, char const* v) { o.minTlen = asCount(v); }},
     {"--max_tlen", true, [](Options& o, char const* v) { o.maxTlen = asCount(v); }},
     {"--chain-seeds", false, [](Options& o, char const*) { o.chainSeeds = true; }},
+    {"--align-chains", false, [](Options& o, char const*) { o.alignChains = true; }},
     {"--min_seed", true, [](Options& o, char const* v) { o.minSeed = asCount(v); }},
     {"--max_seed_rows", true, [](Options& o, char const* v) { o.maxSeedRows = asCount(v); }},
     // accepted for compatibility; nothing to switch in this build (no index cache file, no host threads, one String type)
@@ -487,18 +490,36 @@ struct Run {
         double const tLocate = clock.reset();
         fmc::ChainSpec spec;
         spec.queries = reads.size();
-        spec.wantAnchors = false;
+        spec.wantAnchors = config.alignChains;
         auto const chained = fmc::chainSeeds(anchors, spans, spec);
         double const tChain = clock.reset();
+        // --align-chains: every chain aligned between its ends (fmgpu_chains_align through fmc::alignChains, the text read from the index); the lines of --save_output
+        // gain "status n_match n_mismatch n_ins n_del cigar"
+        fmc::ChainAlignments aligned;
+        if (config.alignChains) aligned = fmc::alignChains(index, chained, anchors, spans, reads);
+        double const tAlign = clock.reset();
         size_t const with = static_cast<size_t>(std::count(chained.classes.begin(), chained.classes.end(), uint8_t{1}));
         std::printf("%-15s %3zu: %10.3gs (%10.3gs +%10.3gs +%10.3gs ) - seeds: %10zu anchors: %10zu chains: %10zu in %10zu of %10zu queries\n", "chain-seeds", k,
                     tSeeds + tLocate + tChain, tSeeds, tLocate, tChain, seeds.size(), anchors.size(), chained.chains.size(), with, reads.size());
+        if (config.alignChains) {
+            size_t out = 0;
+            for (auto const& r : aligned.alignments) out += r.status != 0;
+            std::printf("%-15s %3zu: %10.3gs - chains: %10zu left out: %10zu operations: %10zu\n", "align-chains", k, tAlign, aligned.alignments.size(), out, aligned.ops.size());
+        }
         if (config.outputFile.empty()) return;
         auto* out = std::fopen(config.outputFile.c_str(), "w");
         if (!out) throw std::runtime_error("cannot write " + config.outputFile);
-        for (auto const& c : chained.chains)
-            std::fprintf(out, "%zu %zu %zu %zu %zu %zu %zu %zu\n", static_cast<size_t>(c.qidx), static_cast<size_t>(static_cast<uint32_t>(c.seq_id)), static_cast<size_t>(c.tbeg),
+        for (size_t i = 0; i < chained.chains.size(); ++i) {
+            auto const& c = chained.chains[i];
+            std::fprintf(out, "%zu %zu %zu %zu %zu %zu %zu %zu", static_cast<size_t>(c.qidx), static_cast<size_t>(static_cast<uint32_t>(c.seq_id)), static_cast<size_t>(c.tbeg),
                          static_cast<size_t>(c.tend), static_cast<size_t>(c.qbeg), static_cast<size_t>(c.qend), static_cast<size_t>(c.score), static_cast<size_t>(c.n_anchors));
+            if (config.alignChains) {
+                auto const& r = aligned.alignments[i];
+                std::fprintf(out, " %zu %zu %zu %zu %zu %s", static_cast<size_t>(r.status), static_cast<size_t>(r.n_match), static_cast<size_t>(r.n_mismatch),
+                             static_cast<size_t>(r.n_ins), static_cast<size_t>(r.n_del), aligned.cigar(i).c_str());
+            }
+            std::fputc('\n', out);
+        }
         std::fclose(out);
     }
 
@@ -634,6 +655,8 @@ int main(int argc, char const* const* argv) try {
                     "          --chain-seeds (--mode map, not --packed, --feed, --pair-strands, --device-format, --sam or --mates: in place of the scheme search\\\n"
                     "                 the seeds of every read are located and joined to collinear chains on the device: --save_output gets\\\n"
                     "                 \"qidx seq_id tbeg tend qbeg qend score n_anchors\" per chain)\\\n"
+                    "          --align-chains (only with --chain-seeds: every chain aligned between its ends on the device; each line of --save_output gains\\\n"
+                    "                 \"status n_match n_mismatch n_ins n_del cigar\")\\\n"
                     "          --min_seed <int> --max_seed_rows <int> (--chain-seeds: the shortest seed kept, the most rows of a kept seed; 19 and 50)\\\n"
                     "          --maxhitperquery <int> (some int, 0 = infinite hits)\n");
         return 0;
@@ -648,6 +671,7 @@ int main(int argc, char const* const* argv) try {
     if (config.pairedSam && config.matesFasta.empty()) throw std::runtime_error("--paired-sam needs --mates");
     if (config.minTlen > config.maxTlen) throw std::runtime_error("--min_tlen lies above --max_tlen");
     if (config.chainSeeds && config.hitMode != HitMode::map) throw std::runtime_error("--chain-seeds needs --mode map");
+    if (config.alignChains && !config.chainSeeds) throw std::runtime_error("--align-chains needs --chain-seeds");
     if (config.chainSeeds && (config.packed || config.feed || config.pairStrands || config.deviceFormat || config.sam || !config.matesFasta.empty()))
         throw std::runtime_error("--chain-seeds needs byte reads (no --packed) and does not go with --feed, --pair-strands, --device-format, --sam or --mates");
     auto withReference = [&](Run& run) {                              // --sam: what the header and RNAME are made of

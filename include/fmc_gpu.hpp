@@ -1506,6 +1506,72 @@ inline auto chainSeeds(std::vector<fmgpu_position> const& positions, std::vector
     return out;
 }
 
+// Chain alignments (include/fmgpu.h: fmgpu_chains_align): fmc::alignChains(index, chains, positions, spans, reads, spec) aligns every chain of fmc::chainSeeds between
+// its ends on the device — the anchors are exact matches, the gaps between them small banded dynamic programs — and returns one record per chain and the operations
+// of all chains, len << 4 | op with BAM's codes.  `reads` is the batch in the numbering of qidx (the doubled batch for both-strand mapping).  The text under every
+// chain comes from ONE extract call on `index` (the extract table is built for the call if the index lacks it, and dropped again); the overload without an index takes
+// the windows as (text, offsets): window c at text[offsets[c] .. offsets[c + 1]).
+struct AlignSpec {
+    uint32_t band{64};                                                       // diagonals on either side of a gap's own: 0 .. 65535
+    uint32_t maxGapLen{5000};                                                // 0 .. 65535: a gap with more read or text symbols leaves its chain out (status 1)
+    uint64_t maxCells{uint64_t{1} << 24};                                    // 1 .. 2^30: so does a gap whose band holds more cells
+};
+struct ChainAlignments {
+    std::vector<fmgpu_chain_alignment> alignments;                           // one per chain, in chain order
+    std::vector<uint32_t>              ops;                                  // chain k's at [alignments[k].first_op, + alignments[k].n_ops)
+    // the CIGAR string of chain k: with '=' and 'X', or (extended = false, for SAM) both folded into 'M'; "*" for a chain that was left out
+    auto cigar(size_t k, bool extended = true) const -> std::string {
+        auto const& r = alignments.at(k);
+        if (r.n_ops == 0) return "*";
+        std::string out;
+        uint64_t run = 0; char last = 0;
+        auto flush = [&]() { if (run) out += std::to_string(run) + last; run = 0; };
+        for (uint64_t i = r.first_op; i < r.first_op + r.n_ops; ++i) {
+            const uint32_t op = ops[i] & 15u;
+            char c = op == FMGPU_OP_I ? 'I' : op == FMGPU_OP_D ? 'D' : op == FMGPU_OP_S ? 'S' : op == FMGPU_OP_EQ ? '=' : 'X';
+            if (!extended && (c == '=' || c == 'X')) c = 'M';
+            if (c != last) flush();
+            last = c; run += ops[i] >> 4;
+        }
+        flush();
+        return out;
+    }
+};
+inline auto alignChains(SeedChains const& chains, std::vector<fmgpu_position> const& positions, std::vector<fmgpu_seed_span> const& spans,
+                        std::vector<std::vector<uint8_t>> const& reads, std::vector<uint8_t> const& text, std::vector<uint64_t> const& textOffsets,
+                        AlignSpec const& spec = {}) -> ChainAlignments {
+    std::vector<uint8_t> buf; std::vector<uint64_t> off;
+    detail::flatten(reads, buf, off);
+    if (buf.empty()) buf.push_back(0);
+    fmgpu_align_spec s{};
+    s.nq = reads.size(); s.band = spec.band; s.max_gap_len = spec.maxGapLen; s.max_cells = spec.maxCells;
+    ChainAlignments out;
+    const uint64_t n = chains.chains.size();
+    if (n && textOffsets.size() != n + 1) throw std::runtime_error("fmindex-collection (gpu): alignChains takes one text window per chain");
+    out.alignments.resize(n);
+    std::vector<uint8_t> none(1, 0);
+    uint8_t const* t = text.empty() ? none.data() : text.data();
+    auto call = [&](uint32_t* ops, uint64_t capacity, uint64_t* count) {
+        return fmgpu_chains_align(chains.chains.data(), n, chains.anchors.data(), chains.anchors.size(), positions.data(), positions.size(), spans.data(), spans.size(),
+                                  buf.data(), off.data(), t, textOffsets.data(), &s, out.alignments.data(), ops, capacity, count, nullptr);
+    };
+    uint64_t count = 0;
+    detail::check(call(nullptr, 0, &count));                                 // the counting call sizes the operations exactly
+    out.ops.resize(count);
+    if (count) detail::check(call(out.ops.data(), count, &count));
+    return out;
+}
+template <typename Index>
+auto alignChains(Index const& index, SeedChains const& chains, std::vector<fmgpu_position> const& positions, std::vector<fmgpu_seed_span> const& spans,
+                 std::vector<std::vector<uint8_t>> const& reads, AlignSpec const& spec = {}) -> ChainAlignments {
+    std::vector<fmgpu_text_range> ranges;
+    std::vector<uint64_t> offsets(1, 0);
+    for (auto const& c : chains.chains) { ranges.push_back(fmgpu_text_range{c.seq_id, c.tbeg, c.tend - c.tbeg}); offsets.push_back(offsets.back() + (c.tend - c.tbeg)); }
+    std::vector<uint8_t> text;
+    if (!ranges.empty()) text = detail::extractWithTable(index, ranges);
+    return alignChains(chains, positions, spans, reads, text, offsets, spec);
+}
+
 // Paired-end SAM (include/fmgpu.h: fmgpu_positions_sam_mates): fmc::formatSamMates(positionsA, readsA, positionsB, readsB, pairs, spec) is two alignment lines per
 // fragment, line 2f for mate A and line 2f + 1 for mate B, with the mate fields filled in (flags 1, 2, 8, 32, 64, 128, RNEXT, PNEXT, TLEN), formatted on the device from
 // the positions fmc::map returned for the two FORWARD batches and the pairs fmc::joinMates made of them (its result, or any array of pair records).  A fragment with

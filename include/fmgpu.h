@@ -1290,7 +1290,8 @@ int fmgpu_positions_sam_mates(const fmgpu_position* positions_a, uint64_t count_
  *     rest of the batch.  max_anchors is the caller's guard for it, beside fmgpu_search_smems' max_rows.
  *   - The call returns after completion and frees its scratch: 85 bytes per anchor (24 the sorts, 16 the anchor record, 45 the sweeps' and the passes' words), 25 per
  *     query, 12 per reported chain, plus hipcub's own.
- * Not built: extension or alignment of chains, chains across the two strands of a query, MAPQ, chaining inside fmgpu_map or the feeds, rescue of an unmapped mate. */
+ * Not built: extension of chains past their ends (fmgpu_chains_align below aligns what lies between a chain's ends), chains across the two strands of a query, MAPQ,
+ * chaining inside fmgpu_map or the feeds, rescue of an unmapped mate. */
 typedef struct fmgpu_chain {               /* 56 bytes */
     uint64_t qidx, seq_id;
     uint64_t tbeg, tend;                   /* pos of the first anchor; pos + qlen of the last */
@@ -1320,6 +1321,91 @@ int fmgpu_seeds_chain(const fmgpu_position* positions, uint64_t count,
                       uint64_t* out_off,      /* NULL, or nq + 1 entries */
                       uint8_t* out_class,     /* NULL, or nq bytes */
                       void* stream);
+
+/* ---- seed chains to CIGAR alignments on the device ---------------------------------------------------------------------------------------------
+ * fmgpu_chains_align takes the chains and anchors fmgpu_seeds_chain wrote, the positions and spans that call read, the query batch and the text under every chain, and
+ * returns one alignment per chain: the read from its first to its last symbol against the text window [tbeg, tend), as BAM-coded operations.  The anchors of a chain are
+ * exact matches; what is aligned are the gaps between consecutive anchors, each a small banded dynamic program of its own.  It needs no index handle.  Every other call
+ * and struct is as it was.
+ *   - Input: chains[n_chains] and anchors[n_anchor] as fmgpu_seeds_chain wrote them (out and out_anchor); positions[count] and spans[n_spans] as that call read them;
+ *     qbuf / qoff: spec->nq reads in the numbering of qidx (the doubled batch for both-strand mapping: the call knows nothing of strands), read r at qbuf[qoff[r] ..
+ *     qoff[r + 1]); tbuf / toff: window c, the ranks of the text [tbeg, tend) of chain c, at tbuf[toff[c] .. toff[c + 1]); toff[0] need not be 0.  This is what ONE
+ *     fmgpu_extract call returns for the ranges {seq_id, tbeg, tend - tbeg} in chain order.
+ *   - The rule.  For chain c with anchors k = 0 .. n - 1 (anchor k = positions[anchors[first + k]]: q_k = its span's qbeg, l_k = its span's qlen, t_k = pos), m the
+ *     length of read qidx, Q the read and T the window (T[x] is text position tbeg + x):
+ *       Pieces: l'_k = min(l_k, q_{k+1} - q_k, t_{k+1} - t_k) for k < n - 1, l'_{n-1} = l_{n-1}: the term the chain score uses.  Piece k matches Q[q_k, q_k + l'_k) to
+ *       T[t_k, t_k + l'_k).  Pieces never overlap and none is empty, and each anchor decides from its successor alone.
+ *       Gaps: gap k lies between piece k and piece k + 1: gq = q_{k+1} - q_k - l'_k read symbols, gt = t_{k+1} - t_k - l'_k text symbols.  gq = 0 gives `D gt` when
+ *       gt > 0, gt = 0 gives `I gq` when gq > 0, both 0 give nothing.  Otherwise the gap is aligned globally with unit costs on the band lo <= b - a <= hi, lo =
+ *       min(0, gt - gq) - band, hi = max(0, gt - gq) + band (a read symbols and b text symbols consumed): D(0, 0) = 0, D(a, b) = the minimum over its in-band
+ *       predecessors of D(a - 1, b - 1) + [Q != T], D(a, b - 1) + 1, D(a - 1, b) + 1.  The traceback runs from (gq, gt) and takes at each cell the first that applies:
+ *       the diagonal if a, b > 0 and D(a - 1, b - 1) + [Q != T] = D(a, b): `=` or `X`; else the left cell if b > 0, (a, b - 1) is in the band and D(a, b - 1) + 1 =
+ *       D(a, b): `D`; else `I`.  With ties the traceback is the definition: the output is reproducible to the byte.
+ *       The line: `S qbeg` (qbeg > 0); per k `= l'_k` and the operations of gap k; `S (m - qend)` (m > qend); then the canonical form: neighbours with the same
+ *       operation are merged and no operation has length 0.  No extension beyond the chain's ends: the clips are soft clips.
+ *       Left out: a chain with a gap of gq > 0 and gt > 0 for which max(gq, gt) > max_gap_len or (gq + 1) * (hi - lo + 1) > max_cells has status 1, n_ops 0 and zero
+ *       counts; its first_op stays in the running sequence.  Every other chain has status 0.
+ *   - Output: out[n_chains], one record per chain in chain order: first_op ascends with c.  out_ops: one uint32_t per operation, len << 4 | op with BAM's codes I = 1,
+ *     D = 2, S = 4, `=` = 7, X = 8.  n_match, n_mismatch, n_ins, n_del count the bases under `=`, X, I and D.  *out_ops_count is exact on success and on
+ *     FMGPU_ERR_CAPACITY alike; on FMGPU_ERR_CAPACITY no operation is written and `out` is still written, with its offsets.  out_ops == NULL with ops_capacity == 0 is
+ *     the counting call.  n_chains == 0 returns 0 behind the checks of the next item, with *out_ops_count = 0.
+ *   - Before the first use of the device, FMGPU_ERR_INVALID, each with a message of its own, for: a null spec or out_ops_count; band or max_gap_len above 65535;
+ *     max_cells outside 1 .. 2^30; reserved != 0; with n_chains > 0 a null chains, anchors, positions,
+ *     spans, qbuf, qoff, tbuf, toff or out; a null out_ops while ops_capacity > 0.  Then FMGPU_ERR_UNSUPPORTED where n_chains, n_anchor, count or n_spans reaches
+ *     2^32 - 256.
+ *   - On the device, FMGPU_ERR_INVALID, looked for in this order; nothing is written (*out_ops_count = 0) and the message names the lowest offending chain:
+ *     (1) n_anchors == 0, first + n_anchors > n_anchor, or the anchors of chains 0 .. c together more than n_anchor; (2) an anchor index >= count; (3) a hit >=
+ *     n_spans, or a span with qlen == 0; (4) qidx >= nq, or an anchor whose qidx / seq_id differs from the chain's; (5) two consecutive anchors not strictly ascending
+ *     in both q and t; (6) tbeg / tend / qbeg / qend not what the first and the last anchor give; (7) qend > m; (8) toff[c + 1] - toff[c] != tend - tbeg; (9) a piece
+ *     whose text differs from the read: the message names the chain and the anchor.  Check 9 makes every returned line a true alignment of the read against the
+ *     window.  A read or a window of 2^28 symbols or more is FMGPU_ERR_UNSUPPORTED (an operation's length has 28 bits).
+ *   - Every array (chains, anchors, positions, spans, qbuf, qoff, tbuf, toff, out, out_ops) may be host or device memory; host arrays are staged.  The spec is host
+ *     memory.
+ *   - Passes: per chain (its own fields, the read, the window); a scan of n_anchors that numbers the (chain, anchor) elements; per element (the anchor's checks, l',
+ *     the piece against the text, gq and gt, trivial gaps settled, the other gaps appended to one of four task lists, left-out chains marked); the gap tasks, COUNTING
+ *     (runs, first and last operation, bases): gaps of up to 15 x 15 one per lane with the matrix's directions in LDS, larger ones one per wave: the lanes across 64
+ *     text columns of a row, the row's left-to-right dependency as a min-plus prefix scan over the lanes, the previous row in the wave's scratch, the directions as two
+ *     ballots per 64 cells (2 bits per cell); per element the operations that remain after merging (flags from the neighbours' first and last operations); a scan; per
+ *     chain its record; ONE read-back (the operation count, the error words); then per element the clips, pieces and trivial gaps, and the gap tasks again, WRITING.
+ *     A writing call fills every matrix twice: nothing between the two passes is kept but 32 bytes per element.  Merged `=` runs are summed with atomic adds into
+ *     zeroed slots.  Where the lane tier ends (15 x 15) is not tuned.
+ *   - The call returns after completion and frees its scratch: 116 bytes per anchor, 49 per chain, plus hipcub's own, plus the traceback scratch: a wave whose gap needs
+ *     up to 16 KiB (directions and one row) keeps it in LDS; above that up to 256 waves take 512 KiB each of a fixed budget of 128 MiB, and gaps that need more than 512 KiB go through
+ *     ONE slice of at most 2^28 + 2^21 bytes one behind the other on one wave: what max_cells guards.  No call takes more than 258 MiB of traceback scratch, and none
+ *     takes more than band, max_gap_len and max_cells can ask for.
+ * Not built: extension past the ends of a chain, affine gaps, CIGAR for the edit-distance hits of the search calls, SAM or PAF lines of chains, alignment inside
+ * fmgpu_map or the feeds. */
+typedef struct fmgpu_chain_alignment {     /* 32 bytes */
+    uint64_t first_op;                     /* the chain's operations are out_ops[first_op .. first_op + n_ops) */
+    uint32_t n_ops;
+    uint32_t status;                       /* 0 aligned; 1 left out by max_gap_len or max_cells */
+    uint32_t n_match, n_mismatch, n_ins, n_del;
+} fmgpu_chain_alignment;
+typedef struct fmgpu_align_spec {          /* 32 bytes, host memory */
+    uint64_t nq;                           /* reads in the numbering of qidx: qoff has nq + 1 entries */
+    uint64_t max_cells;                    /* 1 .. 2^30: a gap whose band holds more cells leaves its chain out */
+    uint32_t band;                         /* w, 0 .. 65535 */
+    uint32_t max_gap_len;                  /* 0 .. 65535: a gap with more read or text symbols leaves its chain out */
+    uint8_t  reserved[8];                  /* 0 */
+} fmgpu_align_spec;
+#ifdef __cplusplus
+static_assert(sizeof(fmgpu_chain_alignment) == 32 && sizeof(fmgpu_align_spec) == 32, "fmgpu_chain_alignment / fmgpu_align_spec: the sizes stated above");
+#endif
+#define FMGPU_OP_I  1u
+#define FMGPU_OP_D  2u
+#define FMGPU_OP_S  4u
+#define FMGPU_OP_EQ 7u
+#define FMGPU_OP_X  8u
+int fmgpu_chains_align(const fmgpu_chain* chains, uint64_t n_chains,
+                       const uint32_t* anchors, uint64_t n_anchor,
+                       const fmgpu_position* positions, uint64_t count,
+                       const fmgpu_seed_span* spans, uint64_t n_spans,
+                       const uint8_t* qbuf, const uint64_t* qoff,
+                       const uint8_t* tbuf, const uint64_t* toff,
+                       const fmgpu_align_spec* spec,
+                       fmgpu_chain_alignment* out,
+                       uint32_t* out_ops, uint64_t ops_capacity, uint64_t* out_ops_count,
+                       void* stream);
 
 /* device memory helpers for callers that keep queries / results resident in HBM; fmgpu_malloc_host / fmgpu_free_host: pinned host memory, what a feed copies from and to in place */
 int fmgpu_malloc(void** ptr, uint64_t bytes);
